@@ -21,10 +21,9 @@ import ctypes as C
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # before HIP initialises: concurrent callers need the queues
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -54,7 +53,8 @@ def respawn(n):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    # a fresh child, not an exec: this process has already brought HIP up to count the devices
+    sys.exit(subprocess.call(cmd))
 
 
 def analytic_traffic(wbits, blobs):
@@ -904,6 +904,15 @@ def emit(full):
     sys.stdout.flush()
 
 
+def dump_outputs(dirname, commitments, status):
+    """What the last timed step handed its caller, untimed: the 48-byte compressed commitments (every rank's on rank 0
+    of a multi-rank run) and rank 0's per-blob status bytes, each byte as one float32 (exact), DIR/<name>.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in (("commitments", commitments), ("status", status)):
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -913,9 +922,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true")
     ap.add_argument("--no-pcie", action="store_true", help="skip the host-pointer (PCIe-inclusive) leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (commitments, per-blob status) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        respawn(args.gpus)  # does not return
+        respawn(args.gpus)  # exits with the ranks' status
 
     import torch
     import torch.distributed as dist
@@ -1036,6 +1049,8 @@ def main():
             if g0 is None or tuple(g0.shape) != (world * BLOBS_PER_STEP, 48) or \
                     not torch.equal(g0[:BLOBS_PER_STEP].cpu(), out.cpu()):
                 raise SystemExit("bench: the gathered commitments on rank 0 are not the ranks' outputs")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out if gathered[0] is None else gathered[0], status)
 
     # the reference-shaped call: pageable host pointers, H2D and D2H inside the timed region, same step count
     host_ptr = None

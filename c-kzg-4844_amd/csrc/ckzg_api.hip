@@ -34,13 +34,6 @@ Options options_snapshot() {
 }  // namespace api
 }  // namespace ckzg
 
-// ROCm multiplexes a process's HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4); streams
-// that share a queue serialise.  Every slot of a pool owns two streams, so the concurrent-caller
-// design needs more queues than the default to overlap: ask for 16 unless the user chose a value.
-// Only effective when this library is loaded before the process's first HIP call; a host that
-// initialises HIP earlier (e.g. imports torch first) sets the variable itself.
-__attribute__((constructor)) static void ckzg_hip_queue_hint() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
-
 extern "C" C_KZG_RET ckzg_hip_set_option(const char *key, int64_t value) {
     if (!key) return C_KZG_BADARGS;
     std::lock_guard<std::mutex> lock(g_opts_mu);

@@ -1109,7 +1109,8 @@ int commit_one_graph_build(DeviceCtx *ctx, hipGraphExec_t *exec_out, uint8_t *d_
     zp.height = 1;
     zp.pitch = n * 4;
     zp.value = 0;
-    HIP_TRY(hipGraphAddMemsetNode(&n_zero, own.g, nullptr, 0, &zp));
+    // a single chain of nodes: no parallel branches for the runtime to spread over hardware queues on replay
+    HIP_TRY(hipGraphAddMemsetNode(&n_zero, own.g, &n_in, 1, &zp));
 
     hipKernelNodeParams kp;
     // k_blob_digits(digits, bad, blobs, total, wbits, twin)
@@ -1122,8 +1123,7 @@ int commit_one_graph_build(DeviceCtx *ctx, hipGraphExec_t *exec_out, uint8_t *d_
     kp.gridDim = dim3((unsigned)((total + 255) / 256));
     kp.blockDim = dim3(256);
     kp.kernelParams = a_digits;
-    hipGraphNode_t dep_digits[] = {n_in, n_zero};
-    HIP_TRY(hipGraphAddKernelNode(&n_digits, own.g, dep_digits, 2, &kp));
+    HIP_TRY(hipGraphAddKernelNode(&n_digits, own.g, &n_zero, 1, &kp));
 
     // k_msm_accumulate<256, true>(partials, table, digits, pairs_per_vec, pairs_per_block, half_shift, blocks_per_vec,
     //                             ppv, npoints, vecs_per_group, part_stride, prio_bit)

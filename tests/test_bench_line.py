@@ -82,3 +82,26 @@ def test_round5_record_also_fits():
     assert out["roofline"]["traffic"] and out["roofline"]["traffic_source"].startswith("profiles/r05_final_pmc")
     assert out["cpu_baseline"]["all_cores"]["driver"].startswith("pthreads")
     assert out["baseline_configs"]["configs[4]_recover_256_ms"] == full["baseline_configs"]["configs[4]"]
+
+
+def test_dump_outputs_writes_exact_float32_arrays(tmp_path):
+    """--dump-outputs DIR: what the last timed step returned, one DIR/<name>.npy per array, bytes exact in float32"""
+    import numpy as np
+    import torch
+    b = _bench()
+    commitments = torch.arange(4 * 48, dtype=torch.int64).remainder(256).to(torch.uint8).reshape(4, 48)
+    status = torch.tensor([0, 1, 0, 255], dtype=torch.uint8)
+    b.dump_outputs(str(tmp_path / "out"), commitments, status)
+    for name, t in (("commitments", commitments), ("status", status)):
+        a = np.load(tmp_path / "out" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == tuple(t.shape)
+        assert np.array_equal(a.astype(np.uint8), t.numpy())
+
+
+def test_steps_must_be_positive(monkeypatch):
+    import pytest
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        b.main()
+    assert e.value.code == 2

@@ -29,7 +29,9 @@ def failalloc_so(tmp_path_factory):
 
 
 def walk(so, sections):
-    env = dict(os.environ, LD_PRELOAD=so, FAILALLOC_SO=so, FAILALLOC_SECTIONS=sections)
+    # (added to whatever the environment already preloads, never in its place)
+    env = dict(os.environ, LD_PRELOAD=(os.environ.get("LD_PRELOAD", "") + " " + so).strip(), FAILALLOC_SO=so,
+               FAILALLOC_SECTIONS=sections)
     r = run_watched([sys.executable, os.path.join(HERE, "failalloc", "driver.py")], env=env, timeout=DEADLINE,
                     name="failalloc_" + sections.replace(",", "+"))
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -16,7 +16,7 @@ TSAN_LIB = os.path.join(ROOT, "c-kzg-4844_amd", "libckzg_hip_tsan.so")
 
 
 def _run(mode):
-    env = {k: v for k, v in os.environ.items() if k not in ("LD_PRELOAD", "CKZG_HIP_SO", "CKZG_SHIM_SO")}
+    env = {k: v for k, v in os.environ.items() if k not in ("CKZG_HIP_SO", "CKZG_SHIM_SO")}
     r = run_watched(["bash", os.path.join(ROOT, "tools", "run_sanitized.sh"), mode], cwd=ROOT, env=env, timeout=2400,
                     name="sanitized_" + mode)
     assert r.returncode == 0 and "sanitizers: clean" in r.stdout, (r.stdout[-3000:], r.stderr[-1000:])

@@ -18,7 +18,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402  (also sets GPU_MAX_HW_QUEUES before HIP starts)
+import bench  # noqa: E402
 
 
 def main():

@@ -10,7 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402  (also sets GPU_MAX_HW_QUEUES before HIP starts)
+import bench  # noqa: E402
 
 
 def main():

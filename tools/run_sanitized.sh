@@ -17,6 +17,8 @@ LOG=gpurun_out/sanitize_$mode.log
 # GCC's runtimes for both libraries (c-kzg-4844_amd/Makefile says why not clang's on a GPU box)
 GCC_RT="$(gcc -print-file-name=libasan.so) $(gcc -print-file-name=libubsan.so)"
 CLANG_RT=$GCC_RT
+# the sanitizer runtime goes first; whatever the environment already preloads stays behind it
+PRELOAD0=${LD_PRELOAD:-}
 export ASAN_OPTIONS=detect_leaks=0:use_sigaltstack=0:abort_on_error=0:detect_odr_violation=0   # use_sigaltstack=0: the HIP runtime's threads trip ASan's alternate-stack teardown
 export UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=0
 if [ "$mode" = tsan ]; then
@@ -27,14 +29,14 @@ if [ "$mode" = tsan ]; then
   echo "== ThreadSanitizer: stress (6 threads, 20 s) + async / fan-out tests" >> $LOG
   # (GCC 11's libtsan does not know the address-space layout of kernels with 32 bits of mmap entropy: no ASLR here)
   NOASLR="setarch $(uname -m) -R"
-  LD_PRELOAD=$TSAN_RT CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_tsan.so CKZG_TESTS_NO_AUTOBUILD=1 \
+  LD_PRELOAD="$TSAN_RT $PRELOAD0" CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_tsan.so CKZG_TESTS_NO_AUTOBUILD=1 \
     timeout 900 $NOASLR python tools/stress_gpu.py 20 6 >> $LOG 2>&1
   echo "rc=$?" >> $LOG
-  LD_PRELOAD=$TSAN_RT CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_tsan.so CKZG_TESTS_NO_AUTOBUILD=1 \
+  LD_PRELOAD="$TSAN_RT $PRELOAD0" CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_tsan.so CKZG_TESTS_NO_AUTOBUILD=1 \
     timeout 1200 $NOASLR python -m pytest tests/test_gpu_round3.py -m gpu -q -x -p no:cacheprovider -k "async or fan_out or pipelined" >> $LOG 2>&1
   echo "rc=$?" >> $LOG
   echo "== ThreadSanitizer: the combiner (concurrent one-blob callers sharing batch launches; native + Python threads)" >> $LOG
-  LD_PRELOAD=$TSAN_RT CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_tsan.so CKZG_TESTS_NO_AUTOBUILD=1 \
+  LD_PRELOAD="$TSAN_RT $PRELOAD0" CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_tsan.so CKZG_TESTS_NO_AUTOBUILD=1 \
     timeout 1500 $NOASLR python -m pytest tests/test_gpu_coalesce.py -m gpu -q -x -p no:cacheprovider >> $LOG 2>&1
   echo "rc=$?" >> $LOG
   tail -15 $LOG
@@ -46,16 +48,16 @@ if [ "$mode" = tsan ]; then
 fi
 if [ "$mode" = cpu ]; then
   echo "== host shim under gcc ASan+UBSan: tests/test_host_arith.py tests/test_fk20_edge_builder.py" >> $LOG
-  LD_PRELOAD="$GCC_RT" CKZG_SHIM_SO=c-kzg-4844_amd/csrc/libhost_shim_san.so CKZG_TESTS_NO_AUTOBUILD=1 \
+  LD_PRELOAD="$GCC_RT $PRELOAD0" CKZG_SHIM_SO=c-kzg-4844_amd/csrc/libhost_shim_san.so CKZG_TESTS_NO_AUTOBUILD=1 \
     timeout 3000 python -m pytest tests/test_host_arith.py tests/test_fk20_edge_builder.py -q -x -p no:cacheprovider >> $LOG 2>&1
   echo "rc=$?" >> $LOG
   echo "== product (host half sanitized) under ASan+UBSan: tests/test_abi_exports.py" >> $LOG
-  LD_PRELOAD="$CLANG_RT" CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_san.so CKZG_TESTS_NO_AUTOBUILD=1 \
+  LD_PRELOAD="$CLANG_RT $PRELOAD0" CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_san.so CKZG_TESTS_NO_AUTOBUILD=1 \
     timeout 600 python -m pytest tests/test_abi_exports.py -q -x -p no:cacheprovider >> $LOG 2>&1
   echo "rc=$?" >> $LOG
 else
   echo "== product (host half sanitized) on the GPU: vectors, fuzz, round-3 verification forms" >> $LOG
-  LD_PRELOAD="$CLANG_RT" CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_san.so CKZG_TESTS_NO_AUTOBUILD=1 HSA_XNACK=0 \
+  LD_PRELOAD="$CLANG_RT $PRELOAD0" CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_san.so CKZG_TESTS_NO_AUTOBUILD=1 HSA_XNACK=0 \
     timeout 1500 python -m pytest tests/test_gpu_vectors.py tests/test_gpu_fuzz.py tests/test_gpu_round3.py -m gpu -q -x -p no:cacheprovider >> $LOG 2>&1
   echo "rc=$?" >> $LOG
 fi

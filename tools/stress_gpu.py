@@ -19,7 +19,6 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import __graft_entry__ as ge  # noqa: E402
 from test_gpu_commitment import rand_blob  # noqa: E402
 
