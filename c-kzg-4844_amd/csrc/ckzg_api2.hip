@@ -692,10 +692,12 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
         RC(dev::sha256_challenges_device(ctx, d_z.p, d_blob_bytes, resident ? reinterpret_cast<const uint8_t *>(d_cb) : d_ptb.p, n,
                                          partition ? ctx->sha_stream : nullptr));
         if (partition) {
-            // (stage_ev[1] is free in these forms: only the split validation of small host-pointer batches records it)
-            if (!ctx->stage_ev[1]) OKB(hipEventCreateWithFlags(&ctx->stage_ev[1], hipEventDisableTiming) == hipSuccess);
-            OKB(hipEventRecord(ctx->stage_ev[1], ctx->sha_stream) == hipSuccess);
-            OKB(hipStreamWaitEvent(ctx->stream, ctx->stage_ev[1], 0) == hipSuccess);   // the challenges, before the evaluation
+            // (an event of its own: stage_ev[1] means "subgroup flags written" in the split validation, which a
+            // host-pointer batch of 640..1023 blobs hashed on the GPU takes together with the partition; recording
+            // the hash there made the flags' read wait for the hash instead of the subgroup test)
+            if (!ctx->hash_ev) OKB(hipEventCreateWithFlags(&ctx->hash_ev, hipEventDisableTiming) == hipSuccess);
+            OKB(hipEventRecord(ctx->hash_ev, ctx->sha_stream) == hipSuccess);
+            OKB(hipStreamWaitEvent(ctx->stream, ctx->hash_ev, 0) == hipSuccess);   // the challenges, before the evaluation
         }
         hash_enqueued = true;
         return C_KZG_OK;

@@ -337,6 +337,7 @@ struct DeviceCtx {
     Arena api_arena, lc_arena;    // temporaries of the host-pointer entry points / of gpu_lincomb_multi
     hipEvent_t stage_ev[4] = {};  // copied[2], consumed[2] of the staging pipeline (created on first use)
     hipEvent_t table_ev = nullptr;      // "the call-time table is complete" (verification; created on first use)
+    hipEvent_t hash_ev = nullptr;       // "the challenges are hashed" (partitioned verification; created on first use)
     std::vector<hipEvent_t> chunk_ev;   // per-chunk events of the pipelined verification (grown on demand, kept)
     hipEvent_t ev[12] = {};       // timing events
     // The one-blob blob_to_kzg_commitment as a graph built node by node (copy in, flag reset, recoding, accumulate, fold +

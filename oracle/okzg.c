@@ -96,6 +96,10 @@ static int validate_kzg_g1(og1_t *out, const uint8_t b[48]) {
     return og1_in_subgroup(out) ? OKZG_OK : OKZG_BADARGS;
 }
 
+int okzg_bytes_to_kzg_commitment(og1_t *out, const uint8_t b[48]) { /* common/bytes.c:81-88 */
+    return validate_kzg_g1(out, b);
+}
+
 int okzg_blob_to_polynomial(ofr_t *p, const uint8_t *blob) { /* eip4844/blob.c:31-38 */
     for (size_t i = 0; i < OKZG_FE_PER_BLOB; i++) {
         if (!ofr_from_bytes_canonical(&p[i], blob + 32 * i)) return OKZG_BADARGS;

@@ -64,6 +64,8 @@ int okzg_verify_blob_kzg_proof(bool *ok, const uint8_t *blob, const uint8_t comm
 int okzg_verify_blob_kzg_proof_batch(bool *ok, const uint8_t *blobs, const uint8_t *commitments,
                                      const uint8_t *proofs, uint64_t n, const OKZGSettings *s);
 void okzg_compute_challenge(ofr_t *out, const uint8_t *blob, const og1_t *commitment);
+/* common/bytes.c:81-95 (bytes_to_kzg_commitment / bytes_to_kzg_proof): OKZG_OK or OKZG_BADARGS */
+int okzg_bytes_to_kzg_commitment(og1_t *out, const uint8_t b[48]);
 
 /* src/eip7594/eip7594.h:35-68 */
 int okzg_compute_cells_and_kzg_proofs(uint8_t *cells, uint8_t *proofs, const uint8_t *blob,

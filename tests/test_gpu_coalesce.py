@@ -9,6 +9,7 @@ import threading
 
 import pytest
 
+import g1_points
 from conftest import HIP_SO
 from kzg_ctypes import Kzg, KzgError
 from test_gpu_commitment import rand_blob
@@ -19,6 +20,9 @@ pytestmark = pytest.mark.gpu
 def _fanout():
     import sys
     return sys.modules["ckzg_4844_amd"].fanout
+
+
+_Q_T11 = g1_points.by_label("Q+T11").data   # a curve point outside G1: Q in G1 plus a point of order 11
 
 
 def _spoil(blob, element=2111):
@@ -221,8 +225,9 @@ def test_a_lone_caller_never_queues(hip, material):
 
 def test_single_blob_verifications_share_a_batch_and_bad_ones_answer_for_themselves(hip, oracle, material):
     """verify_blob_kzg_proof from 48 native threads: valid triples, a wrong proof (valid point, other blob's), a commitment
-    that is no curve point, a non-canonical blob.  Every caller gets exactly what the single call gives: true / false /
-    C_KZG_BADARGS -- whatever batch it happened to share."""
+    that is no curve point, a proof on the curve but outside G1 (a batch's true verdict vouches for every member, so the
+    shared batch's subgroup flags are that caller's whole check), a non-canonical blob.  Every caller gets exactly what
+    the single call gives: true / false / C_KZG_BADARGS -- whatever batch it happened to share."""
     fo = _fanout()
     blobs, cm = material
     pr = [oracle.compute_blob_kzg_proof(blobs[i], cm[i]) for i in range(8)]
@@ -233,6 +238,8 @@ def test_single_blob_verifications_share_a_batch_and_bad_ones_answer_for_themsel
             ins.append(blobs[i]); aux.append(cm[i] + pr[(i + 1) % 8]); exp.append((0, 0))          # wrong proof -> false
         elif t == 11:
             ins.append(blobs[i]); aux.append(b"\x8f" + cm[i][1:] + pr[i]); exp.append((1, 0))       # malformed commitment -> BADARGS
+        elif t == 23:
+            ins.append(blobs[i]); aux.append(cm[i] + _Q_T11); exp.append((1, 0))                    # proof outside G1 -> BADARGS
         elif t == 40:
             ins.append(_spoil(blobs[i], 99)); aux.append(cm[i] + pr[i]); exp.append((1, 0))         # non-canonical element -> BADARGS
         else:
