@@ -116,6 +116,23 @@ class Kzg:
                    bytes(proof), self.sp)
         return ok.value
 
+    def verify_kzg_proof_batch(self, commitments, zs, ys, proofs):
+        """ckzg_hip_verify_kzg_proof_batch: one verify_kzg_proof per item, on the GPU.  Returns (ok, status): ok[i] is
+        the item's verdict and status[i] its C_KZG_RET (1 = C_KZG_BADARGS: invalid point or field element)."""
+        n = len(commitments)
+        _check(len(zs) == n and len(ys) == n and len(proofs) == n, "list lengths")
+        for c in list(commitments) + list(proofs):
+            _check(len(c) == 48, "commitment/proof")
+        for x in list(zs) + list(ys):
+            _check(len(x) == 32, "z/y")
+        ok = (C.c_bool * max(n, 1))()
+        st = (C.c_uint8 * max(n, 1))()
+        ret = self._fn("ckzg_hip_verify_kzg_proof_batch")(
+            ok, st, b"".join(commitments), b"".join(zs), b"".join(ys), b"".join(proofs), C.c_uint64(n), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_verify_kzg_proof_batch -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:n]], [int(v) for v in st[:n]]
+
     def verify_blob_kzg_proof(self, blob, commitment, proof):
         _check(len(blob) == BYTES_PER_BLOB, "blob")
         _check(len(commitment) == 48 and len(proof) == 48, "commitment/proof")

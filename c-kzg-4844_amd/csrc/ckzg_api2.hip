@@ -1232,6 +1232,82 @@ extern "C" C_KZG_RET ckzg_hip_compute_blob_kzg_proof_batch(KZGProof *proofs, uin
     });
 }
 
+// verify_kzg_proof for n independent items on the GPU, one verdict each (ckzg_hip_verify_kzg_proof_batch): per chunk, the
+// inputs go to HBM, both points of every item are decompressed and subgroup-checked, one lane per item computes
+// P1 = C - [y]G + [z]proof (an invalid item -- bad point, z or y not canonical -- becomes infinity there) and one lane
+// per item runs the two-pairing check e(P1, [1]_2) * e(-proof, [s]_2) == 1 against the prepared lines of the two setup
+// constants (pairing.hip).  Every stage runs on the slot's compute stream, so each kernel that reads a flag or a point
+// is ordered after the one that wrote it; no event is involved.
+static C_KZG_RET verify_point_proofs_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                        const Bytes32 *zs_bytes, const Bytes32 *ys_bytes, const Bytes48 *proofs_bytes,
+                                        uint64_t n) {
+    for (uint64_t i = 0; i < n; i++) ok[i] = false;
+    if (n == 0) return C_KZG_OK;
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    // one lane per item: 65,536 items are one wave on each SIMD of the chip
+    const uint64_t CH = 65536;
+    const uint64_t m = n < CH ? n : CH;
+    const size_t TAB = 4 * (size_t)MILLER_STEPS * 2;   // Fp: lam[68], c[68] of [1]_2, then of [s]_2, Fp2 each
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(TAB * sizeof(Fp) +
+                 m * (2 * 48 + 2 * 32 + 2 * sizeof(G1Affine) + 2 * 2 + sizeof(G1XYZZ) + sizeof(Fp) + 2 * sizeof(G1Affine) + 2)));
+    ArenaTrim trim(ar);
+    ABuf<Fp> d_tab(ar, TAB), d_prefix(ar, m);
+    ABuf<uint8_t> d_in48(ar, 2 * m * 48), d_zy(ar, 2 * m * 32), d_st(ar, 4 * m), d_bad(ar, m), d_res(ar, m);
+    ABuf<G1Affine> d_pts(ar, 2 * m), d_lhs(ar, m), d_negp(ar, m);
+    ABuf<G1XYZZ> d_xyzz(ar, m);
+    OKM(d_tab.p && d_prefix.p && d_in48.p && d_zy.p && d_st.p && d_bad.p && d_res.p && d_pts.p && d_lhs.p && d_negp.p &&
+        d_xyzz.p);
+    std::vector<Fp> tab(TAB);
+    const host::G2Prepared *q[2] = {&pg->gen, &pg->s1};
+    for (int j = 0; j < 2; j++) {
+        memcpy(&tab[(size_t)(2 * j) * MILLER_STEPS * 2], q[j]->lam, sizeof q[j]->lam);
+        memcpy(&tab[(size_t)(2 * j + 1) * MILLER_STEPS * 2], q[j]->c, sizeof q[j]->c);
+    }
+    struct StreamDrain {  // nothing enqueued may outlive this frame (the host table) or the arena's reuse, on every exit path
+        hipStream_t s;
+        ~StreamDrain() { (void)dev::sync_stream(s); }
+    } drain{ctx->stream};
+    OKB(hipMemcpyAsync(d_tab.p, tab.data(), TAB * sizeof(Fp), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    std::vector<uint8_t> res(m);
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t off = 0; off < n; off += CH) {
+        const uint64_t k = n - off < CH ? n - off : CH;
+        OKB(hipMemcpyAsync(d_in48.p, commitments_bytes + off, k * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        OKB(hipMemcpyAsync(d_in48.p + k * 48, proofs_bytes + off, k * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        OKB(hipMemcpyAsync(d_zy.p, zs_bytes + off, k * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        OKB(hipMemcpyAsync(d_zy.p + k * 32, ys_bytes + off, k * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        // validate_kzg_g1 (bytes.c:81-95) of both points: decompression flags in d_st[0, 2k), subgroup flags in [2k, 4k)
+        RC(dev::decompress_g1_batch_device(ctx, d_pts.p, d_st.p, d_in48.p, 2 * k));
+        RC(dev::subgroup_g1_batch_device(ctx, d_st.p + 2 * k, d_pts.p, 2 * k));
+        RC(dev::point_lhs_enqueue(ctx, d_xyzz.p, d_negp.p, d_bad.p, d_pts.p, d_st.p, d_st.p + 2 * k, d_zy.p, d_zy.p + k * 32, k));
+        RC(dev::batch_to_affine_device(ctx, d_lhs.p, d_xyzz.p, d_prefix.p, k));
+        RC(dev::pairing_check_enqueue(ctx, d_res.p, d_lhs.p, d_negp.p, d_bad.p, d_tab.p, k));
+        OKB(d_res.down(res.data(), k));
+        for (uint64_t i = 0; i < k; i++) {
+            ok[off + i] = res[i] == 1;
+            if (status) status[off + i] = res[i] == 2 ? (uint8_t)C_KZG_BADARGS : (uint8_t)C_KZG_OK;
+            if (res[i] == 2) ret = C_KZG_BADARGS;
+        }
+    }
+    return ret;
+}
+
+extern "C" C_KZG_RET ckzg_hip_verify_kzg_proof_batch(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                                    const Bytes32 *zs_bytes, const Bytes32 *ys_bytes,
+                                                    const Bytes48 *proofs_bytes, uint64_t n, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        if (!ok || !commitments_bytes || !zs_bytes || !ys_bytes || !proofs_bytes) return C_KZG_BADARGS;
+        return for_each_device_shard(s, n, 64, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return verify_point_proofs_on(ctx, ok + lo, status ? status + lo : nullptr, commitments_bytes + lo,
+                                          zs_bytes + lo, ys_bytes + lo, proofs_bytes + lo, hi - lo);
+        });
+    });
+}
+
 extern "C" C_KZG_RET compute_blob_kzg_proof(KZGProof *out, const Blob *blob, const Bytes48 *commitment_bytes,
                                             const KZGSettings *s) {
     // eip4844.c:496-535; evaluation, quotient and MSM on the GPU: a batch of one for a lone caller, one batch

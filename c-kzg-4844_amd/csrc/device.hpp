@@ -520,6 +520,17 @@ int cell_aggregate_device(DeviceCtx *ctx, Fr *d_agg, const Fr *d_cell_fr, const 
 int interp_sum_device(DeviceCtx *ctx, Fr *d_interp, const Fr *d_cols);
 int fr_mul_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n, size_t period);
 int fr_div_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n);
+// pairing.hip: verify_kzg_proof for n independent items (ckzg_api2.hip: verify_point_proofs_on).  Enqueue-only, on
+// ctx->stream.  d_pts: commitments [0, n), proofs [n, 2n), decompressed; d_st_dec / d_st_sub: their 2n flags from
+// decompress_g1_batch_device / subgroup_g1_batch_device; d_z32 / d_y32: n x 32 big-endian bytes.  Writes the check's
+// left-hand point P1 = C - [y]G + [z]proof (XYZZ; infinity for an invalid item), -proof (affine) and d_bad[n].
+int point_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8_t *d_bad, const G1Affine *d_pts,
+                      const uint8_t *d_st_dec, const uint8_t *d_st_sub, const uint8_t *d_z32, const uint8_t *d_y32,
+                      size_t n);
+// d_res[i] = 1 / 0 / 2 (valid / not / invalid item) for e(d_lhs[i], [1]_2) * e(d_neg_proof[i], [s]_2) == 1; d_tab: the
+// prepared lines lam[68], c[68] of [1]_2, then of [s]_2, as Fp2 = 2 x Fp (host_pairing.hpp: G2Prepared)
+int pairing_check_enqueue(DeviceCtx *ctx, uint8_t *d_res, const G1Affine *d_lhs, const G1Affine *d_neg_proof,
+                          const uint8_t *d_bad, const Fp *d_tab, size_t n);
 // generic helpers
 int batch_to_affine_device(DeviceCtx *ctx, G1Affine *d_out, const G1XYZZ *d_in, Fp *d_prefix, size_t n);
 

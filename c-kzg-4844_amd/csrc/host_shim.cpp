@@ -4,6 +4,7 @@
 // libckzg_hip.so.
 #include <vector>
 #include "host_pairing.hpp"
+#include "pairing_dev.hpp"
 using namespace ckzg;
 using namespace ckzg::host;
 
@@ -538,4 +539,47 @@ extern "C" void hs_fr29_eval_tree_bytes(Fr *y, uint32_t *bad, const uint8_t *blo
 extern "C" void hs_fr29_eval_tree(Fr *y, const Fr *poly, const Fr *z, const Fr *brp_roots, int log_per) {
     if (log_per == 6) eval_tree_emulate<6>(y, poly, z, brp_roots);
     else eval_tree_emulate<4>(y, poly, z, brp_roots);
+}
+
+// pairing_dev.hpp (the per-lane pairing of pairing.hip: k_pairing_check) against host_pairing.hpp.  Fp12 values are
+// 576-byte Montgomery limb arrays, identical in both headers' layouts.
+static_assert(sizeof(pdev::Fp12) == sizeof(Fp12), "Fp12 layouts");
+static_assert(sizeof(pdev::Fp2) == sizeof(Fp2), "Fp2 layouts");
+extern "C" {
+void hs_pd_final_exp(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::final_exp(*f); }
+void hs_host_final_exp(Fp12 *r, const Fp12 *f) { *r = final_exp(*f); }
+void hs_pd_fp12_inv(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::inv(*f); }
+void hs_host_fp12_inv(Fp12 *r, const Fp12 *f) { *r = inv(*f); }
+void hs_pd_fp12_mul(pdev::Fp12 *r, const pdev::Fp12 *a, const pdev::Fp12 *b) { *r = pdev::mul(*a, *b); }
+void hs_host_fp12_mul(Fp12 *r, const Fp12 *a, const Fp12 *b) { *r = mul(*a, *b); }
+void hs_pd_fp12_sqr(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::sqr(*f); }
+void hs_pd_cyclotomic_sqr(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::cyclotomic_sqr(*f); }
+// the easy part f^((p^6-1)(p^2+1)): an element of the cyclotomic subgroup
+void hs_pd_easy_part(pdev::Fp12 *r, const pdev::Fp12 *f) {
+    const pdev::Fp12 a = pdev::mul(pdev::conj(*f), pdev::inv(*f));
+    *r = pdev::mul(pdev::frobenius<2>(a), a);
+}
+int hs_pd_is_one(const pdev::Fp12 *f) { return pdev::is_one(*f) ? 1 : 0; }
+// Miller product and full two-pair check with G2 arguments prepared by host_pairing.hpp's g2_prepare
+static pdev::LineTable pd_table(const G2Prepared &q) {
+    return {reinterpret_cast<const pdev::Fp2 *>(q.lam), reinterpret_cast<const pdev::Fp2 *>(q.c)};
+}
+void hs_pd_miller(pdev::Fp12 *r, const G1Jac *a1, const G2Jac *q1, const G1Jac *a2, const G2Jac *q2) {
+    G2Prepared p1, p2;
+    g2_prepare(p1, g2_to_affine(*q1));
+    g2_prepare(p2, g2_to_affine(*q2));
+    *r = pdev::miller_product_tables(jac_to_affine(*a1), pd_table(p1), jac_to_affine(*a2), pd_table(p2));
+}
+void hs_host_miller(Fp12 *r, const G1Jac *a1, const G2Jac *q1, const G1Jac *a2, const G2Jac *q2) {
+    G2Prepared p1, p2;
+    g2_prepare(p1, g2_to_affine(*q1));
+    g2_prepare(p2, g2_to_affine(*q2));
+    *r = miller_product_prepared(jac_to_affine(*a1), p1, jac_to_affine(*a2), p2);
+}
+int hs_pd_pairing_check(const G1Jac *a1, const G2Jac *q1, const G1Jac *a2, const G2Jac *q2) {
+    G2Prepared p1, p2;
+    g2_prepare(p1, g2_to_affine(*q1));
+    g2_prepare(p2, g2_to_affine(*q2));
+    return pdev::pairing_product_is_one(jac_to_affine(*a1), pd_table(p1), jac_to_affine(*a2), pd_table(p2)) ? 1 : 0;
+}
 }

@@ -156,6 +156,22 @@ C_KZG_RET ckzg_hip_compute_blob_kzg_proof_batch(KZGProof *proofs, uint8_t *statu
                                                 const Bytes48 *commitments_bytes, uint64_t n,
                                                 const KZGSettings *s);
 
+/* verify_kzg_proof (src/eip4844/eip4844.c) over n independent items, one verdict each:
+ * for every i, (status[i], ok[i]) is exactly (return value, *ok) of verify_kzg_proof(&commitments[i], &zs[i], &ys[i],
+ * &proofs[i], s).  Returns C_KZG_BADARGS if any item is invalid (its ok[i] = false; the verdicts of the other items
+ * are still written), C_KZG_OK otherwise; C_KZG_ERROR / C_KZG_MALLOC if the call itself failed.  status may be NULL.
+ * Deterministic: no random linear combination, every item gets its own two-pairing check on the GPU.
+ * This is NOT the reference's static verify_kzg_proof_batch (eip4844.c:697-758), which returns one aggregate bool for
+ * all items: here every item has its own verdict, and one bad proof says nothing about the others.
+ * Always the GPU path (one lane per item: point validation, P1 = C - [y]G + [z]proof, then the two-pairing check
+ * e(P1, [1]_2) * e(-proof, [s]_2) == 1 against prepared line tables).  Latency is flat: ~65 ms for any
+ * n <= 4096 (k_pairing_check alone ~58 ms), ~87 ms at n = 65,536.  Below about 2,000 items a loop of verify_kzg_proof
+ * on host threads is faster: measured with 256 host threads, the loop took 56 ms at n = 1536 and 77 ms at n = 2048
+ * against 65 ms for this call (profiles/point_verify_bench.json).  With fewer host threads the crossover is lower. */
+C_KZG_RET ckzg_hip_verify_kzg_proof_batch(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                          const Bytes32 *zs_bytes, const Bytes32 *ys_bytes,
+                                          const Bytes48 *proofs_bytes, uint64_t n, const KZGSettings *s);
+
 /* verify_blob_kzg_proof_batch (src/eip4844/eip4844.c:775-844) with blobs, commitments and proofs resident in HBM
  * (device pointers on one GPU: n Blob, n Bytes48, n Bytes48).  Point validation, bytes -> field elements, the
  * Fiat-Shamir challenges (SHA-256 of every blob, on the GPU), the evaluations and the three random-linear-combination
