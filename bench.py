@@ -4,13 +4,21 @@
 (SURVEY.md section 8e).  One JSON line on rank 0.
 
 A step = one call of ckzg_hip_blob_to_kzg_commitment_batch_device over 1024 synthetic blobs that are
-already resident in HBM (the task's measurement contract: `value` is the HBM-resident rate).  The same
-1024 blobs through the reference-shaped host-pointer call (H2D + D2H inside the timed region, pageable
-host memory) are timed over the same number of steps and reported next to it as `host_pointer`.
+already resident in HBM (the task's measurement contract: `value` is the HBM-resident rate).
+
+A plain run does only what that figure needs: it loads the wide tables, warms up, times the steps, writes
+--dump-outputs if asked and prints the line.  Everything else is measured with --full:
+  * the same 1024 blobs through the reference-shaped host-pointer call (H2D + D2H inside the timed region,
+    pageable host memory), timed over the same number of steps and reported next to it as `host_pointer`;
+  * the spot check of the timed outputs against the CPU oracle and the CPU baseline;
+  * the secondary rows (cells + proofs, verification, recovery, concurrent callers, default footprint, the
+    footprint curve), the predicted scaling, and at N > 1 the per-rank bookkeeping, the sharded rows and
+    the C-ABI fan-out.
+--no-cpu-baseline, --no-secondary and --no-pcie leave out parts of a --full run.
 
 ONE KZGSettings (commit 16-bit + proof 16-bit + FK20 13-bit GLV tables, ~238 GB) serves every wide-table
-row of the line; a second, co-resident KZGSettings with the library's default tables (~7 GB) gives the
-default-footprint figures.  Nothing is reloaded between rows.
+row of the line; with --full a second, co-resident KZGSettings with the library's default tables (~7 GB)
+gives the default-footprint figures.  Nothing is reloaded between rows.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself through
 torch.distributed.run with N ranks (one per GPU); under the driver's own torchrun launch it reads
@@ -887,9 +895,8 @@ def compact_line(full, side_file=None):
     return out
 
 
-def emit(full):
-    """Full record -> gpurun_out/bench_secondary.json and one stderr line (written first); the compact record is the ONE
-    line on stdout."""
+def write_side_file(full):
+    """The full record -> the side file; returns its path relative to ROOT, or None if it could not be written."""
     side = os.path.join("gpurun_out", "bench_secondary.json")
     try:
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -898,6 +905,13 @@ def emit(full):
     except OSError as e:
         sys.stderr.write("bench: could not write %s: %s\n" % (side, e))
         side = None
+    return side
+
+
+def emit(full, side_file=True):
+    """Full record -> the side file (side_file: a --full run; a plain run has nothing for it) and one stderr line
+    (written first); the compact record is the ONE line on stdout."""
+    side = write_side_file(full) if side_file else None
     sys.stderr.write(json.dumps({"bench_full_record": full}) + "\n")
     sys.stderr.flush()
     sys.stdout.write(json.dumps(compact_line(full, side)) + "\n")
@@ -919,14 +933,19 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--wbits", type=int, default=int(os.environ.get("CKZG_BENCH_WBITS", str(WIDE["commit_wbits"]))))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-pointer (PCIe-inclusive) leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: host-pointer leg, oracle spot check, "
+                         "CPU baseline, secondary rows, footprint curve, per-rank and sharded rows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary rows")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the host-pointer (PCIe-inclusive) leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (commitments, per-blob status) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the headline alone
+        args.no_cpu_baseline = args.no_secondary = args.no_pcie = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         respawn(args.gpus)  # exits with the ranks' status
 
@@ -981,25 +1000,28 @@ def main():
     opts = dict(WIDE, device=local_rank, commit_wbits=args.wbits, async_tables=1)
     if one_gpu and world > 1:
         opts.update(commit_wbits=min(args.wbits, 12), proof_wbits=8, fk20_wbits=8)  # ranks share one GPU's HBM
-    import hashlib
-    first_blob = b"".join(b"\x00" + hashlib.sha256(b"first%d" % j).digest()[:31] for j in range(4096))
-    free_before = torch.cuda.mem_get_info(local_rank)[0]
+    if args.full:
+        import hashlib
+        first_blob = b"".join(b"\x00" + hashlib.sha256(b"first%d" % j).digest()[:31] for j in range(4096))
+        free_before = torch.cuda.mem_get_info(local_rank)[0]
     t_load = time.perf_counter()
     hip = mod.Kzg(mod.HIP_SO, options=opts)
     returned_s = time.perf_counter() - t_load
     hip.lib.ckzg_hip_set_option(b"async_tables", 0)   # later loads of this process are ordinary ones
     # (round 4 switched "commit_graph" off here for multi-rank runs: RCCL's watchdog thread makes HIP calls of its own and
     # a stream capture could not be kept away from it.  The graph is built node by node now -- nothing to switch off.)
-    first_commitment = hip.blob_to_kzg_commitment(first_blob)
-    first_commit_s = time.perf_counter() - t_load
+    if args.full:   # time to the first commitment, served from the default-width tables while the wide ones are built
+        first_commitment = hip.blob_to_kzg_commitment(first_blob)
+        first_commit_s = time.perf_counter() - t_load
     L = Lib(hip.lib)
     sp = C.addressof(hip.s)
     if L.wait_tables(sp) != 0:
         raise SystemExit("bench: ckzg_hip_wait_tables failed")
     load_s = time.perf_counter() - t_load
-    if hip.blob_to_kzg_commitment(first_blob) != first_commitment:
-        raise SystemExit("bench: commitment from the wide tables differs from the one served while they were built")
-    free_after = torch.cuda.mem_get_info(local_rank)[0]
+    if args.full:
+        if hip.blob_to_kzg_commitment(first_blob) != first_commitment:
+            raise SystemExit("bench: commitment from the wide tables differs from the one served while they were built")
+        free_after = torch.cuda.mem_get_info(local_rank)[0]
     wbits = int(L.table_wbits(sp, 0))  # what was actually built
 
     # synthetic blobs: 31 random bytes per field element, top byte 0 => canonical
@@ -1044,7 +1066,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        if rank == 0:   # what rank 0 holds after the last step: its own shard first, every rank's rows behind it
+        if rank == 0 and args.full:   # what rank 0 holds after the last step: its own shard first, every rank's rows behind it
             g0 = gathered[0]
             if g0 is None or tuple(g0.shape) != (world * BLOBS_PER_STEP, 48) or \
                     not torch.equal(g0[:BLOBS_PER_STEP].cpu(), out.cpu()):
@@ -1101,7 +1123,7 @@ def main():
 
     # spot-check the timed kernel's output against the CPU oracle (checker only, untimed)
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             orc = mod.Kzg(os.path.join(ROOT, "oracle", "liboracle.so"), "okzg_")
             hb_all = blobs.cpu().numpy()
@@ -1184,7 +1206,7 @@ def main():
 
     # per-rank bookkeeping and the sharded forms of configs[3] / configs[4]: every rank takes part, rank 0 reports
     per_rank = sharded = None
-    if world > 1:
+    if world > 1 and args.full:
         t = torch.tensor([load_s, free_before / 1e9, free_after / 1e9, sum(kern_ms) / len(kern_ms)], dtype=torch.float64, device=red_dev)
         parts = [torch.zeros_like(t) for _ in range(world)]
         dist.all_gather(parts, t)
@@ -1285,7 +1307,7 @@ def main():
         if cpu_base is not None:
             line["cpu_baseline"] = cpu_base
         # the 1/2/4/8-GPU curve this host should give, per BASELINE config, and what bounds it
-        if world == 1:
+        if world == 1 and args.full:
             eff = None
             try:
                 cb = line["cpu_baseline"]
@@ -1295,7 +1317,7 @@ def main():
             budget = L._fn("ckzg_hip_host_thread_budget", [])()
             line["predicted_scaling"] = predicted_scaling(value, None if host_ptr is None else host_ptr["value"], secondary or {},
                                                           lib_budget=int(budget), effective_cores=eff)
-        else:
+        elif world > 1:
             v1, src = committed_single_gpu_value()
             line["predicted"] = {"value": None if v1 is None else round(world * v1, 0), "unit": "blobs/s",
                                  "from": "N x the committed one-GPU value (%s): ranks share nothing on this path" % src,
@@ -1326,7 +1348,7 @@ def main():
         except BaseException as e:  # noqa: BLE001
             secondary["footprint_curve"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
     if rank == 0:
-        emit(line)
+        emit(line, side_file=args.full)
     if world > 1:
         dist.destroy_process_group()
 

@@ -63,6 +63,21 @@ def test_emit_prints_the_compact_line_last(tmp_path, monkeypatch):
     assert "secondary" in side and "predicted_scaling" in side
 
 
+def test_plain_emit_writes_no_side_file(tmp_path, monkeypatch):
+    """a plain run (no --full) has no secondary record: the line and the stderr record only, nothing on disk"""
+    b = _bench()
+    monkeypatch.setattr(b, "ROOT", str(tmp_path))
+    buf, err = io.StringIO(), io.StringIO()
+    monkeypatch.setattr(sys, "stdout", buf)
+    monkeypatch.setattr(sys, "stderr", err)
+    b.emit(_full_record(), side_file=False)
+    monkeypatch.undo()
+    lines = buf.getvalue().strip().split("\n")
+    assert len(lines) == 1 and json.loads(lines[0])["secondary_file"] is None
+    assert "bench_full_record" in json.loads(err.getvalue())
+    assert not any(tmp_path.iterdir())
+
+
 def test_oversized_extras_are_dropped_not_the_head():
     b = _bench()
     full = _full_record()

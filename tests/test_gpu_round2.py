@@ -597,12 +597,27 @@ def _run_bench(extra_env, args):
     return full
 
 
+def test_bench_plain_run_times_the_headline_alone(tmp_path):
+    """`python bench.py` without --full loads, warms up, times the steps, dumps and prints the line: no host-pointer
+    leg, no oracle spot check, no CPU baseline, no secondary rows, no scaling model."""
+    import numpy as np
+    line = _run_bench({}, ["--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")])
+    assert line["metric"] == "blob_to_kzg_commitment throughput" and line["unit"] == "blobs/s"
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2 and line["warmup"] == 1
+    assert line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["host_pointer"] is None and line["parity_spot_check_vs_oracle"] is None and line["secondary"] is None
+    for k in ("cpu_baseline", "predicted_scaling", "baseline_configs"):
+        assert k not in line, k
+    c, st = np.load(tmp_path / "out" / "commitments.npy"), np.load(tmp_path / "out" / "status.npy")
+    assert c.shape == (1024, 48) and st.shape == (1024,) and not st.any()
+
+
 def test_bench_two_ranks_control_flow_on_one_gpu():
     """`python bench.py --gpus 2` spawns two ranks itself (torch.distributed.run); here both ranks share the one
     GPU over gloo, which exercises the barrier / MAX-over-ranks timing, the whole-job host-pointer leg and the
     C-ABI fan-out leg (two table replicas standing in for two devices)."""
     line = _run_bench({"CKZG_BENCH_ONE_GPU": "1", "CKZG_BENCH_BACKEND": "gloo"},
-                      ["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+                      ["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert line["n_gpus"] == 2 and line["parity_spot_check_vs_oracle"] is True
     assert line["value"] > 0 and line["host_pointer"]["value"] > 0
     assert line["c_abi_fan_out"]["devices"] == 2 and line["c_abi_fan_out"]["rc"] == 0
@@ -611,6 +626,6 @@ def test_bench_two_ranks_control_flow_on_one_gpu():
 @pytest.mark.skipif("__import__('subprocess').run(['bash', '-c', 'rocm-smi --showid | grep -c \"Device ID\"'], capture_output=True, text=True).stdout.strip() in ('', '0', '1')",
                     reason="needs two visible GPUs")
 def test_bench_two_ranks_on_two_gpus_over_rccl():
-    line = _run_bench({}, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    line = _run_bench({}, ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert line["n_gpus"] == 2 and line["parity_spot_check_vs_oracle"] is True
     assert line["c_abi_fan_out"]["devices"] == 2 and line["c_abi_fan_out"]["rc"] == 0

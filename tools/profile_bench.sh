@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/prof
 rm -rf $O && mkdir -p $O
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/timed -- python bench.py --no-cpu-baseline --no-secondary --no-pcie > $O/bench_timed.json 2> $O/timed.err
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_$c -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-secondary --no-pcie > /dev/null 2> $O/pmc_$c.err
