@@ -692,10 +692,7 @@ class OutPipe {
             if (!ctx->out_stream && hipStreamCreateWithFlags(&ctx->out_stream, hipStreamNonBlocking) != hipSuccess) return false;
             if (!ensure_pinned(ctx->h_out, ctx->h_out_bytes, PIECE)) return false;
             for (auto &e : piece_ev) {
-                if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-                    e = nullptr;
-                    return false;
-                }
+                if (dev::ensure_event(e) != hipSuccess) return false;
             }
             worker = std::thread([this]() { run(); });
             started = true;
@@ -811,8 +808,9 @@ struct DeviceBuffer {
 // there -- a down() placed after an enqueue-only stage would read stale bytes without any error.
 template <class T>
 struct ABuf {
-    T *p;
-    hipStream_t stream;
+    T *p = nullptr;
+    hipStream_t stream = nullptr;
+    ABuf() = default;
     ABuf(dev::Arena &a, size_t count) : p(a.get<T>(count)), stream(a.stream) {}
     bool up(const T *h, size_t count) {
         return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, stream) == hipSuccess &&
@@ -824,6 +822,15 @@ struct ABuf {
     }
 };
 using dev::Arena;
+
+// Waits for a stream (if any) when it goes out of scope: declared before the first enqueue on its stream, it keeps
+// every exit path, an early error return included, from leaving work queued that reads the arena or the frame
+struct StreamDrain {
+    hipStream_t s;
+    ~StreamDrain() {
+        if (s) (void)dev::sync_stream(s);
+    }
+};
 
 // a very large batch must not pin its temporaries in HBM for ever: blocks above 2 GiB are returned
 // when the call ends (one hipFree per such call), smaller ones stay for the next call

@@ -401,11 +401,8 @@ static C_KZG_RET commit_batch_on(dev::DeviceCtx *ctx, KZGCommitment *out, uint8_
     // pinned staging: two input buffers of up to CH blobs; the results come back through the first 49 n
     // bytes of a third one (a pageable destination would make the final copy a blocking staged copy)
     if (!ensure_pinned(ctx->h_stage, ctx->h_stage_bytes, n == 1 || pinned_io ? (size_t)BYTES_PER_BLOB : CH * BYTES_PER_BLOB)) return C_KZG_MALLOC;
-    for (int i = 0; i < 4; i++) {
-        if (!ctx->stage_ev[i] && hipEventCreateWithFlags(&ctx->stage_ev[i], hipEventDisableTiming) != hipSuccess) {
-            ctx->stage_ev[i] = nullptr;
-            ret = C_KZG_ERROR;
-        }
+    for (auto &e : ctx->stage_ev) {
+        if (dev::ensure_event(e) != hipSuccess) ret = C_KZG_ERROR;
     }
     tr.mark("buffers + events");
     if (one_chunk && ret == C_KZG_OK) {
@@ -600,11 +597,8 @@ extern "C" C_KZG_RET ckzg_hip_compute_cells_and_kzg_proofs_batch_device(void *d_
 }
 
 static bool ensure_stage_events(dev::DeviceCtx *ctx) {
-    for (int i = 0; i < 4; i++) {
-        if (!ctx->stage_ev[i] && hipEventCreateWithFlags(&ctx->stage_ev[i], hipEventDisableTiming) != hipSuccess) {
-            ctx->stage_ev[i] = nullptr;
-            return false;
-        }
+    for (auto &e : ctx->stage_ev) {
+        if (dev::ensure_event(e) != hipSuccess) return false;
     }
     return true;
 }

@@ -381,6 +381,15 @@ G1Jac host_lincomb(const std::vector<G1Jac> &pts, const std::vector<Fr> &k) {
 // 2.6 ms for any n up to ~16 -> hand-over after 3.
 constexpr uint64_t SMALL_VERIFY_N = 3;
 
+// r = H("RCKZGBATCH___V1_" | u64be 4096 | u64be n | (C_i | z_i | y_i | proof_i)*)  (eip4844.c:597-680): the header
+void batch_transcript_head(Sha256 &h, uint64_t n) {
+    uint8_t head[32];
+    memcpy(head, "RCKZGBATCH___V1_", 16);
+    be64(head + 16, FIELD_ELEMENTS_PER_BLOB);
+    be64(head + 24, n);
+    h.update(head, 32);
+}
+
 // The batch challenge's transcript (eip4844.c:637-664: one SHA-256 stream over every C_i, z_i, y_i, proof_i) hashed
 // while the batch is still in flight: the pipelined form downloads each chunk's evaluations into page-locked memory
 // right behind the kernel that produced them, and this thread feeds them to the hash in order as they land.  When
@@ -414,11 +423,7 @@ struct TranscriptHasher {
     }
     void start(int device, size_t n, size_t chunk, const hipEvent_t *landed, const Bytes48 *cb, const Bytes48 *pb,
                const Fr *z, const Fr *h_y) {
-        uint8_t head[32];
-        memcpy(head, "RCKZGBATCH___V1_", 16);
-        be64(head + 16, FIELD_ELEMENTS_PER_BLOB);
-        be64(head + 24, n);
-        h.update(head, 32);
+        batch_transcript_head(h, n);
         auto body = [=]() {
             if (hipSetDevice(device) != hipSuccess) {
                 failed = true;
@@ -572,36 +577,36 @@ static bool ensure_cu_partition(dev::DeviceCtx *ctx) {
 }
 
 
-// Shared core of verify_blob_kzg_proof and verify_blob_kzg_proof_batch (eip4844.c:537-595,
-// 697-844).  Per blob, on the GPU: point validation, bytes -> Fr, evaluation at the challenge;
-// then three lincombs over all blobs; host: transcripts and the pairing check
+// ---- verify_blob_kzg_proof and verify_blob_kzg_proof_batch (eip4844.c:537-595, 697-844) ----
+// Per blob, on the GPU: point validation, bytes -> Fr, evaluation at the challenge; then three lincombs over all
+// blobs; host: transcripts and the pairing check
 //   e(sum r^i proof_i, [s]G2) == e(sum r^i (C_i - [y_i]G1) + sum r^i z_i proof_i, G2).
-// Three forms of the per-blob stage:
-//   * classic (n < 1024, or challenges hashed on the GPU): one copy of all blobs, then the kernels;
-//   * pipelined (host pointers, n >= 1024): the blobs cross PCIe in chunks on the copy stream -- DMA'd in place
-//     from page-locked caller memory, through pinned staging otherwise -- while earlier chunks are converted and
-//     evaluated and host threads hash the challenges in order, so that only the transcript, the three sums and
-//     the pairing follow the last byte;
-//   * resident (ckzg_hip_verify_blob_kzg_proof_batch_device): blobs, commitments and proofs already in HBM, the
-//     challenges hashed by k_sha256_challenges; only 96 + 64 bytes per blob travel to the host for the transcript.
-C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, const Bytes48 *pb, uint64_t n,
-                            const KZGSettings *s, dev::DeviceCtx *ctx, bool resident = false) {
-    const bool small = !resident && n <= SMALL_VERIFY_N;
-    Trace tr("verify_blobs");
-    std::vector<G1Jac> hc, hp;  // host copies of the validated points (small n)
-    if (small) {
-        hc.resize(n);
-        hp.resize(n);
-        for (size_t i = 0; i < n; i++) {
-            if (validate_kzg_g1(hc[i], cb[i].bytes) != C_KZG_OK) return C_KZG_BADARGS;
-            if (validate_kzg_g1(hp[i], pb[i].bytes) != C_KZG_OK) return C_KZG_BADARGS;
-        }
-    }
-    tr.mark("host point validation");
+// Forms of the per-blob stage (plan_verify decides, verify_blobs_core dispatches), each ending in BlobVerify::tail:
+//   * small (host pointers, n <= SMALL_VERIFY_N): points and sums on the host, the evaluation on the GPU;
+//   * one-copy (n < verify_pipe_min, or challenges hashed on the GPU): one copy of all blobs, then the kernels;
+//   * pipelined (host pointers, n >= verify_pipe_min): the blobs cross PCIe in chunks underneath the kernels;
+//   * resident (ckzg_hip_verify_blob_kzg_proof_batch_device): blobs, commitments and proofs already in HBM.
+struct VerifyPlan {
+    bool small, gpu_sha, piped, split_validation, partition_wanted, use_table;
+    dev::FixedBaseTable tbl;   // the call-time table's geometry (use_table)
+    size_t tbl_bytes = 0, tbl_tmp = 0, sums_scratch = 0;
+};
+
+// The per-call decisions, from n, the inputs' home and the options (each g_verify_* read once per call).  At run time
+// BlobVerify::carve clears use_table when the arena cannot hold the table, and the partition needs a GpuHashCall that
+// finds no other call and the masked streams (verify_blobs_core).
+VerifyPlan plan_verify(uint64_t n, bool resident) {
+    VerifyPlan p;
+    p.small = !resident && n <= SMALL_VERIFY_N;
     // (never for the small path: its commitments are validated on the host and are not in d_ptb)
-    const bool gpu_sha = resident || (!small && challenges_on_gpu(n));
+    p.gpu_sha = resident || (!p.small && challenges_on_gpu(n));
     const size_t pipe_min = (size_t)g_verify_pipe_min.load(std::memory_order_relaxed);   // option "verify_pipe_min"
-    const bool piped = !resident && !small && !gpu_sha && n >= pipe_min;
+    p.piped = !resident && !p.small && !p.gpu_sha && n >= pipe_min;
+    // Split validation: decompression, then the subgroup test, on the second stream, so that the ladder kernel runs
+    // under the (host-blocking, pageable) copy of the blobs and the subgroup test underneath evaluation and sums.
+    // Only for batches whose blob copy is short: measured, a concurrent kernel slows a long pageable copy by more than
+    // the ~1.3 ms it hides -- n = 4096: 30 -> 37 ms; n = 64: 8.0 -> 5.6 ms.
+    p.split_validation = !p.small && !p.piped && !resident && n < 1024;
     // Call-time table (msm.hip): while the blobs of a batch cross PCIe (or, in the resident form, while one lane per
     // blob hashes them) the GPU is mostly idle and the batch challenge does not exist yet, so the 128 doublings per
     // term of the three sums are done early, as a narrow fixed-base table over the 2n validated points built on a side
@@ -615,152 +620,236 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
     // (option "verify_call_table" = 0 keeps the ladder sums: the path a device too full for the table takes)
     static const int call_table_wbits = (int)dev::ab_knob("CKZG_HIP_VERIFY_TABLE_WBITS", 6);
     static const size_t call_table_min = (size_t)dev::ab_knob("CKZG_HIP_VERIFY_TABLE_MIN", 8);
-    bool use_table = g_verify_call_table.load(std::memory_order_relaxed) != 0 && call_table_wbits >= 4 && call_table_wbits <= 10 &&
-                     n >= call_table_min && !small;
-    dev::FixedBaseTable tbl;
-    size_t tbl_bytes = 0, tbl_tmp = 0, sums_scratch = 0;
-    Arena &ar = ctx->api_arena;
-    // (no converted polynomials: the evaluation reads the blobs' bytes -- verify.hip: k_eval_tree's BYTES form)
-    const size_t plain_bytes = (resident ? n * 160 : n * BYTES_PER_BLOB) + 2 * n * sizeof(Fr) + n * 4 +
-                               2 * n * (48 + 2 + sizeof(G1Affine)) + 8192;   // (resident: the transcript rows, no blobs)
-    if (use_table) {
-        dev::call_table_geometry(&tbl, (int)(2 * n), call_table_wbits);
-        tbl_bytes = dev::call_table_bytes(tbl);
-        tbl_tmp = dev::call_table_tmp_bytes(tbl);
-        sums_scratch = dev::table_sums_scratch_bytes(tbl, 3);
-        // the table is an optimisation (1.3 GB at n = 4096): a device too full for it still verifies, by ladders
-        if (!ar.begin(plain_bytes + tbl_bytes + tbl_tmp + sums_scratch + 6 * n * 32 + 1024)) {
-            use_table = false;
-            tbl_bytes = tbl_tmp = sums_scratch = 0;
-        }
+    p.use_table = g_verify_call_table.load(std::memory_order_relaxed) != 0 && call_table_wbits >= 4 && call_table_wbits <= 10 &&
+                  n >= call_table_min && !p.small;
+    if (p.use_table) {
+        dev::call_table_geometry(&p.tbl, (int)(2 * n), call_table_wbits);
+        p.tbl_bytes = dev::call_table_bytes(p.tbl);
+        p.tbl_tmp = dev::call_table_tmp_bytes(p.tbl);
+        p.sums_scratch = dev::table_sums_scratch_bytes(p.tbl, 3);
     }
-    if (!use_table) OKM(ar.begin(plain_bytes));
-    ABuf<uint8_t> d_ptb(ar, 2 * n * 48), d_st(ar, 2 * n), d_st2(ar, 2 * n), d_blobs_own(ar, resident ? 1 : n * BYTES_PER_BLOB);
-    ABuf<G1Affine> d_pts(ar, 2 * n);
-    ABuf<Fr> d_z(ar, n), d_y(ar, n);
-    ABuf<uint32_t> d_bad(ar, n);
-    OKM(d_ptb.p && d_st.p && d_st2.p && d_blobs_own.p && d_pts.p && d_z.p && d_y.p && d_bad.p);
-    ABuf<uint8_t> d_tbl(ar, use_table ? tbl_bytes : 1), d_tbl_tmp(ar, use_table ? tbl_tmp : 1), d_sums_scr(ar, use_table ? sums_scratch : 1);
-    ABuf<uint32_t> d_sc(ar, use_table ? 6 * n * 8 : 1);
-    ABuf<G1XYZZ> d_sums(ar, 3);
-    OKM(d_tbl.p && d_tbl_tmp.p && d_sums_scr.p && d_sc.p && d_sums.p);
-    ArenaTrim trim(ar);
-    tr.mark("arena");
-    // resident: the device copies of the inputs ARE the caller's buffers, and nothing of them is read on the host -- the
-    // rows of the batch transcript (commitment | z | y | proof) are assembled on the device and come back in one copy
-    const uint8_t *d_blob_bytes = resident ? reinterpret_cast<const uint8_t *>(blobs) : d_blobs_own.p;
-    const Bytes48 *d_cb = cb, *d_pb = pb;
-    ABuf<uint8_t> d_rows(ar, resident ? n * 160 : 1);
-    OKM(d_rows.p);
-    if (resident) {
-        OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, n * 160));   // rows | evaluations + flags
-        cb = pb = nullptr;
-        blobs = nullptr;   // never dereferenced on the host
-        OKB(hipEventRecord(ctx->ev[1], ctx->stream) == hipSuccess);
-    }
-    // whatever path leaves this function, the second stream must be idle before the arena is reused
-    // (declared before the first enqueue on it: an early error return drains it too)
-    struct StreamDrain {
-        hipStream_t s;
-        ~StreamDrain() {
-            if (s) (void)dev::sync_stream(s);
-        }
-    } drain{ctx->copy_stream};
-    const bool split_validation = !small && !piped && !resident && n < 1024;
-    // Resident form: the hash chain on its own quarter of the compute units, validation and table build on the rest.
-    // Measured (tools/ubench/sha_contention_probe.py, profiles/r06_cu_partition_ab.txt): sharing the chip, the chain of a
-    // 4096-blob batch takes 4.9 ms -- a validation or table wave that lands on a hash wave's SIMD takes issue slots from
-    // it for as long as it lives, and the launch ends with its slowest wave -- against 3.8 ms alone; partitioned, the
-    // call goes 7.5 -> 6.3 ms (2048 blobs: 6.7 -> 5.7).  Below ~640 blobs the side work rarely collides (768 blobs: 3 calls of 16 took the extra 1.1 ms) and the
-    // masked streams only cost their 0.07 ms.
-    static const size_t partition_min = (size_t)dev::ab_knob("CKZG_HIP_CU_PARTITION_MIN", 640);
+    // Partition of the compute units (GPU hash only): the hash chain on its own quarter, validation and table build on
+    // the rest.  Measured (tools/ubench/sha_contention_probe.py, profiles/r06_cu_partition_ab.txt): sharing the chip,
+    // the chain of a 4096-blob batch takes 4.9 ms -- a validation or table wave that lands on a hash wave's SIMD takes
+    // issue slots from it for as long as it lives, and the launch ends with its slowest wave -- against 3.8 ms alone;
+    // partitioned, the resident call goes 7.5 -> 6.3 ms (2048 blobs: 6.7 -> 5.7).  Below ~640 blobs the side work
+    // rarely collides (768 blobs: 3 calls of 16 took the extra 1.1 ms) and the masked streams only cost their 0.07 ms.
     // (host-pointer batches whose challenges are hashed on the GPU -- a rank with few host threads -- partition the same
     // way: there the validation runs before the copy on the main stream, hash and table build after it)
     // (up to 8192 blobs: 128 hash workgroups of two waves have a SIMD per wave on a quarter of 256 compute units; a
     // larger batch would crowd the quarter and spreads over the chip instead)
-    const bool partition_wanted = gpu_sha && !small && n >= partition_min && n <= 8192 &&
-                                  g_verify_cu_partition.load(std::memory_order_relaxed) != 0;
-    std::optional<GpuHashCall> hash_call;   // (counted only by calls that could partition; lives until the call returns)
-    if (partition_wanted) hash_call.emplace(ctx->device);
-    const bool partition = partition_wanted && hash_call->alone && ensure_cu_partition(ctx);
-    StreamDrain drain_sha{partition ? ctx->sha_stream : nullptr}, drain_val{partition ? ctx->side_stream[0] : nullptr};
-    // The hash of the challenges: the enqueue-only step every GPU-hash form shares.  The resident form runs it HERE --
-    // its inputs are the caller's buffers, nothing precedes it, and every 10 us the longest kernel of the call starts
-    // earlier is 10 us off the call --, the host-pointer form further down, behind its copies.
-    bool hash_enqueued = false;
-    auto enqueue_hash = [&]() -> C_KZG_RET {
-        RC(dev::sha256_challenges_device(ctx, d_z.p, d_blob_bytes, resident ? reinterpret_cast<const uint8_t *>(d_cb) : d_ptb.p, n,
-                                         partition ? ctx->sha_stream : nullptr));
+    static const size_t partition_min = (size_t)dev::ab_knob("CKZG_HIP_CU_PARTITION_MIN", 640);
+    p.partition_wanted = p.gpu_sha && !p.small && n >= partition_min && n <= 8192 &&
+                         g_verify_cu_partition.load(std::memory_order_relaxed) != 0;
+    return p;
+}
+
+void hash_challenges(Fr *z, const Blob *blobs, const Bytes48 *cb, uint64_t n) {
+    parallel_for(n, [&](size_t i) { z[i] = challenge_from_bytes(blobs[i].bytes, cb[i].bytes); });
+}
+
+// r's transcript hashed on the host from the inputs and z, y: valid compressed encodings are canonical, so the input
+// bytes are the re-compressed bytes
+void host_batch_digest(uint8_t digest[32], uint64_t n, const Bytes48 *cb, const Bytes48 *pb, const Fr *z, const Fr *y) {
+    Sha256 h;
+    uint8_t zb[64];
+    batch_transcript_head(h, n);
+    for (size_t i = 0; i < n; i++) {
+        h.update(cb[i].bytes, 48);
+        fr_to_bytes(zb, z[i]);
+        fr_to_bytes(zb + 32, y[i]);
+        h.update(zb, 64);
+        h.update(pb[i].bytes, 48);
+    }
+    h.finish(digest);
+}
+
+// Kernel-only time of the resident form (ckzg_hip_last_kernel_ms, which = 3): validation + conversion + challenges +
+// evaluation (ev[1] .. ev[2]), and the three sums (ev[3] .. ev[4]); the host transcript between them is not GPU time
+C_KZG_RET record_resident_kernel_ms(dev::DeviceCtx *ctx) {
+    float a = 0, b = 0;
+    OKB(hipEventRecord(ctx->ev[4], ctx->stream) == hipSuccess && dev::sync_event(ctx->ev[4]) == hipSuccess);
+    if (hipEventElapsedTime(&a, ctx->ev[1], ctx->ev[2]) == hipSuccess && hipEventElapsedTime(&b, ctx->ev[3], ctx->ev[4]) == hipSuccess) {
+        ctx->last_ms[3] = a + b;
+        ctx->last_ms[0] = a;
+        ctx->last_ms[2] = b;
+    }
+    return C_KZG_OK;
+}
+
+// One call of verify_blobs_core: its plan, its device buffers, and what its form hands the shared tail
+struct BlobVerify {
+    Trace tr{"verify_blobs"};
+    dev::DeviceCtx *const ctx;
+    const uint64_t n;
+    const bool resident;
+    VerifyPlan p;
+    bool partition = false;   // the GPU hash on sha_stream, validation and table build on side_stream[0] / [1]
+    // commitments [0,n), proofs [n,2n): compressed, decompression status, subgroup status (split validation), points
+    ABuf<uint8_t> d_ptb, d_st, d_st2, d_blobs_own;
+    ABuf<G1Affine> d_pts;
+    ABuf<Fr> d_z, d_y;
+    ABuf<uint32_t> d_bad;
+    ABuf<uint8_t> d_tbl, d_tbl_tmp, d_sums_scr;
+    ABuf<uint32_t> d_sc;
+    ABuf<G1XYZZ> d_sums;
+    ABuf<uint8_t> d_rows;        // resident: the rows of the batch transcript
+    std::vector<Fr> z, y;        // (outlive every host hasher of the call)
+    std::vector<G1Jac> hc, hp;   // host copies of the validated points (small form)
+    BlobVerify(dev::DeviceCtx *c, uint64_t n_, bool res) : ctx(c), n(n_), resident(res), p(plan_verify(n_, res)), z(n_), y(n_) {}
+    // The slot's arena at the size of the form -- with the call-time table when it fits: the table is an optimisation
+    // (1.3 GB at n = 4096), a device too full for it still verifies, by ladders -- and the buffers cut from it in order.
+    C_KZG_RET carve(Arena &ar) {
+        // (no converted polynomials: the evaluation reads the blobs' bytes -- verify.hip: k_eval_tree's BYTES form)
+        const size_t plain_bytes = (resident ? n * 160 : n * BYTES_PER_BLOB) + 2 * n * sizeof(Fr) + n * 4 +
+                                   2 * n * (48 + 2 + sizeof(G1Affine)) + 8192;   // (resident: the transcript rows, no blobs)
+        if (p.use_table && !ar.begin(plain_bytes + p.tbl_bytes + p.tbl_tmp + p.sums_scratch + 6 * n * 32 + 1024)) {
+            p.use_table = false;
+            p.tbl_bytes = p.tbl_tmp = p.sums_scratch = 0;
+        }
+        if (!p.use_table) OKM(ar.begin(plain_bytes));
+        d_ptb = {ar, 2 * n * 48}, d_st = {ar, 2 * n}, d_st2 = {ar, 2 * n}, d_blobs_own = {ar, resident ? 1 : n * BYTES_PER_BLOB};
+        d_pts = {ar, 2 * n}, d_z = {ar, n}, d_y = {ar, n}, d_bad = {ar, n};
+        d_tbl = {ar, p.use_table ? p.tbl_bytes : 1}, d_tbl_tmp = {ar, p.use_table ? p.tbl_tmp : 1};
+        d_sums_scr = {ar, p.use_table ? p.sums_scratch : 1}, d_sc = {ar, p.use_table ? 6 * n * 8 : 1};
+        d_sums = {ar, 3}, d_rows = {ar, resident ? n * 160 : 1};
+        OKM(d_ptb.p && d_st.p && d_st2.p && d_blobs_own.p && d_pts.p && d_z.p && d_y.p && d_bad.p && d_tbl.p && d_tbl_tmp.p &&
+            d_sums_scr.p && d_sc.p && d_sums.p && d_rows.p);
+        return C_KZG_OK;
+    }
+    // The hash of the challenges on the GPU: the enqueue-only step every GPU-hash form shares.  Partitioned, an event of its
+    // own orders the evaluation on the main stream after it.
+    C_KZG_RET enqueue_gpu_hash(const uint8_t *d_blob_bytes, const uint8_t *d_cb48) {
+        RC(dev::sha256_challenges_device(ctx, d_z.p, d_blob_bytes, d_cb48, n, partition ? ctx->sha_stream : nullptr));
         if (partition) {
-            // (an event of its own: stage_ev[1] means "subgroup flags written" in the split validation, which a
-            // host-pointer batch of 640..1023 blobs hashed on the GPU takes together with the partition; recording
-            // the hash there made the flags' read wait for the hash instead of the subgroup test)
-            if (!ctx->hash_ev) OKB(hipEventCreateWithFlags(&ctx->hash_ev, hipEventDisableTiming) == hipSuccess);
+            OKB(dev::ensure_event(ctx->hash_ev) == hipSuccess);
             OKB(hipEventRecord(ctx->hash_ev, ctx->sha_stream) == hipSuccess);
             OKB(hipStreamWaitEvent(ctx->stream, ctx->hash_ev, 0) == hipSuccess);   // the challenges, before the evaluation
         }
-        hash_enqueued = true;
         return C_KZG_OK;
-    };
-    if (resident && gpu_sha) RC(enqueue_hash());
-    if (!small) {
-        // commitments [0,n), proofs [n,2n): decompress + subgroup-check on the GPU, on the second stream
-        // so that the ladder kernel runs under the (host-blocking, pageable) copy of the blobs
-        // (only for batches whose blob copy is short: measured, a concurrent kernel slows a long pageable
-        // copy by more than the ~1.3 ms it hides -- n = 4096: 30 -> 37 ms; n = 64: 8.0 -> 5.6 ms)
-        // Below 1024 blobs the validation is also split: event 0 marks the decompressed points, the
-        // subgroup test (event 1) keeps running on the second stream underneath evaluation and sums.
-        // (resident inputs: nothing blocks the host, so the validation ladders always run on the second stream,
-        // underneath the challenge hashing -- the longest kernel of that form -- and the evaluation)
-        hipStream_t vs = (split_validation || resident) ? ctx->copy_stream : ctx->stream;
+    }
+    // Commitments [0,n), proofs [n,2n): decompress + subgroup-check on the GPU.  (resident inputs: nothing blocks the
+    // host, so the validation ladders always run on the second stream, underneath the challenge hashing and evaluation)
+    C_KZG_RET enqueue_validation(const Bytes48 *cb, const Bytes48 *pb) {
+        hipStream_t vs = (p.split_validation || resident) ? ctx->copy_stream : ctx->stream;
         if (partition && resident) vs = ctx->side_stream[0];
-        if (!ctx->stage_ev[0]) OKB(hipEventCreateWithFlags(&ctx->stage_ev[0], hipEventDisableTiming) == hipSuccess);
-        if (!ctx->stage_ev[1]) OKB(hipEventCreateWithFlags(&ctx->stage_ev[1], hipEventDisableTiming) == hipSuccess);
+        OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess);
         const hipMemcpyKind kind = resident ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        OKB(hipMemcpyAsync(d_ptb.p, d_cb, n * 48, kind, vs) == hipSuccess);
-        OKB(hipMemcpyAsync(d_ptb.p + n * 48, d_pb, n * 48, kind, vs) == hipSuccess);
-        if (split_validation) {
+        OKB(hipMemcpyAsync(d_ptb.p, cb, n * 48, kind, vs) == hipSuccess);
+        OKB(hipMemcpyAsync(d_ptb.p + n * 48, pb, n * 48, kind, vs) == hipSuccess);
+        if (p.split_validation) {
             RC(dev::decompress_g1_batch_device(ctx, d_pts.p, d_st.p, d_ptb.p, 2 * n, vs));
-            OKB(hipEventRecord(ctx->stage_ev[0], vs) == hipSuccess);
+            OKB(hipEventRecord(ctx->pts_ev, vs) == hipSuccess);
             RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pts.p, 2 * n, vs));
-            OKB(hipEventRecord(ctx->stage_ev[1], vs) == hipSuccess);
+            OKB(hipEventRecord(ctx->subgroup_ev, vs) == hipSuccess);
         } else {
             RC(dev::validate_g1_batch_device(ctx, d_pts.p, d_st.p, d_ptb.p, 2 * n, vs));
-            OKB(hipEventRecord(ctx->stage_ev[0], vs) == hipSuccess);
+            OKB(hipEventRecord(ctx->pts_ev, vs) == hipSuccess);
         }
+        return C_KZG_OK;
     }
-    hipStream_t table_stream = nullptr;
-    if (use_table) {
-        if (partition) {
-            table_stream = ctx->side_stream[1];
-        } else {
-            if (!ctx->aux_stream) OKB(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) == hipSuccess);
-            table_stream = ctx->aux_stream;
+    // The evaluation of a batch whose blobs are all in d_blobs_own: z to the device (host hash) or from it (GPU hash),
+    // then y and the blobs' flags; `underneath` is host work that runs while the GPU evaluates.
+    template <class F>
+    C_KZG_RET evaluate(F &&underneath) {
+        OKB(p.gpu_sha ? d_z.down(z.data(), n) : d_z.up(z.data(), n));
+        RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p, d_bad.p, d_blobs_own.p, d_z.p, n));
+        underneath();
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+        // (the evaluation is what reads the field elements: a blob with one >= r is known now, bytes.c:52-70)
+        std::vector<uint32_t> bad(n);
+        OKB(d_bad.down(bad.data(), n));
+        for (size_t i = 0; i < n; i++) {
+            if (bad[i]) return C_KZG_BADARGS;
         }
+        OKB(d_y.down(y.data(), n));
+        tr.mark("GPU evaluation (+ the proof's half of the check on the host)");
+        return C_KZG_OK;
     }
-    StreamDrain drain_aux{table_stream};
-    if (use_table) {
-        OKB(hipStreamWaitEvent(table_stream, ctx->stage_ev[0], 0) == hipSuccess);   // the validated points
-        RC(dev::call_table_enqueue(table_stream, &tbl, d_tbl.p, d_tbl_tmp.p, d_pts.p));
-        if (!ctx->table_ev) OKB(hipEventCreateWithFlags(&ctx->table_ev, hipEventDisableTiming) == hipSuccess);
-        OKB(hipEventRecord(ctx->table_ev, table_stream) == hipSuccess);
+    // ---- small form: host pointers, n <= SMALL_VERIFY_N ----
+    C_KZG_RET small_form(bool *ok, const Blob *blobs, const Bytes48 *cb, const Bytes48 *pb) {
+        hc.resize(n);
+        hp.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            if (validate_kzg_g1(hc[i], cb[i].bytes) != C_KZG_OK) return C_KZG_BADARGS;
+            if (validate_kzg_g1(hp[i], pb[i].bytes) != C_KZG_OK) return C_KZG_BADARGS;
+        }
+        tr.mark("host point validation");
+        Arena &ar = ctx->api_arena;
+        RC(carve(ar));
+        ArenaTrim trim(ar);
+        tr.mark("arena");
+        StreamDrain drain{ctx->copy_stream};   // (as in every form: the second stream idle before the arena is reused)
+        tr.mark("validation (+ call-time table) enqueued");
+        OKB(hipMemcpyAsync(d_blobs_own.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        OKB(hipMemsetAsync(d_bad.p, 0, n * 4, ctx->stream) == hipSuccess);
+        tr.mark("enqueue H2D (+ GPU validation, GPU challenges)");
+        hash_challenges(z.data(), blobs, cb, n);   // (a thread costs ~0.2 ms: not for these few blobs)
+        tr.mark("host SHA-256 challenges");
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+        tr.mark("wait for GPU");
+        ProofSide ps;
+        RC(evaluate([&]() {
+            if (n == 1) ps = verify_proof_side(z[0], hp[0], prepared_of(ctx));   // host work underneath the GPU's evaluation
+        }));
+        if (n == 1) {
+            // the single-blob form of the check (eip4844.c:537-595)
+            *ok = verify_with_proof_side(hc[0], y[0], ps, prepared_of(ctx));
+            tr.mark("[y]G1 + the commitment's Miller loop + final exponentiation");
+            return C_KZG_OK;
+        }
+        uint8_t digest[32];
+        host_batch_digest(digest, n, cb, pb, z.data(), y.data());
+        return tail(ok, digest);
     }
-    tr.mark("validation (+ call-time table) enqueued");
-    std::vector<Fr> z(n), y(n);
-    ProofSide ps;
-    uint8_t digest[32];
-    bool have_digest = false;   // the pipelined form hashes the batch transcript while the batch is in flight
-    if (piped) {
-        // ---- pipelined host-pointer form ----
+    // ---- one-copy form: host pointers, one copy of all blobs ----
+    // Challenges: on host threads, started BEFORE the blob copy -- a copy from pageable memory blocks this thread for its
+    // whole duration (3.5 us per blob), and with the x86 SHA extensions the hashing (2 us per blob on 32 threads) finishes
+    // underneath it.  Hosts without the extensions hash large batches on the GPU instead (a lane per blob; ~6 ms whatever
+    // the batch size), behind the copies.
+    C_KZG_RET one_copy_form(const Blob *blobs, const Bytes48 *cb, const Bytes48 *pb, uint8_t digest[32]) {
+        JoinThreads hasher;
+        const bool threaded = !p.gpu_sha && n >= 16;  // a thread costs ~0.2 ms: not for the single-blob call
+        if (threaded) hasher.spawn([&]() { hash_challenges(z.data(), blobs, cb, n); });
+        OKB(hipMemcpyAsync(d_blobs_own.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        OKB(hipMemsetAsync(d_bad.p, 0, n * 4, ctx->stream) == hipSuccess);
+        OKB(hipStreamWaitEvent(ctx->stream, ctx->pts_ev, 0) == hipSuccess);  // d_ptb, d_pts, d_st ready
+        if (p.gpu_sha) {
+            if (partition) {
+                // the blobs and the commitments' bytes reach HBM on the main stream: the hash stream starts behind them
+                OKB(dev::ensure_event(ctx->blobs_ev) == hipSuccess);
+                OKB(hipEventRecord(ctx->blobs_ev, ctx->stream) == hipSuccess);
+                OKB(hipStreamWaitEvent(ctx->sha_stream, ctx->blobs_ev, 0) == hipSuccess);
+            }
+            RC(enqueue_gpu_hash(d_blobs_own.p, d_ptb.p));
+        }
+        tr.mark("enqueue H2D (+ GPU validation, GPU challenges)");
+        hasher.join();
+        if (!p.gpu_sha && !threaded) hash_challenges(z.data(), blobs, cb, n);
+        tr.mark("host SHA-256 challenges");
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+        tr.mark("wait for GPU");
+        std::vector<uint8_t> st(2 * n);
+        OKB(d_st.down(st.data(), 2 * n));
+        for (size_t i = 0; i < 2 * n; i++) {
+            if (st[i]) return C_KZG_BADARGS;
+        }
+        RC(evaluate([]() {}));
+        host_batch_digest(digest, n, cb, pb, z.data(), y.data());
+        return C_KZG_OK;
+    }
+    // ---- pipelined form: host pointers, n >= verify_pipe_min, challenges hashed on the host ----
+    // The blobs cross PCIe in chunks on the copy stream -- DMA'd in place from page-locked caller memory, through pinned
+    // staging otherwise -- while earlier chunks are converted and evaluated and host threads hash the challenges and the
+    // batch transcript in order, so that only r, the three sums and the pairing follow the last byte.
+    C_KZG_RET piped_form(const Blob *blobs, const Bytes48 *cb, const Bytes48 *pb, uint8_t digest[32]) {
         // 256 blobs = 32 MB per chunk: ~0.6 ms of PCIe, 16 chunks at n = 4096 (profiles/r03_verify_pipeline_sweep.txt)
         static const size_t CH = (size_t)(dev::ab_knob("CKZG_HIP_VERIFY_CHUNK", 256) < 16 ? 16 : dev::ab_knob("CKZG_HIP_VERIFY_CHUNK", 256));
         const size_t nch = (n + CH - 1) / CH;
         const bool src_pinned = host_pointer_is_pinned(blobs);
         if (!src_pinned) OKM(ensure_pinned(ctx->h_stage, ctx->h_stage_bytes, CH * (size_t)BYTES_PER_BLOB));
-        for (int i = 2; i < 4; i++) {
-            if (!ctx->stage_ev[i]) OKB(hipEventCreateWithFlags(&ctx->stage_ev[i], hipEventDisableTiming) == hipSuccess);
-        }
-        hipEvent_t *copied = ctx->stage_ev + 2;
+        OKB(dev::ensure_event(ctx->stage_ev[0]) == hipSuccess && dev::ensure_event(ctx->stage_ev[1]) == hipSuccess);
+        hipEvent_t *copied = ctx->stage_ev;   // staging buffer b has been copied out
         // what the host needs back -- evaluations per chunk, the flags of the blobs and of the points at the end --
         // lands in page-locked memory behind the kernels that produce it, never through a blocking copy
         OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, n * sizeof(Fr)));
@@ -793,6 +882,17 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
         hasher.start(z.data(), blobs, cb);   // its destructor waits for the workers on every exit path
         TranscriptHasher transcript;         // likewise
         transcript.start(ctx->device, n, CH, landed, cb, pb, z.data(), h_y);
+        // the evaluation of chunk c (its challenges, conversion, evaluation, y back to the host), once its challenges exist
+        auto evaluate_chunk = [&](size_t c) -> C_KZG_RET {
+            const size_t po = c * CH, k = n - po < CH ? n - po : CH;
+            OKB(hasher.wait_chunk(c));
+            OKB(hipMemcpyAsync(d_z.p + po, z.data() + po, k * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p + po, d_bad.p + po, d_blobs_own.p + po * BYTES_PER_BLOB, d_z.p + po, k));
+            OKB(hipMemcpyAsync(h_y_bytes + po * sizeof(Fr), d_y.p + po, k * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+            OKB(hipEventRecord(landed[c], ctx->stream) == hipSuccess);
+            transcript.publish(c + 1);
+            return C_KZG_OK;
+        };
         bool used[2] = {false, false};
         for (size_t c = 0; c < nch; c++) {
             const size_t off = c * CH, k = n - off < CH ? n - off : CH;
@@ -810,25 +910,9 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
             }
             // the evaluation of chunk c - 1 is enqueued once its challenges exist: one chunk of slack, so that this
             // thread never waits for the hashers while there is a copy to issue
-            if (c >= 1) {
-                const size_t po = (c - 1) * CH;
-                OKB(hasher.wait_chunk(c - 1));
-                OKB(hipMemcpyAsync(d_z.p + po, z.data() + po, CH * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-                RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p + po, d_bad.p + po, d_blobs_own.p + po * BYTES_PER_BLOB, d_z.p + po, CH));
-                OKB(hipMemcpyAsync(h_y_bytes + po * sizeof(Fr), d_y.p + po, CH * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-                OKB(hipEventRecord(landed[c - 1], ctx->stream) == hipSuccess);
-                transcript.publish(c);
-            }
+            if (c >= 1) RC(evaluate_chunk(c - 1));
         }
-        {
-            const size_t po = (nch - 1) * CH, k = n - po;
-            OKB(hasher.wait_chunk(nch - 1));
-            OKB(hipMemcpyAsync(d_z.p + po, z.data() + po, k * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-            RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p + po, d_bad.p + po, d_blobs_own.p + po * BYTES_PER_BLOB, d_z.p + po, k));
-            OKB(hipMemcpyAsync(h_y_bytes + po * sizeof(Fr), d_y.p + po, k * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-            OKB(hipEventRecord(landed[nch - 1], ctx->stream) == hipSuccess);
-            transcript.publish(nch);
-        }
+        RC(evaluate_chunk(nch - 1));
         OKB(hipMemcpyAsync(h_bad, d_bad.p, n * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
         OKB(hipMemcpyAsync(h_st, d_st.p, 2 * n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
         tr.mark("chunked H2D + evaluation enqueued (challenges hashed in order on host threads)");
@@ -843,56 +927,30 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
         memcpy(y.data(), h_y, n * sizeof(Fr));
         tr.mark("flags checked");
         OKB(transcript.finish(digest));
-        have_digest = true;
         tr.mark("transcript thread joined");
-    } else {
-    // Challenges: on host threads, started BEFORE the blob copy -- a copy from pageable memory blocks
-    // this thread for its whole duration (3.5 us per blob), and with the x86 SHA extensions the hashing
-    // (2 us per blob on 32 threads) finishes underneath it.  Hosts without the extensions hash large
-    // batches on the GPU instead (a lane per blob; ~6 ms whatever the batch size).
-    struct Joiner {
-        std::thread t;
-        ~Joiner() {
-            if (t.joinable()) t.join();
-        }
-    } hasher;
-    auto hash_all = [&]() {
-        parallel_for(n, [&](size_t i) { z[i] = challenge_from_bytes(blobs[i].bytes, cb[i].bytes); });
-    };
-    const bool threaded = !gpu_sha && n >= 16;  // a thread costs ~0.2 ms: not for the single-blob call
-    if (threaded) hasher.t = std::thread(hash_all);
-    if (!resident) OKB(hipMemcpyAsync(d_blobs_own.p, blobs, n * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemsetAsync(d_bad.p, 0, n * 4, ctx->stream) == hipSuccess);
-    if (!small && !resident) OKB(hipStreamWaitEvent(ctx->stream, ctx->stage_ev[0], 0) == hipSuccess);  // d_ptb, d_pts, d_st ready
-    if (gpu_sha) {
-        if (partition && !resident) {
-            // the blobs and the commitments' bytes reach HBM on the main stream: the hash stream starts behind them
-            if (!ctx->stage_ev[2]) OKB(hipEventCreateWithFlags(&ctx->stage_ev[2], hipEventDisableTiming) == hipSuccess);
-            OKB(hipEventRecord(ctx->stage_ev[2], ctx->stream) == hipSuccess);
-            OKB(hipStreamWaitEvent(ctx->sha_stream, ctx->stage_ev[2], 0) == hipSuccess);
-        }
-        if (!hash_enqueued) RC(enqueue_hash());
+        tr.mark("GPU evaluation (+ the proof's half of the check on the host)");
+        return C_KZG_OK;
     }
-    tr.mark("enqueue H2D (+ GPU validation, GPU challenges)");
-    if (hasher.t.joinable()) hasher.t.join();
-    if (!gpu_sha && !threaded) hash_all();
-    tr.mark("host SHA-256 challenges");
-    if (resident) {
-        // resident inputs: nothing to learn from the host before the evaluation -- enqueue it straight away
+    // ---- resident form: inputs in HBM, challenges hashed on the GPU (enqueued before the validation) ----
+    // The device copies of the inputs ARE the caller's buffers, and nothing of them is read on the host: the rows of the
+    // batch transcript (commitment | z | y | proof) are assembled on the device, and only they (160 bytes per blob), y
+    // and the flags come back.  z comes back only for the ladder sums (the table's scalars are made from d_z).
+    C_KZG_RET resident_form(const uint8_t *d_blob_bytes, uint8_t digest[32]) {
+        OKB(hipMemsetAsync(d_bad.p, 0, n * 4, ctx->stream) == hipSuccess);
+        tr.mark("enqueue H2D (+ GPU validation, GPU challenges)");
+        tr.mark("host SHA-256 challenges");
+        // nothing to learn from the host before the evaluation -- enqueue it straight away
         RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p, d_bad.p, d_blob_bytes, d_z.p, n));
-        OKB(hipStreamWaitEvent(ctx->stream, ctx->stage_ev[0], 0) == hipSuccess);   // the validated points, their status, d_ptb
+        OKB(hipStreamWaitEvent(ctx->stream, ctx->pts_ev, 0) == hipSuccess);   // the validated points, their status, d_ptb
         RC(dev::batch_transcript_rows_device(ctx, d_rows.p, d_ptb.p, d_z.p, d_y.p, n));
         OKB(hipEventRecord(ctx->ev[2], ctx->stream) == hipSuccess);
-        uint8_t *h1 = static_cast<uint8_t *>(ctx->h_out[1]);
+        uint8_t *h1 = static_cast<uint8_t *>(ctx->h_out[1]);   // evaluations | blob flags | point flags
         OKB(hipMemcpyAsync(ctx->h_out[0], d_rows.p, n * 160, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
         OKB(hipMemcpyAsync(h1, d_y.p, n * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
         OKB(hipMemcpyAsync(h1 + n * sizeof(Fr), d_bad.p, n * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
         OKB(hipMemcpyAsync(h1 + n * (sizeof(Fr) + 4), d_st.p, 2 * n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-    }
-    OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-    tr.mark("wait for GPU");
-    if (resident) {
-        const uint8_t *h1 = static_cast<const uint8_t *>(ctx->h_out[1]);
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+        tr.mark("wait for GPU");
         const uint8_t *st = h1 + n * (sizeof(Fr) + 4);
         uint32_t any = 0;
         for (size_t i = 0; i < 2 * n; i++) any |= st[i];
@@ -901,79 +959,23 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
         for (size_t i = 0; i < n; i++) any |= bad[i];
         if (any) return C_KZG_BADARGS;
         memcpy(y.data(), h1, n * sizeof(Fr));
-        if (!use_table) OKB(d_z.down(z.data(), n));   // the ladder sums take their scalars from the host
-        // r's transcript (eip4844.c:597-680): the header, then the rows as the device left them
+        if (!p.use_table) OKB(d_z.down(z.data(), n));   // the ladder sums take their scalars from the host
+        // r's transcript: the header, then the rows as the device left them
         Sha256 h;
-        uint8_t head[32];
-        memcpy(head, "RCKZGBATCH___V1_", 16);
-        be64(head + 16, FIELD_ELEMENTS_PER_BLOB);
-        be64(head + 24, n);
-        h.update(head, 32);
+        batch_transcript_head(h, n);
         h.update(static_cast<const uint8_t *>(ctx->h_out[0]), n * 160);
         h.finish(digest);
-        have_digest = true;
-    } else {
-    if (!small) {
-        std::vector<uint8_t> st(2 * n);
-        OKB(d_st.down(st.data(), 2 * n));
-        for (size_t i = 0; i < 2 * n; i++) {
-            if (st[i]) return C_KZG_BADARGS;
-        }
-    }
-    if (gpu_sha) {
-        OKB(d_z.down(z.data(), n));
-    } else {
-        OKB(d_z.up(z.data(), n));
-    }
-    RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p, d_bad.p, d_blob_bytes, d_z.p, n));
-    if (n == 1) ps = verify_proof_side(z[0], hp[0], prepared_of(ctx));   // host work underneath the GPU's evaluation
-    OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-    // (the evaluation is what reads the field elements: a blob with one >= r is known now, bytes.c:52-70)
-    std::vector<uint32_t> bad(n);
-    OKB(d_bad.down(bad.data(), n));
-    for (size_t i = 0; i < n; i++) {
-        if (bad[i]) return C_KZG_BADARGS;
-    }
-    OKB(d_y.down(y.data(), n));
-    }
-    }
-    tr.mark("GPU evaluation (+ the proof's half of the check on the host)");
-    if (n == 1 && !resident) {
-        // the single-blob form of the check (eip4844.c:537-595)
-        *ok = verify_with_proof_side(hc[0], y[0], ps, prepared_of(ctx));
-        tr.mark("[y]G1 + the commitment's Miller loop + final exponentiation");
+        tr.mark("GPU evaluation (+ the proof's half of the check on the host)");
         return C_KZG_OK;
     }
-    // r = H("RCKZGBATCH___V1_" | u64be 4096 | u64be n | (C_i | z_i | y_i | proof_i)*)  (eip4844.c:597-680);
-    // valid compressed encodings are canonical, so the input bytes are the re-compressed bytes
-    if (!have_digest) {
-        Sha256 h;
-        uint8_t head[32], zb[64];
-        memcpy(head, "RCKZGBATCH___V1_", 16);
-        be64(head + 16, FIELD_ELEMENTS_PER_BLOB);
-        be64(head + 24, n);
-        h.update(head, 32);
-        for (size_t i = 0; i < n; i++) {
-            h.update(cb[i].bytes, 48);
-            fr_to_bytes(zb, z[i]);
-            fr_to_bytes(zb + 32, y[i]);
-            h.update(zb, 64);
-            h.update(pb[i].bytes, 48);
-        }
-        h.finish(digest);
-    }
-    Fr r = fr_from_bytes_reduce(digest);
-    tr.mark("batch challenge r (one SHA-256 stream over every C, z, y, proof)");
-    G1Jac lc[3];  // sum r^i proof_i, sum r^i z_i proof_i, sum r^i C_i
-    Fr ysum = Fr::zero();
-    if (use_table) {
-        // The sums over the call-time table.  Their scalars are made where their digits are needed: one lane per blob
-        // raises r to its index (k_rlc_scalars; the challenges z are in d_z since their chunks were evaluated), so only
-        // r crosses PCIe, and while the GPU recodes and accumulates the host adds up sum r^i y_i for its side of the check.
+    // The sums over the call-time table.  Their scalars are made where their digits are needed: one lane per blob raises r
+    // to its index (k_rlc_scalars; the challenges z are in d_z since their chunks were evaluated), so only r crosses PCIe,
+    // and while the GPU recodes and accumulates the host adds up sum r^i y_i for its side of the check.
+    C_KZG_RET table_sums(const Fr &r, G1Jac lc[3], Fr &ysum) {
         if (resident) OKB(hipEventRecord(ctx->ev[3], ctx->stream) == hipSuccess);
         OKB(hipStreamWaitEvent(ctx->stream, ctx->table_ev, 0) == hipSuccess);   // the table is complete
         RC(dev::rlc_scalars_enqueue(ctx->stream, d_sc.p, d_z.p, r, n));
-        RC(dev::table_sums_enqueue(ctx->stream, tbl, d_sums.p, d_sc.p, 3, d_sums_scr.p));
+        RC(dev::table_sums_enqueue(ctx->stream, p.tbl, d_sums.p, d_sc.p, 3, d_sums_scr.p));
         Fr pw = Fr::one();
         for (size_t i = 0; i < n; i++) {
             ysum = add(ysum, mul(pw, y[i]));
@@ -983,31 +985,25 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
         G1XYZZ hs[3];
         OKB(d_sums.down(hs, 3));
         for (int j = 0; j < 3; j++) lc[j] = jac_from_xyzz(hs[j]);
-        if (resident) {
-            float a = 0, b = 0;
-            OKB(hipEventRecord(ctx->ev[4], ctx->stream) == hipSuccess && dev::sync_event(ctx->ev[4]) == hipSuccess);
-            if (hipEventElapsedTime(&a, ctx->ev[1], ctx->ev[2]) == hipSuccess &&
-                hipEventElapsedTime(&b, ctx->ev[3], ctx->ev[4]) == hipSuccess) {
-                ctx->last_ms[3] = a + b;
-                ctx->last_ms[0] = a;
-                ctx->last_ms[2] = b;
-            }
-        }
-    } else {
-    std::vector<Fr> rpf(n), rzf(n);
-    Fr pw = Fr::one();
-    for (size_t i = 0; i < n; i++) {
-        rpf[i] = pw;
-        rzf[i] = mul(pw, z[i]);
-        ysum = add(ysum, mul(pw, y[i]));
-        pw = mul(pw, r);
+        return resident ? record_resident_kernel_ms(ctx) : C_KZG_OK;
     }
-    tr.mark("powers of r");
-    if (small) {
-        lc[0] = host_lincomb(hp, rpf);
-        lc[1] = host_lincomb(hp, rzf);
-        lc[2] = host_lincomb(hc, rpf);
-    } else {
+    // The sums by ladders: the scalars made on the host; the small form's few points summed there as well
+    C_KZG_RET ladder_sums(const Fr &r, G1Jac lc[3], Fr &ysum) {
+        std::vector<Fr> rpf(n), rzf(n);
+        Fr pw = Fr::one();
+        for (size_t i = 0; i < n; i++) {
+            rpf[i] = pw;
+            rzf[i] = mul(pw, z[i]);
+            ysum = add(ysum, mul(pw, y[i]));
+            pw = mul(pw, r);
+        }
+        tr.mark("powers of r");
+        if (p.small) {
+            lc[0] = host_lincomb(hp, rpf);
+            lc[1] = host_lincomb(hp, rzf);
+            lc[2] = host_lincomb(hc, rpf);
+            return C_KZG_OK;
+        }
         std::vector<RawScalar> rp(n), rz(n);
         for (size_t i = 0; i < n; i++) {
             rp[i] = raw_of(rpf[i]);
@@ -1015,38 +1011,85 @@ C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, cons
         }
         if (resident) OKB(hipEventRecord(ctx->ev[3], ctx->stream) == hipSuccess);
         LincombJob jobs[3] = {{d_pts.p + n, &rp}, {d_pts.p + n, &rz}, {d_pts.p, &rp}};
-        C_KZG_RET ret = gpu_lincomb_multi(ctx, lc, jobs, 3);
-        if (ret != C_KZG_OK) return ret;
-        if (resident) {
-            // kernel-only time of the resident form (ckzg_hip_last_kernel_ms, which = 3): validation + conversion +
-            // challenges + evaluation, and the three sums; the host transcript between them is not GPU time
-            float a = 0, b = 0;
-            OKB(hipEventRecord(ctx->ev[4], ctx->stream) == hipSuccess && dev::sync_event(ctx->ev[4]) == hipSuccess);
-            if (hipEventElapsedTime(&a, ctx->ev[1], ctx->ev[2]) == hipSuccess &&
-                hipEventElapsedTime(&b, ctx->ev[3], ctx->ev[4]) == hipSuccess) {
-                ctx->last_ms[3] = a + b;
-                ctx->last_ms[0] = a;
-                ctx->last_ms[2] = b;
+        RC(gpu_lincomb_multi(ctx, lc, jobs, 3));
+        return resident ? record_resident_kernel_ms(ctx) : C_KZG_OK;
+    }
+    // The tail every form of more than one blob shares: r, the three sums, the subgroup flags of a split validation
+    // (after the sums, which they make meaningless but not unsafe), the pairing check.
+    C_KZG_RET tail(bool *ok, const uint8_t digest[32]) {
+        Fr r = fr_from_bytes_reduce(digest);
+        tr.mark("batch challenge r (one SHA-256 stream over every C, z, y, proof)");
+        G1Jac lc[3];  // sum r^i proof_i, sum r^i z_i proof_i, sum r^i C_i
+        Fr ysum = Fr::zero();
+        RC(p.use_table ? table_sums(r, lc, ysum) : ladder_sums(r, lc, ysum));
+        if (p.split_validation) {
+            OKB(dev::sync_event(ctx->subgroup_ev) == hipSuccess);
+            std::vector<uint8_t> st2(2 * n);
+            OKB(d_st2.down(st2.data(), 2 * n));
+            for (size_t i = 0; i < 2 * n; i++) {
+                if (st2[i]) return C_KZG_BADARGS;  // a point outside G1: the sums above are discarded
             }
         }
+        tr.mark("transcript + lincombs");
+        // sum r^i (C_i - [y_i]G) = sum r^i C_i - [sum r^i y_i]G
+        G1Jac rhs = jac_add(jac_add(lc[2], jac_neg(g1_gen_mul_fr(ysum))), lc[1]);
+        // e(sum r^i proof_i, [s]G2) == e(rhs, G2)
+        *ok = pairing_product_is_one(jac_to_affine_fast(jac_neg(lc[0])), prepared_of(ctx)->s1, jac_to_affine_fast(rhs),
+                                     prepared_of(ctx)->gen);
+        tr.mark("pairing check");
+        return C_KZG_OK;
     }
+};
+
+// Shared core of verify_blob_kzg_proof and verify_blob_kzg_proof_batch: what every form but the small one enqueues
+// first (validation, call-time table; resident: the hash before them), then the form, then the tail.
+C_KZG_RET verify_blobs_core(bool *ok, const Blob *blobs, const Bytes48 *cb, const Bytes48 *pb, uint64_t n,
+                            const KZGSettings *s, dev::DeviceCtx *ctx, bool resident = false) {
+    BlobVerify v(ctx, n, resident);
+    if (v.p.small) return v.small_form(ok, blobs, cb, pb);
+    v.tr.mark("host point validation");
+    Arena &ar = ctx->api_arena;
+    RC(v.carve(ar));
+    ArenaTrim trim(ar);
+    v.tr.mark("arena");
+    if (resident) {
+        OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, n * 160));   // rows | evaluations + flags
+        OKB(hipEventRecord(ctx->ev[1], ctx->stream) == hipSuccess);
     }
-    if (split_validation) {
-        OKB(dev::sync_event(ctx->stage_ev[1]) == hipSuccess);
-        std::vector<uint8_t> st2(2 * n);
-        OKB(d_st2.down(st2.data(), 2 * n));
-        for (size_t i = 0; i < 2 * n; i++) {
-            if (st2[i]) return C_KZG_BADARGS;  // a point outside G1: the sums above are discarded
-        }
+    // whatever path leaves this function, the other streams must be idle before the arena is reused
+    // (each declared before the first enqueue on its stream: an early error return drains it too)
+    StreamDrain drain{ctx->copy_stream};
+    std::optional<GpuHashCall> hash_call;   // (counted only by calls that could partition; lives until the call returns)
+    if (v.p.partition_wanted) hash_call.emplace(ctx->device);
+    v.partition = v.p.partition_wanted && hash_call->alone && ensure_cu_partition(ctx);
+    StreamDrain drain_sha{v.partition ? ctx->sha_stream : nullptr}, drain_val{v.partition ? ctx->side_stream[0] : nullptr};
+    // resident: the hash HERE -- its inputs are the caller's buffers, nothing precedes it, and every 10 us the longest
+    // kernel of the call starts earlier is 10 us off the call
+    const uint8_t *d_blob_bytes = resident ? reinterpret_cast<const uint8_t *>(blobs) : v.d_blobs_own.p;
+    if (resident) RC(v.enqueue_gpu_hash(d_blob_bytes, reinterpret_cast<const uint8_t *>(cb)));
+    RC(v.enqueue_validation(cb, pb));
+    hipStream_t table_stream = nullptr;
+    if (v.p.use_table) {
+        if (!v.partition && !ctx->aux_stream) OKB(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) == hipSuccess);
+        table_stream = v.partition ? ctx->side_stream[1] : ctx->aux_stream;
     }
-    tr.mark("transcript + lincombs");
-    // sum r^i (C_i - [y_i]G) = sum r^i C_i - [sum r^i y_i]G
-    G1Jac rhs = jac_add(jac_add(lc[2], jac_neg(g1_gen_mul_fr(ysum))), lc[1]);
-    // e(sum r^i proof_i, [s]G2) == e(rhs, G2)
-    *ok = pairing_product_is_one(jac_to_affine_fast(jac_neg(lc[0])), prepared_of(ctx)->s1, jac_to_affine_fast(rhs),
-                                 prepared_of(ctx)->gen);
-    tr.mark("pairing check");
-    return C_KZG_OK;
+    StreamDrain drain_aux{table_stream};
+    if (v.p.use_table) {
+        OKB(hipStreamWaitEvent(table_stream, ctx->pts_ev, 0) == hipSuccess);   // the validated points
+        RC(dev::call_table_enqueue(table_stream, &v.p.tbl, v.d_tbl.p, v.d_tbl_tmp.p, v.d_pts.p));
+        OKB(dev::ensure_event(ctx->table_ev) == hipSuccess);
+        OKB(hipEventRecord(ctx->table_ev, table_stream) == hipSuccess);
+    }
+    v.tr.mark("validation (+ call-time table) enqueued");
+    uint8_t digest[32];
+    if (resident) {
+        RC(v.resident_form(d_blob_bytes, digest));
+    } else if (v.p.piped) {
+        RC(v.piped_form(blobs, cb, pb, digest));
+    } else {
+        RC(v.one_copy_form(blobs, cb, pb, digest));
+    }
+    return v.tail(ok, digest);
 }
 
 }  // namespace
@@ -1147,10 +1190,7 @@ static C_KZG_RET blob_proof_batch_on(dev::DeviceCtx *ctx, KZGProof *proofs, uint
         ABuf<int> d_hit(ar, m);
         OKM(d_blobs.p && d_ptb.p && d_pst.p && d_out.p && d_pts.p && d_poly.p && d_z.p && d_y.p && d_bad.p && d_q.p &&
             d_hit.p);
-        struct StreamDrain {  // the second stream must be idle before the arena is reused, on every exit path
-            hipStream_t s;
-            ~StreamDrain() { (void)dev::sync_stream(s); }
-        } drain{ctx->copy_stream};
+        StreamDrain drain{ctx->copy_stream};   // the second stream must be idle before the arena is reused, on every exit path
         std::vector<Fr> z(m);
         std::vector<uint8_t> pst(m);
         std::vector<uint32_t> bad(m);
@@ -1265,10 +1305,7 @@ static C_KZG_RET verify_point_proofs_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *
         memcpy(&tab[(size_t)(2 * j) * MILLER_STEPS * 2], q[j]->lam, sizeof q[j]->lam);
         memcpy(&tab[(size_t)(2 * j + 1) * MILLER_STEPS * 2], q[j]->c, sizeof q[j]->c);
     }
-    struct StreamDrain {  // nothing enqueued may outlive this frame (the host table) or the arena's reuse, on every exit path
-        hipStream_t s;
-        ~StreamDrain() { (void)dev::sync_stream(s); }
-    } drain{ctx->stream};
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive this frame (the host table) or the arena's reuse
     OKB(hipMemcpyAsync(d_tab.p, tab.data(), TAB * sizeof(Fp), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     std::vector<uint8_t> res(m);
     C_KZG_RET ret = C_KZG_OK;
@@ -1831,26 +1868,20 @@ static C_KZG_RET verify_cells_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *c
     OKB(hipMemcpyAsync(h_st, d_st.p, n + nc, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
     if (use_table)
         OKB(hipMemcpyAsync(d_pts.p + n + nc, ctx->d_mono, l * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
-    for (int i = 0; i < 4; i++) {
-        if (!ctx->stage_ev[i]) OKB(hipEventCreateWithFlags(&ctx->stage_ev[i], hipEventDisableTiming) == hipSuccess);
-    }
-    OKB(hipEventRecord(ctx->stage_ev[0], ctx->stream) == hipSuccess);
-    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->stage_ev[0], 0) == hipSuccess);
+    OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess &&
+        dev::ensure_event(ctx->table_ev) == hipSuccess && dev::ensure_event(ctx->flags_ev) == hipSuccess);
+    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
+    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
     RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pts.p, n + nc, ctx->copy_stream));
     OKB(hipMemcpyAsync(h_st2, d_st2.p, n + nc, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
-    OKB(hipEventRecord(ctx->stage_ev[1], ctx->copy_stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
     // whatever path leaves this function, the other streams must be idle before the arena is reused
-    struct StreamDrain {
-        hipStream_t s;
-        ~StreamDrain() {
-            if (s) (void)dev::sync_stream(s);
-        }
-    } drain{ctx->copy_stream};
+    StreamDrain drain{ctx->copy_stream};
     if (use_table) {
         if (!ctx->aux_stream) OKB(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) == hipSuccess);
-        OKB(hipStreamWaitEvent(ctx->aux_stream, ctx->stage_ev[0], 0) == hipSuccess);
+        OKB(hipStreamWaitEvent(ctx->aux_stream, ctx->pts_ev, 0) == hipSuccess);
         RC(dev::call_table_enqueue(ctx->aux_stream, &tbl, d_tbl.p, d_tbl_tmp.p, d_pts.p));
-        OKB(hipEventRecord(ctx->stage_ev[2], ctx->aux_stream) == hipSuccess);
+        OKB(hipEventRecord(ctx->table_ev, ctx->aux_stream) == hipSuccess);
     }
     StreamDrain drain_aux{use_table ? ctx->aux_stream : nullptr};
     // cells grouped by column (counting sort) for the aggregation kernel
@@ -1880,7 +1911,7 @@ static C_KZG_RET verify_cells_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *c
     // checked here, underneath it.  A small one (ladder sums): the subgroup test (~1 ms of dependent doublings) keeps
     // running on the second stream next to the sums, and the flags are checked after those.
     auto flags_ok = [&]() -> C_KZG_RET {
-        OKB(dev::sync_event(ctx->stage_ev[3]) == hipSuccess && dev::sync_event(ctx->stage_ev[1]) == hipSuccess);
+        OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
         for (size_t i = 0; i < n + nc; i++) {
             if (h_st[i] || h_st2[i]) return C_KZG_BADARGS;  // bad encoding / off the curve / outside G1
         }
@@ -1889,7 +1920,7 @@ static C_KZG_RET verify_cells_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *c
         }
         return C_KZG_OK;
     };
-    OKB(hipEventRecord(ctx->stage_ev[3], ctx->stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
     if (use_table) RC(flags_ok());
     tr.mark("copies, validation, grouping (underneath the transcript hash)");
     if (hash_job.submitted)
@@ -1937,7 +1968,7 @@ static C_KZG_RET verify_cells_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *c
     G1Jac lc[4];
     if (use_table) {
         OKB(hipMemcpyAsync(d_sc.p + 3 * row + (n + nc) * 8, d_interp.p, l * 32, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
-        OKB(hipStreamWaitEvent(ctx->stream, ctx->stage_ev[2], 0) == hipSuccess);   // the table is complete
+        OKB(hipStreamWaitEvent(ctx->stream, ctx->table_ev, 0) == hipSuccess);   // the table is complete
         RC(dev::table_sums_enqueue(ctx->stream, tbl, d_sums.p, d_sc.p, 4, d_sums_scr.p));
         G1XYZZ hs[4];
         OKB(d_sums.down(hs, 4));

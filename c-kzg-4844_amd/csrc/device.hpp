@@ -187,6 +187,13 @@ inline hipError_t sync_stream(hipStream_t s, int64_t spin_us = 100) {
 inline hipError_t sync_event(hipEvent_t ev, int64_t spin_us = 100) {
     return bounded_device_wait([ev]() { return hipEventQuery(ev); }, "event", (const void *)ev, spin_us);
 }
+// an event of a slot, created (timing disabled) on first use; left null when the runtime refuses
+inline hipError_t ensure_event(hipEvent_t &e) {
+    if (e) return hipSuccess;
+    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (r != hipSuccess) e = nullptr;
+    return r;
+}
 
 struct FixedBaseTable {
     G1Affine *d_table = nullptr;
@@ -335,9 +342,15 @@ struct DeviceCtx {
     G1Affine *d_lagr = nullptr;   // g1_values_lagrange_brp, affine, 4096 (bases of the commitment table; kept for widening)
     Scratch scratch;              // per slot: reused by every call that leases the slot
     Arena api_arena, lc_arena;    // temporaries of the host-pointer entry points / of gpu_lincomb_multi
-    hipEvent_t stage_ev[4] = {};  // copied[2], consumed[2] of the staging pipeline (created on first use)
-    hipEvent_t table_ev = nullptr;      // "the call-time table is complete" (verification; created on first use)
-    hipEvent_t hash_ev = nullptr;       // "the challenges are hashed" (partitioned verification; created on first use)
+    // events created on first use (ensure_event), each with one meaning within a call
+    hipEvent_t stage_ev[4] = {};  // the staging pipelines only: copied[2], consumed[2] (ckzg_api.hip, fk20.hip), copied[2]
+                                  // of the pipelined blob verification
+    hipEvent_t pts_ev = nullptr;        // verification: "the points are validated" (split validation: decompressed)
+    hipEvent_t subgroup_ev = nullptr;   // verification: "the subgroup flags are written" (cells: and copied to the host)
+    hipEvent_t blobs_ev = nullptr;      // "the blobs are in HBM" (host-pointer verification, before the partitioned GPU hash)
+    hipEvent_t flags_ev = nullptr;      // "the main stream's flags are copied to the host" (cell verification)
+    hipEvent_t table_ev = nullptr;      // "the call-time table is complete" (verification)
+    hipEvent_t hash_ev = nullptr;       // "the challenges are hashed" (partitioned verification)
     std::vector<hipEvent_t> chunk_ev;   // per-chunk events of the pipelined verification (grown on demand, kept)
     hipEvent_t ev[12] = {};       // timing events
     // The one-blob blob_to_kzg_commitment as a graph built node by node (copy in, flag reset, recoding, accumulate, fold +

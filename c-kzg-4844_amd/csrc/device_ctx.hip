@@ -201,8 +201,9 @@ static void destroy_slot(dev::DeviceCtx *ctx) {
         if (e) (void)hipEventDestroy(e);
     }
     for (auto e : ctx->chunk_ev) (void)hipEventDestroy(e);
-    if (ctx->table_ev) (void)hipEventDestroy(ctx->table_ev);
-    if (ctx->hash_ev) (void)hipEventDestroy(ctx->hash_ev);
+    for (auto e : {ctx->pts_ev, ctx->subgroup_ev, ctx->blobs_ev, ctx->flags_ev, ctx->table_ev, ctx->hash_ev}) {
+        if (e) (void)hipEventDestroy(e);
+    }
     if (ctx->one_commit.exec) (void)hipGraphExecDestroy(ctx->one_commit.exec);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);

@@ -1154,7 +1154,7 @@ int cells_and_proofs_device(DeviceCtx *ctx, uint8_t *d_cells, uint8_t *d_proofs,
         // else, so the three small kernels of the cells run on the slot's second stream underneath the first
         // kernels of the proof path instead of in front of them.
         for (int i = 0; i < 2; i++) {
-            if (!ctx->stage_ev[i]) HIP_TRY(hipEventCreateWithFlags(&ctx->stage_ev[i], hipEventDisableTiming));
+            HIP_TRY(dev::ensure_event(ctx->stage_ev[i]));
         }
         HIP_TRY(hipMemsetAsync(d_bad, 0, n * 4, ctx->stream));
         rc = cells_stage_enqueue(ctx, nullptr, d_poly, d_ext, d_bad, d_blobs, n);  // coefficients only
