@@ -116,6 +116,26 @@ class Kzg:
                    bytes(proof), self.sp)
         return ok.value
 
+    def compute_kzg_proof_batch(self, blobs, zs):
+        """ckzg_hip_compute_kzg_proof_batch: one compute_kzg_proof per (blob, z) item, on the GPU.  Returns (proofs, ys,
+        status): status[i] is the item's C_KZG_RET (1 = C_KZG_BADARGS: z or a blob element not canonical; its proof and
+        y are then unspecified)."""
+        n = len(blobs)
+        _check(len(zs) == n, "list lengths")
+        for b in blobs:
+            _check(len(b) == BYTES_PER_BLOB, "blob")
+        for z in zs:
+            _check(len(z) == 32, "z")
+        proofs = C.create_string_buffer(48 * max(n, 1))
+        ys = C.create_string_buffer(32 * max(n, 1))
+        st = (C.c_uint8 * max(n, 1))()
+        ret = self._fn("ckzg_hip_compute_kzg_proof_batch")(proofs, ys, st, b"".join(blobs), b"".join(zs), C.c_uint64(n),
+                                                           self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_compute_kzg_proof_batch -> C_KZG_RET %d" % ret)
+        return ([proofs.raw[48 * i:48 * i + 48] for i in range(n)], [ys.raw[32 * i:32 * i + 32] for i in range(n)],
+                [int(v) for v in st[:n]])
+
     def verify_kzg_proof_batch(self, commitments, zs, ys, proofs):
         """ckzg_hip_verify_kzg_proof_batch: one verify_kzg_proof per item, on the GPU.  Returns (ok, status): ok[i] is
         the item's verdict and status[i] its C_KZG_RET (1 = C_KZG_BADARGS: invalid point or field element)."""

@@ -17,21 +17,6 @@ using namespace ckzg::api;
 
 namespace {
 
-template <class T>
-struct DBuf {
-    T *p = nullptr;
-    size_t n = 0;
-    bool alloc(size_t count) {
-        n = count;
-        return hipMalloc((void **)&p, (count ? count : 1) * sizeof(T)) == hipSuccess;
-    }
-    bool up(const T *h, size_t count) { return hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice) == hipSuccess; }
-    bool down(T *h, size_t count) const { return hipMemcpy(h, p, count * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess; }
-    ~DBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
-
 #define RC(expr)                          \
     do {                                  \
         int _rc = (expr);                 \
@@ -101,60 +86,6 @@ G1Jac g1_mul_fr(const G1Jac &p, const Fr &k) {
     return host::g1_mul_glv_host(p, r.l);
 }
 
-// src/eip4844/eip4844.c:80-106
-bool fr_batch_inv(Fr *out, const Fr *a, size_t len) {
-    Fr acc = Fr::one();
-    for (size_t i = 0; i < len; i++) {
-        out[i] = acc;
-        acc = mul(acc, a[i]);
-    }
-    if (acc.is_zero()) return false;
-    acc = fr_inv(acc);
-    for (size_t i = len; i-- > 0;) {
-        out[i] = mul(out[i], acc);
-        acc = mul(acc, a[i]);
-    }
-    return true;
-}
-
-Fr fr_pow_u64(Fr a, uint64_t n) {
-    Fr out = Fr::one();
-    while (true) {
-        if (n & 1) out = mul(out, a);
-        if ((n >>= 1) == 0) break;
-        a = sqr(a);
-    }
-    return out;
-}
-
-// src/eip4844/blob.c:31-38
-C_KZG_RET blob_to_polynomial(Fr *p, const Blob *blob) {
-    for (size_t i = 0; i < FIELD_ELEMENTS_PER_BLOB; i++) {
-        if (!fr_from_bytes_canonical(p[i], blob->bytes + 32 * i)) return C_KZG_BADARGS;
-    }
-    return C_KZG_OK;
-}
-
-// src/eip4844/eip4844.c:192-240 (host form, used where the inverses are needed anyway)
-C_KZG_RET evaluate_host(Fr &out, const Fr *poly, const Fr &x, const KZGSettings *s) {
-    const size_t n = FIELD_ELEMENTS_PER_BLOB;
-    const Fr *dom = as_fr(s->brp_roots_of_unity);
-    std::vector<Fr> den(n), inv(n);
-    for (size_t i = 0; i < n; i++) {
-        if (x == dom[i]) {
-            out = poly[i];
-            return C_KZG_OK;
-        }
-        den[i] = sub(x, dom[i]);
-    }
-    if (!fr_batch_inv(inv.data(), den.data(), n)) return C_KZG_BADARGS;
-    Fr acc = Fr::zero();
-    for (size_t i = 0; i < n; i++) acc = add(acc, mul(mul(inv[i], dom[i]), poly[i]));
-    acc = mul(acc, fr_inv(fr_from_u64(n)));
-    out = mul(acc, sub(fr_pow_u64(x, n), Fr::one()));
-    return C_KZG_OK;
-}
-
 // "FSBLOBVERIFY_V1_" | u64be 0 | u64be 4096 | blob | commitment  (eip4844.c:147-178)
 Fr challenge_from_bytes(const uint8_t *blob, const uint8_t *commitment48) {
     Sha256 h;
@@ -200,52 +131,6 @@ bool verify_kzg_proof_impl(const G1Jac &commitment, const Fr &z, const Fr &y, co
                            const PreparedG2 *pg) {
     G1Jac lhs = jac_add(jac_add(commitment, jac_neg(g1_gen_mul_fr(y))), g1_mul_fr(proof, z));
     return pairing_product_is_one(jac_to_affine_fast(lhs), pg->gen, jac_to_affine_fast(jac_neg(proof)), pg->s1);
-}
-
-// quotient polynomial and its commitment (eip4844.c:417-494); the 4096-term MSM runs on the GPU
-C_KZG_RET compute_kzg_proof_impl(KZGProof *proof_out, Fr &y_out, const Fr *poly, const Fr &z,
-                                 const KZGSettings *s, dev::DeviceCtx *ctx) {
-    const size_t n = FIELD_ELEMENTS_PER_BLOB;
-    const Fr *dom = as_fr(s->brp_roots_of_unity);
-    C_KZG_RET ret = evaluate_host(y_out, poly, z, s);
-    if (ret != C_KZG_OK) return ret;
-    std::vector<Fr> den(n), inv(n), q(n);
-    size_t m = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (z == dom[i]) {
-            m = i + 1;
-            den[i] = Fr::one();
-            q[i] = Fr::zero();
-            continue;
-        }
-        q[i] = sub(poly[i], y_out);
-        den[i] = sub(dom[i], z);
-    }
-    if (!fr_batch_inv(inv.data(), den.data(), n)) return C_KZG_BADARGS;
-    for (size_t i = 0; i < n; i++) q[i] = mul(q[i], inv[i]);
-    if (m != 0) {
-        m--;
-        q[m] = Fr::zero();
-        for (size_t i = 0; i < n; i++) {
-            if (i == m) continue;
-            den[i] = mul(sub(z, dom[i]), z);
-        }
-        den[m] = Fr::one();
-        if (!fr_batch_inv(inv.data(), den.data(), n)) return C_KZG_BADARGS;
-        for (size_t i = 0; i < n; i++) {
-            if (i == m) continue;
-            q[m] = add(q[m], mul(mul(sub(poly[i], y_out), dom[i]), inv[i]));
-        }
-    }
-    std::vector<RawScalar> raw(n);
-    for (size_t i = 0; i < n; i++) raw[i] = raw_of(q[i]);
-    DBuf<RawScalar> d_sc;
-    DBuf<uint8_t> d_out;
-    OKM(d_sc.alloc(n) && d_out.alloc(48));
-    OKB(d_sc.up(raw.data(), n));
-    RC(dev::msm_commit_table_raw_device(ctx, d_out.p, (const uint32_t *)d_sc.p, 1));
-    OKB(d_out.down(proof_out->bytes, 48));
-    return C_KZG_OK;
 }
 
 // fn(0) ... fn(n - 1) on up to 32 threads: the caller takes part, the rest are jobs on the process-wide worker pool
@@ -1104,78 +989,124 @@ extern "C" void compute_challenge(fr_t *eval_challenge_out, const Blob *blob, co
     *as_fr(eval_challenge_out) = challenge_from_bytes(blob->bytes, c48);
 }
 
-static C_KZG_RET compute_kzg_proof_on(dev::DeviceCtx *ctx, KZGProof *proof_out, Bytes32 *y_out, const Blob *blob,
-                                      const Bytes32 *z_bytes, const KZGSettings *s) {
-    // eip4844.c:386-415.  Evaluation, quotient polynomial and MSM on the GPU; a z inside the evaluation
-    // domain (eip4844.c:458-481) takes the host form of the quotient instead.
-    Fr z, y;
-    if (!fr_from_bytes_canonical(z, z_bytes->bytes)) return C_KZG_BADARGS;
-    {
-        Arena &ar = ctx->api_arena;
-        OKM(ar.begin(BYTES_PER_BLOB + 2 * FIELD_ELEMENTS_PER_BLOB * sizeof(Fr) + 2 * sizeof(Fr) + 64));
-        ABuf<uint8_t> d_blob(ar, BYTES_PER_BLOB), d_out(ar, 48);
-        ABuf<Fr> d_poly(ar, FIELD_ELEMENTS_PER_BLOB), d_z(ar, 1), d_y(ar, 1);
-        ABuf<uint32_t> d_bad(ar, 1), d_q(ar, FIELD_ELEMENTS_PER_BLOB * 8);
-        ABuf<int> d_hit(ar, 1);
-        OKM(d_blob.p && d_out.p && d_poly.p && d_z.p && d_y.p && d_bad.p && d_q.p && d_hit.p);
-        OKB(hipMemcpyAsync(d_blob.p, blob->bytes, BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-        OKB(hipMemcpyAsync(d_z.p, &z, sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-        OKB(hipMemsetAsync(d_bad.p, 0, 4, ctx->stream) == hipSuccess);
-        RC(dev::bytes_to_fr_batch(ctx, d_poly.p, d_bad.p, d_blob.p, FIELD_ELEMENTS_PER_BLOB, FIELD_ELEMENTS_PER_BLOB));
-        RC(dev::eval_quotient_batch_device(ctx, d_y.p, d_q.p, d_hit.p, d_poly.p, d_z.p, 1));
-        RC(dev::msm_commit_table_raw_device(ctx, d_out.p, d_q.p, 1));
-        uint32_t bad = 0;
-        int hit = -1;
-        OKB(d_bad.down(&bad, 1) && d_hit.down(&hit, 1));
-        if (bad) return C_KZG_BADARGS;  // a non-canonical field element in the blob (blob.c:31-38)
-        if (hit < 0) {
-            OKB(d_y.down(&y, 1) && d_out.down(proof_out->bytes, 48));
-            fr_to_bytes(y_out->bytes, y);
-            return C_KZG_OK;
+// compute_kzg_proof (eip4844.c:386-415) over one chunk of k <= POINT_CHUNK items whose blobs and z are in HBM as bytes:
+// bytes -> Fr (an element >= r, in the blob or in z, flags the item: blob.c:31-38, bytes.c:52-70), y and the quotient
+// polynomial for every z -- outside the evaluation domain (k_eval_barycentric<true>) or on it (k_quotient_in_domain,
+// eip4844.c:458-481) --, y back to bytes, the statuses, and the 4096-term MSMs.  Everything runs on the slot's compute
+// stream, which msm_commit_table_raw_device drains before it returns.  d_status may be null.
+constexpr uint64_t POINT_CHUNK = 256;
+struct PointProofBufs {
+    ABuf<Fr> poly, z, y;
+    ABuf<uint32_t> bad, q;
+    ABuf<int> hit;
+    static size_t bytes(uint64_t m) {
+        return m * (2 * FIELD_ELEMENTS_PER_BLOB * sizeof(Fr) + 2 * sizeof(Fr) + sizeof(uint32_t) + sizeof(int));
+    }
+    PointProofBufs(Arena &ar, uint64_t m)
+        : poly(ar, m * FIELD_ELEMENTS_PER_BLOB), z(ar, m), y(ar, m), bad(ar, m), q(ar, m * FIELD_ELEMENTS_PER_BLOB * 8), hit(ar, m) {}
+    bool ok() const { return poly.p && z.p && y.p && bad.p && q.p && hit.p; }
+};
+
+static C_KZG_RET point_proofs_chunk(dev::DeviceCtx *ctx, const PointProofBufs &b, uint8_t *d_proofs48, uint8_t *d_ys32,
+                                    uint8_t *d_status, const uint8_t *d_blobs, const uint8_t *d_zs32, uint64_t k) {
+    OKB(hipMemsetAsync(b.bad.p, 0, k * sizeof(uint32_t), ctx->stream) == hipSuccess);
+    RC(dev::bytes_to_fr_batch(ctx, b.poly.p, b.bad.p, d_blobs, k * FIELD_ELEMENTS_PER_BLOB, FIELD_ELEMENTS_PER_BLOB));
+    RC(dev::bytes_to_fr_batch(ctx, b.z.p, b.bad.p, d_zs32, k, 1));
+    RC(dev::eval_quotient_batch_device(ctx, b.y.p, b.q.p, b.hit.p, b.poly.p, b.z.p, k));
+    RC(dev::fr_to_bytes_batch(ctx, d_ys32, b.y.p, k));
+    if (d_status) RC(dev::flags_to_status_enqueue(ctx, d_status, b.bad.p, k));
+    RC(dev::msm_commit_table_raw_device(ctx, d_proofs48, b.q.p, k));
+    return C_KZG_OK;
+}
+
+// One device's share of a host-pointer ckzg_hip_compute_kzg_proof_batch: per chunk, blobs and z to HBM, the chunk, and
+// proofs | ys | statuses back in one copy.
+static C_KZG_RET point_proofs_on(dev::DeviceCtx *ctx, KZGProof *proofs, Bytes32 *ys, uint8_t *status, const Blob *blobs,
+                                 const Bytes32 *zs, uint64_t n) {
+    if (n == 0) return C_KZG_OK;
+    const uint64_t m = n < POINT_CHUNK ? n : POINT_CHUNK;
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(m * (BYTES_PER_BLOB + 32 + 48 + 32 + 1) + PointProofBufs::bytes(m)));
+    ArenaTrim trim(ar);
+    ABuf<uint8_t> d_blobs(ar, m * BYTES_PER_BLOB), d_zb(ar, m * 32), d_res(ar, m * (48 + 32 + 1));
+    PointProofBufs b(ar, m);
+    OKM(d_blobs.p && d_zb.p && d_res.p && b.ok());
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the caller's buffers or the arena's reuse
+    std::vector<uint8_t> res(m * (48 + 32 + 1));
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t off = 0; off < n; off += POINT_CHUNK) {
+        const uint64_t k = n - off < POINT_CHUNK ? n - off : POINT_CHUNK;
+        OKB(hipMemcpyAsync(d_blobs.p, blobs + off, k * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        OKB(hipMemcpyAsync(d_zb.p, zs + off, k * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        RC(point_proofs_chunk(ctx, b, d_res.p, d_res.p + k * 48, d_res.p + k * 80, d_blobs.p, d_zb.p, k));
+        OKB(d_res.down(res.data(), k * (48 + 32 + 1)));
+        memcpy(proofs + off, res.data(), k * 48);
+        memcpy(ys + off, res.data() + k * 48, k * 32);
+        for (uint64_t i = 0; i < k; i++) {
+            const uint8_t st = res[k * 80 + i];
+            if (status) status[off + i] = st;
+            if (st) ret = C_KZG_BADARGS;
         }
     }
-    std::vector<Fr> poly(FIELD_ELEMENTS_PER_BLOB);
-    C_KZG_RET ret = blob_to_polynomial(poly.data(), blob);
-    if (ret != C_KZG_OK) return ret;
-    ret = compute_kzg_proof_impl(proof_out, y, poly.data(), z, s, ctx);
-    if (ret != C_KZG_OK) return ret;
-    fr_to_bytes(y_out->bytes, y);
-    return C_KZG_OK;
+    return ret;
+}
+
+extern "C" C_KZG_RET ckzg_hip_compute_kzg_proof_batch(KZGProof *proofs, Bytes32 *ys, uint8_t *status, const Blob *blobs,
+                                                     const Bytes32 *zs, uint64_t n, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        if (!proofs || !ys || !blobs || !zs) return C_KZG_BADARGS;
+        return for_each_device_shard(s, n, 64, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return point_proofs_on(ctx, proofs + lo, ys + lo, status ? status + lo : nullptr, blobs + lo, zs + lo, hi - lo);
+        });
+    });
+}
+
+extern "C" C_KZG_RET ckzg_hip_compute_kzg_proof_batch_device(void *d_proofs, void *d_ys, void *d_status, const void *d_blobs,
+                                                            const void *d_zs, uint64_t n, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        SettingsCtx *sc = settings_of(s);
+        if (!sc) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        const void *ptrs[5] = {d_proofs, d_ys, d_status, d_blobs, d_zs};
+        const int pool = pool_of_pointers(sc, ptrs, 5);
+        if (pool < 0 || !d_proofs || !d_ys || !d_blobs || !d_zs) return C_KZG_BADARGS;
+        Lease lease(s, pool);
+        dev::DeviceCtx *ctx = lease.ctx;
+        if (!ctx) return C_KZG_ERROR;
+        const uint64_t m = n < POINT_CHUNK ? n : POINT_CHUNK;
+        Arena &ar = ctx->api_arena;
+        OKM(ar.begin(PointProofBufs::bytes(m)));
+        ArenaTrim trim(ar);
+        PointProofBufs b(ar, m);
+        OKM(b.ok());
+        StreamDrain drain{ctx->stream};
+        uint8_t *proofs = static_cast<uint8_t *>(d_proofs), *ys = static_cast<uint8_t *>(d_ys), *st = static_cast<uint8_t *>(d_status);
+        const uint8_t *blobs = static_cast<const uint8_t *>(d_blobs), *zs = static_cast<const uint8_t *>(d_zs);
+        for (uint64_t off = 0; off < n; off += POINT_CHUNK) {
+            const uint64_t k = n - off < POINT_CHUNK ? n - off : POINT_CHUNK;
+            RC(point_proofs_chunk(ctx, b, proofs + off * 48, ys + off * 32, st ? st + off : nullptr, blobs + off * BYTES_PER_BLOB,
+                                  zs + off * 32, k));
+        }
+        return C_KZG_OK;
+    });
 }
 
 extern "C" C_KZG_RET compute_kzg_proof(KZGProof *proof_out, Bytes32 *y_out, const Blob *blob,
                                        const Bytes32 *z_bytes, const KZGSettings *s) {
-    return guarded([&]() -> C_KZG_RET {
-        Lease lease(s);
-        if (!lease.ctx) return C_KZG_ERROR;
-        return compute_kzg_proof_on(lease.ctx, proof_out, y_out, blob, z_bytes, s);
-    });
-}
-
-// compute_blob_kzg_proof with the evaluation and the quotient polynomial on the host (only the MSM on
-// the GPU): the general form, which also covers a challenge that falls inside the evaluation domain
-// (eip4844.c:458-481).  The batch entry point sends such blobs here.
-static C_KZG_RET blob_proof_host_quotient(dev::DeviceCtx *ctx, KZGProof *out, const Blob *blob,
-                                          const Bytes48 *commitment_bytes, const KZGSettings *s) {
-    std::vector<Fr> poly(FIELD_ELEMENTS_PER_BLOB);
-    G1Jac c;
-    Fr y;
-    C_KZG_RET ret = validate_kzg_g1(c, commitment_bytes->bytes);
-    if (ret != C_KZG_OK) return ret;
-    ret = blob_to_polynomial(poly.data(), blob);
-    if (ret != C_KZG_OK) return ret;
-    Fr z = challenge_from_bytes(blob->bytes, commitment_bytes->bytes);
-    return compute_kzg_proof_impl(out, y, poly.data(), z, s, ctx);
+    // eip4844.c:386-415: a batch of one
+    uint8_t st = 0;
+    return ckzg_hip_compute_kzg_proof_batch(proof_out, y_out, &st, blob, z_bytes, 1, s);
 }
 
 // compute_blob_kzg_proof for a batch: challenges on the host (SHA-256), evaluation + quotient
-// polynomial and the 4096-term MSMs on the GPU.
+// polynomial (a challenge in the evaluation domain included) and the 4096-term MSMs on the GPU.
 static C_KZG_RET blob_proof_batch_on(dev::DeviceCtx *ctx, KZGProof *proofs, uint8_t *status, const Blob *blobs,
-                                     const Bytes48 *commitments_bytes, uint64_t n, const KZGSettings *s) {
+                                     const Bytes48 *commitments_bytes, uint64_t n) {
     if (n == 0) return C_KZG_OK;
     C_KZG_RET ret = C_KZG_OK;
     std::vector<uint8_t> st(n, 0);
-    std::vector<int> redo;
     {
         const uint64_t CH = 256;
         const uint64_t m = n < CH ? n : CH;
@@ -1194,7 +1125,6 @@ static C_KZG_RET blob_proof_batch_on(dev::DeviceCtx *ctx, KZGProof *proofs, uint
         std::vector<Fr> z(m);
         std::vector<uint8_t> pst(m);
         std::vector<uint32_t> bad(m);
-        std::vector<int> hit(m);
         for (uint64_t off = 0; off < n; off += CH) {
             const uint64_t k = n - off < CH ? n - off : CH;
             // commitments must be valid G1 points (bytes_to_kzg_commitment, eip4844.c:513)
@@ -1236,23 +1166,14 @@ static C_KZG_RET blob_proof_batch_on(dev::DeviceCtx *ctx, KZGProof *proofs, uint
                 OKB(dev::sync_stream(ctx->copy_stream) == hipSuccess);
                 OKB(d_pst.down(pst.data(), k));
             }
-            OKB(d_bad.down(bad.data(), k) && d_hit.down(hit.data(), k));
+            OKB(d_bad.down(bad.data(), k));
             OKB(hipMemcpy(proofs + off, d_out.p, k * 48, hipMemcpyDeviceToHost) == hipSuccess);
             for (uint64_t i = 0; i < k; i++) {
                 if (pst[i] || bad[i]) {
                     st[off + i] = C_KZG_BADARGS;
                     ret = C_KZG_BADARGS;
-                } else if (hit[i] >= 0) {
-                    redo.push_back((int)(off + i));  // challenge inside the domain: scalar path below
                 }
             }
-        }
-    }
-    for (int i : redo) {
-        C_KZG_RET r = blob_proof_host_quotient(ctx, &proofs[i], &blobs[i], &commitments_bytes[i], s);
-        if (r != C_KZG_OK) {
-            st[i] = (uint8_t)r;
-            ret = r;
         }
     }
     if (status) memcpy(status, st.data(), n);
@@ -1267,7 +1188,7 @@ extern "C" C_KZG_RET ckzg_hip_compute_blob_kzg_proof_batch(KZGProof *proofs, uin
         if (n == 0) return C_KZG_OK;
         return for_each_device_shard(s, n, 64, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
             return blob_proof_batch_on(ctx, proofs + lo, status ? status + lo : nullptr, blobs + lo,
-                                       commitments_bytes + lo, hi - lo, s);
+                                       commitments_bytes + lo, hi - lo);
         });
     });
 }
@@ -1369,9 +1290,9 @@ extern "C" C_KZG_RET compute_blob_kzg_proof(KZGProof *out, const Blob *blob, con
                 Lease lease(s);
                 if (!lease.ctx) return C_KZG_ERROR;
                 C_KZG_RET r = blob_proof_batch_on(lease.ctx, reinterpret_cast<KZGProof *>(h_out), st, reinterpret_cast<const Blob *>(h_in),
-                                                  reinterpret_cast<const Bytes48 *>(h_in + UNITS * BYTES_PER_BLOB), n, s);
+                                                  reinterpret_cast<const Bytes48 *>(h_in + UNITS * BYTES_PER_BLOB), n);
                 // blob_proof_batch_on writes flags only on its last path, where a non-OK return is the code of a flagged
-                // unit (BADARGS, or ERROR / MALLOC from one unit's host quotient): the verdict is per unit, and the
+                // unit (BADARGS): the verdict is per unit, and the
                 // combiner demotes exactly BADARGS-with-flags to that -- an unflagged member must not inherit it
                 if (r != C_KZG_OK)
                     for (size_t i = 0; i < n; i++)

@@ -495,8 +495,11 @@ int cell_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_vec_rp, uint3
                              const uint32_t *d_cell_idx, const uint32_t *d_grp_start, const uint32_t *d_members,
                              const Fr &r, size_t n, size_t nc);
 int rlc_scalars_enqueue(hipStream_t stream, uint32_t *d_sc, const Fr *d_z, const Fr &r, size_t n);
+// y = p(z) and the quotient scalars of the opening at z, z in the evaluation domain (k_quotient_in_domain) or not
 int eval_quotient_batch_device(DeviceCtx *ctx, Fr *d_y, uint32_t *d_q_raw, int *d_hit, const Fr *d_poly,
                                const Fr *d_z, size_t n);
+// d_status[i] = d_flag[i] ? C_KZG_BADARGS : C_KZG_OK
+int flags_to_status_enqueue(DeviceCtx *ctx, uint8_t *d_status, const uint32_t *d_flag, size_t n);
 // stream: nullptr = the context's compute stream
 int validate_g1_batch_device(DeviceCtx *ctx, G1Affine *d_out, uint8_t *d_status, const uint8_t *d_in48,
                              size_t n, hipStream_t stream = nullptr);

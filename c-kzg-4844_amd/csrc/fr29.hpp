@@ -216,7 +216,9 @@ constexpr int PER = 8;       // terms per thread
 constexpr int WAVES = 8;     // waves of a workgroup: 8 x 64 x PER = 4096
 
 // prefix products of the thread's denominators (Montgomery's trick); returns the index of a domain point equal to
-// z, or -1.  pre[k] = prod_{j<k} (z - w_j), acc = the whole product (< 1.1 r).
+// z, or -1.  pre[k] = prod_{j<k} (z - w_j), acc = the whole product (< 1.1 r).  ONE_AT_HIT: the denominator of the
+// term whose root equals z is one instead of zero (the quotient at a domain point, quotient_in_domain below).
+template <bool ONE_AT_HIT = false>
 HD int forward(Fr29 *pre, Fr29 &acc, const Fr29 &z, const Fr29 *roots29, int first, int stride) {
     int hit = -1;
     acc = fr29_const(FR29_ONE);
@@ -224,8 +226,10 @@ HD int forward(Fr29 *pre, Fr29 &acc, const Fr29 &z, const Fr29 *roots29, int fir
     for (int k = 0; k < PER; k++) {
         const int i = first + k * stride;
         const Fr29 root = roots29[i];
-        if (fr29_equal(z, root)) hit = i;
+        const bool eq = fr29_equal(z, root);
+        if (eq) hit = i;
         pre[k] = acc;
+        if (ONE_AT_HIT && eq) continue;
         acc = fr29_mul(acc, fr29_sub_canonical(z, root));
     }
     return hit;
@@ -267,6 +271,41 @@ HD Fr29 backward(const Fr29 *pre, Fr29 inv, const Fr29 &z, const Fr29 *roots29, 
         const Fr29 t = fr29_mul(fr29_pack(poly[i].l), fr29_mul(di, root));   // p_i w_i / (z - w_i), radix 2^256
 #pragma unroll
         for (int j = 0; j < 9; j++) sum.l[j] += t.l[j];
+        if ((k & 3) == 0) fr29_carry(sum);
+    }
+    return sum;
+}
+
+// The quotient of the opening at a domain point z = w_m (eip4844.c:441-481), where y = p_m:
+//   q_i = (p_i - y) / (w_i - z) = (y - p_i) * 1/(z - w_i)      for i != m,
+//   q_m = sum_{i != m} (p_i - y) w_i / (z (z - w_i)) = -(1/z) sum_{i != m} w_i q_i,
+// so the terms i != m need the same inverses as the evaluation (forward<true> makes the denominator at m one) and the
+// reference's second batch inversion is not needed.  inv = 2^261 / acc on entry.  put(i, raw) receives q_i for the
+// thread's terms i != m as canonical integers (eight words); returns the thread's part of sum_{i != m} w_i q_i as an
+// integer (below 2^5 r, limbs carried).  q_m is the caller's: -(that sum, over all threads) * 1/z.
+template <class Put>
+HD Fr29 quotient_in_domain(const Fr29 *pre, Fr29 inv, const Fr29 &z, const Fr29 *roots29, const Fr *poly, const Fr &y,
+                           int m, int first, int stride, Put put) {
+    const Fr29 two5 = fr29_const(FR29_2POW5);
+    Fr29 sum;
+#pragma unroll
+    for (int i = 0; i < 9; i++) sum.l[i] = 0;
+#pragma unroll
+    for (int k = PER - 1; k >= 0; k--) {
+        const int i = first + k * stride;
+        if (i != m) {   // (the term at m had the denominator one: inv stays as it is)
+            const Fr29 root = roots29[i];
+            const Fr29 di = fr29_mul(inv, pre[k]);             // 1/(z - w_i)
+            if (k) inv = fr29_mul(inv, fr29_sub_canonical(z, root));
+            // (y - p_i) 2^256 times 2^261/(z - w_i) is q_i 2^256; times 2^5 (an integer) is q_i itself
+            const Fr29 q = fr29_canonical<0>(fr29_mul(fr29_mul(fr29_pack(sub(y, poly[i]).l), di), two5));
+            uint32_t raw[8];
+            fr29_unpack(raw, q);
+            put(i, raw);
+            const Fr29 t = fr29_mul(q, root);                  // w_i q_i, an integer (the radix of the root cancels)
+#pragma unroll
+            for (int j = 0; j < 9; j++) sum.l[j] += t.l[j];
+        }
         if ((k & 3) == 0) fr29_carry(sum);
     }
     return sum;

@@ -489,6 +489,29 @@ extern "C" int hs_fr29_eval(Fr *y, uint32_t *di_out, const Fr *poly, const Fr *z
     return -1;
 }
 
+// The quotient of the opening at the domain point z = brp_roots[m] through k_quotient_in_domain's algorithm (512
+// threads of 8 terms, ev29::forward<true>, one inversion per lane of the first wave, ev29::quotient_in_domain, q_m from
+// the roots table's 1/w).  q_out: 4096 x 8 words, canonical integers.
+extern "C" void hs_fr29_quotient_in_domain(uint32_t *q_out, const Fr *poly, int m, const Fr *brp_roots) {
+    constexpr int T = 64 * ev29::WAVES, NB = 4096;
+    std::vector<Fr29> roots29(NB + NB / 2), pre((size_t)T * ev29::PER), acc(T), parked(T), inv(T);
+    for (int i = 0; i < NB; i++) roots29[i] = fr29_from_fr(brp_roots[i]);
+    for (int j = 0; j < NB / 2; j++) roots29[NB + j] = fr29_canonical<0>(fr29_inv(roots29[2 * j]));
+    const Fr29 z = roots29[m];
+    for (int t = 0; t < T; t++) (void)ev29::forward<true>(&pre[(size_t)t * ev29::PER], acc[t], z, roots29.data(), t, T);
+    for (int l = 0; l < 64; l++)
+        ev29::invert_across([&](int w) { return acc[l + 64 * w]; }, [&](int w, const Fr29 &v) { parked[l + 64 * w] = v; },
+                            [&](int w) { return parked[l + 64 * w]; }, [&](int w, const Fr29 &v) { inv[l + 64 * w] = v; },
+                            [](const Fr29 &v) { return fr29_inv(v); });
+    Fr sum = Fr::zero();
+    for (int t = 0; t < T; t++)
+        sum = add(sum, ev29::to_fr_radix256(ev29::quotient_in_domain(
+                           &pre[(size_t)t * ev29::PER], inv[t], z, roots29.data(), poly, poly[m], m, t, T,
+                           [&](int i, const uint32_t *raw) { memcpy(q_out + (size_t)i * 8, raw, 32); })));
+    const Fr s = (m & 1) ? sum : sub(Fr::zero(), sum);
+    fr29_unpack(q_out + (size_t)m * 8, fr29_canonical<0>(fr29_mul(fr29_pack(s.l), roots29[NB + (m >> 1)])));
+}
+
 // One blob through k_eval_tree<LOG_PER>'s algorithm: 4096 >> LOG_PER threads each fold 2^LOG_PER leaves, six levels
 // of lane exchanges inside a wave (both lanes of a pair compute the parent), the waves' values by thread 0.
 // bytes != nullptr: the leaves come from the blob's bytes (k_eval_tree's BYTES form); *bad |= 1 for an element >= r.

@@ -53,6 +53,12 @@ constexpr size_t EVAL_ONE_WAVE_FROM = 256;   // polynomials per launch from whic
 constexpr size_t EVAL_TWO_PER_SIMD_FROM = 1024;   // ... above which a compute unit takes eight of them at a time
 
 __device__ __noinline__ Fr29 fr29_inv_dev(const Fr29 &a) { return fr29_inv(a); }
+// the same with the operand in registers: a called function's reference argument travels through scratch
+__device__ __noinline__ Fr29 fr29_inv_regs(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, uint32_t a4, uint32_t a5,
+                                           uint32_t a6, uint32_t a7, uint32_t a8) {
+    const Fr29 a = {{a0, a1, a2, a3, a4, a5, a6, a7, a8}};
+    return fr29_inv(a);
+}
 
 // the evaluation domain in fr29.hpp's form (canonical, radix 2^261), made once per context: out[i] = brp_roots[i],
 // i < 4096 (k_eval_barycentric), then tab[m] = 1 / brp_roots[2 m], m < 2048 (k_eval_tree)
@@ -271,7 +277,7 @@ __device__ __forceinline__ Fr29 ev_get(uint32_t (*sh)[EV_THREADS], int col) {
 //   q_i = (p_i - y)/(w_i - z) = (y - p_i) * 1/(z - w_i)          (eip4844.c:441-456)
 // as canonical little-endian scalars ready for the MSM recoding.  The inverses are parked in the
 // output buffer until y is known.  hit_out[blob] = index of the domain point equal to z, or -1;
-// for such a blob (eip4844.c:458-481) q is not produced here and the caller takes the scalar path.
+// for such a blob (eip4844.c:458-481) q is not produced here: k_quotient_in_domain writes it.
 template <bool QUOT>
 __global__ __launch_bounds__(EV_THREADS) void k_eval_barycentric(Fr *y_out, uint32_t *q_raw, int *hit_out,
                                                                  const Fr *poly, const Fr *zs,
@@ -368,6 +374,72 @@ __global__ __launch_bounds__(EV_THREADS) void k_eval_barycentric(Fr *y_out, uint
     }
 }
 
+// The quotient of an opening at a domain point z = w_m (eip4844.c:458-481), for the items k_eval_barycentric<true>
+// found there (hit[item] = m; it has written y = p_m): one workgroup per item of the launch, and a workgroup whose item
+// has hit < 0 leaves at once.  Same shape as k_eval_barycentric -- a thread's eight terms, one inversion per lane of
+// the first wave for the eight waves' products (ev29::invert_across) -- with the denominator at m made one
+// (ev29::forward<true>), so that q_i = (y - p_i)/(z - w_i), i != m, comes out of ONE batch inversion; then
+//   q_m = -(1/z) sum_{i != m} w_i q_i      (ev29::quotient_in_domain)
+// where 1/z = 1/w_m is a domain point itself: tab[m >> 1] = 1/w_{2 (m >> 1)} of the roots table, and in bit-reversed
+// order w_{2j+1} = w_{2j} w^2048 = -w_{2j}.  Output: canonical raw scalars, [item][4096][8], as k_eval_barycentric.
+__global__ __launch_bounds__(EV_THREADS) void k_quotient_in_domain(uint32_t *q_raw, const int *hit, const Fr *poly,
+                                                                   const uint32_t *roots29_words) {
+    __shared__ uint32_t sh[9][EV_THREADS];    // the threads' products, then their inverses; later the sum tree
+    __shared__ uint32_t sh2[9][EV_THREADS];   // the first wave's prefix products over the waves
+    const int m = hit[blockIdx.x];
+    if (m < 0) return;   // (the whole workgroup: z is outside the domain)
+    const int tid = threadIdx.x;
+    const Fr *p = poly + (size_t)blockIdx.x * N_BLOB;
+    uint32_t *q = q_raw + (size_t)blockIdx.x * N_BLOB * 8;
+    const Fr29 *roots29 = reinterpret_cast<const Fr29 *>(roots29_words);
+    const Fr29 z = roots29[m];
+    const Fr y = vld_fr(p + m);
+    Fr29 pre[EV_PER], acc;
+    (void)ev29::forward<true>(pre, acc, z, roots29, tid, EV_THREADS);
+    ev_put(sh, tid, acc);
+    __syncthreads();
+    if (tid < 64) {
+        ev29::invert_across([&](int w) { return ev_get(sh, tid + 64 * w); },
+                            [&](int w, const Fr29 &v) { ev_put(sh2, tid + 64 * w, v); },
+                            [&](int w) { return ev_get(sh2, tid + 64 * w); },
+                            [&](int w, const Fr29 &v) { ev_put(sh, tid + 64 * w, v); },
+                            [](const Fr29 &v) {
+                                return fr29_inv_regs(v.l[0], v.l[1], v.l[2], v.l[3], v.l[4], v.l[5], v.l[6], v.l[7], v.l[8]);
+                            });
+    }
+    __syncthreads();
+    Fr sum = ev29::to_fr_radix256(ev29::quotient_in_domain(
+        pre, ev_get(sh, tid), z, roots29, p, y, m, tid, EV_THREADS, [&](int i, const uint32_t *raw) {
+            uint4 *slot = reinterpret_cast<uint4 *>(q + (size_t)i * 8);
+            slot[0] = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+            slot[1] = make_uint4(raw[4], raw[5], raw[6], raw[7]);
+        }));
+    __syncthreads();   // every thread has read its inverse: the rows are free for the sum
+    for (int s = EV_THREADS / 2; s >= 1; s >>= 1) {
+        if (tid >= s && tid < 2 * s) {
+#pragma unroll
+            for (int k = 0; k < 8; k++) sh[k][tid - s] = sum.l[k];
+        }
+        __syncthreads();
+        if (tid < s) {
+            Fr o;
+#pragma unroll
+            for (int k = 0; k < 8; k++) o.l[k] = sh[k][tid];
+            sum = add(sum, o);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        // sum = sum_{i != m} w_i q_i (an integer); q_m = -sum / w_m = (m odd ? sum : -sum) * tab[m >> 1]
+        const Fr s = (m & 1) ? sum : sub(Fr::zero(), sum);
+        uint32_t raw[8];
+        fr29_unpack(raw, fr29_canonical<0>(fr29_mul(fr29_pack(s.l), roots29[N_BLOB + (m >> 1)])));
+        uint4 *slot = reinterpret_cast<uint4 *>(q + (size_t)m * 8);
+        slot[0] = make_uint4(raw[0], raw[1], raw[2], raw[3]);
+        slot[1] = make_uint4(raw[4], raw[5], raw[6], raw[7]);
+    }
+}
+
 int eval_blob_bytes_batch_device(DeviceCtx *ctx, Fr *d_y, uint32_t *d_bad, const uint8_t *d_blob_bytes, const Fr *d_z, size_t n) {
     if (!n) return 0;
     const uint32_t *tab = ctx->d_brp_roots29 + (size_t)N_BLOB * 9;
@@ -444,13 +516,29 @@ int rlc_scalars_enqueue(hipStream_t stream, uint32_t *d_sc, const Fr *d_z, const
     return 0;
 }
 
-// y_i = p_i(z_i) and the quotient scalars q (canonical limbs, [n][4096][8]); d_hit[i] >= 0 flags a
-// blob whose z lies in the evaluation domain
+// y_i = p_i(z_i) and the quotient scalars q (canonical limbs, [n][4096][8]) for every z, in the evaluation domain or
+// not; d_hit[i] = index of the domain point equal to z_i, or -1 (n ints)
 int eval_quotient_batch_device(DeviceCtx *ctx, Fr *d_y, uint32_t *d_q_raw, int *d_hit, const Fr *d_poly,
                                const Fr *d_z, size_t n) {
     if (!n) return 0;
     hipLaunchKernelGGL(k_eval_barycentric<true>, dim3((unsigned)n), dim3(EV_THREADS), 0, ctx->stream, d_y,
                        d_q_raw, d_hit, d_poly, d_z, ctx->d_brp_roots29);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_quotient_in_domain, dim3((unsigned)n), dim3(EV_THREADS), 0, ctx->stream, d_q_raw, d_hit,
+                       d_poly, ctx->d_brp_roots29);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// C_KZG_RET per item from a 32-bit flag per item: status[i] = flag[i] ? C_KZG_BADARGS : C_KZG_OK
+__global__ void k_flags_to_status(uint8_t *status, const uint32_t *flag, size_t n) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) status[i] = flag[i] ? 1 : 0;
+}
+
+int flags_to_status_enqueue(DeviceCtx *ctx, uint8_t *d_status, const uint32_t *d_flag, size_t n) {
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_flags_to_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_status, d_flag, n);
     HIP_TRY(hipGetLastError());
     return 0;
 }

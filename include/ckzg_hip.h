@@ -156,6 +156,23 @@ C_KZG_RET ckzg_hip_compute_blob_kzg_proof_batch(KZGProof *proofs, uint8_t *statu
                                                 const Bytes48 *commitments_bytes, uint64_t n,
                                                 const KZGSettings *s);
 
+/* compute_kzg_proof (src/eip4844/eip4844.c:386-415) over n independent (blob, z) items: for every i,
+ * (status[i], proofs[i], ys[i]) is exactly (return value, *proof_out, *y_out) of
+ * compute_kzg_proof(&proofs[i], &ys[i], &blobs[i], &zs[i], s).  Returns C_KZG_BADARGS if any item is invalid (z not
+ * canonical, or a non-canonical field element in the blob): its status[i] is 1 and its outputs are unspecified, the
+ * other items are still computed and written.  C_KZG_ERROR / C_KZG_MALLOC if the call itself failed.  status may be
+ * NULL; NULL outputs or inputs with n > 0 give C_KZG_BADARGS.  Every item runs on the GPU, a z inside the evaluation
+ * domain (z = brp_roots[i] opens field element i, y = that element) included; compute_kzg_proof is a batch of one. */
+C_KZG_RET ckzg_hip_compute_kzg_proof_batch(KZGProof *proofs, Bytes32 *ys, uint8_t *status, const Blob *blobs,
+                                           const Bytes32 *zs, uint64_t n, const KZGSettings *s);
+
+/* Same with blobs (n Blob), zs (n x 32 bytes), proofs (n x 48), ys (n x 32) and status (n bytes; may be NULL) resident
+ * in HBM.  z is parsed and checked and y written back as bytes on the device.  As for
+ * ckzg_hip_blob_to_kzg_commitment_batch_device, invalid items are reported through d_status ONLY (d_status[i] = 1 =
+ * C_KZG_BADARGS): the return value is C_KZG_OK unless the call itself failed. */
+C_KZG_RET ckzg_hip_compute_kzg_proof_batch_device(void *d_proofs, void *d_ys, void *d_status, const void *d_blobs,
+                                                  const void *d_zs, uint64_t n, const KZGSettings *s);
+
 /* verify_kzg_proof (src/eip4844/eip4844.c) over n independent items, one verdict each:
  * for every i, (status[i], ok[i]) is exactly (return value, *ok) of verify_kzg_proof(&commitments[i], &zs[i], &ys[i],
  * &proofs[i], s).  Returns C_KZG_BADARGS if any item is invalid (its ok[i] = false; the verdicts of the other items
