@@ -239,6 +239,37 @@ class Kzg:
                    b"".join(cells), b"".join(proofs), C.c_uint64(n), self.sp)
         return ok.value
 
+    def verify_cell_kzg_proof_batch_groups(self, groups):
+        """ckzg_hip_verify_cell_kzg_proof_batch_groups: one verify_cell_kzg_proof_batch per group, in one call.  groups
+        is a list of (commitments, cell_indices, cells, proofs) tuples.  Returns (ok, status): ok[g] is the group's
+        verdict and status[g] its C_KZG_RET (1 = C_KZG_BADARGS: invalid index, point or field element)."""
+        g = len(groups)
+        start = [0]
+        flat = ([], [], [], [])
+        for grp in groups:
+            _check(len(grp) == 4, "a group is (commitments, cell_indices, cells, proofs)")
+            commitments, cell_indices, cells, proofs = grp
+            n = len(cells)
+            _check(len(commitments) == n and len(cell_indices) == n and len(proofs) == n, "list lengths")
+            for c in cells:
+                _check(len(c) == BYTES_PER_CELL, "cell")
+            for c in list(commitments) + list(proofs):
+                _check(len(c) == 48, "commitment/proof")
+            for i in cell_indices:
+                _check(0 <= i < 1 << 64, "cell index")
+            for dst, src in zip(flat, grp):
+                dst.extend(src)
+            start.append(start[-1] + n)
+        total = start[-1]
+        ok = (C.c_bool * max(g, 1))()
+        st = (C.c_uint8 * max(g, 1))()
+        ret = self._fn("ckzg_hip_verify_cell_kzg_proof_batch_groups")(
+            ok, st, b"".join(flat[0]), (C.c_uint64 * max(total, 1))(*flat[1]), b"".join(flat[2]), b"".join(flat[3]),
+            (C.c_uint64 * (g + 1))(*start), C.c_uint64(g), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_verify_cell_kzg_proof_batch_groups -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:g]], [int(v) for v in st[:g]]
+
     # ---- test-exposed internals (src/eip4844/eip4844.h:84, src/eip7594/eip7594.h:59-68) ----
     def compute_challenge(self, blob, commitment):
         _check(len(blob) == BYTES_PER_BLOB, "blob")

@@ -9,6 +9,9 @@
 
 #include "api_common.hpp"
 #include <optional>
+#include <string_view>
+#include <unordered_map>
+#include "cell_groups_plan.hpp"
 #include "combiner.hpp"
 
 using namespace ckzg;
@@ -134,37 +137,54 @@ bool verify_kzg_proof_impl(const G1Jac &commitment, const Fr &z, const Fr &y, co
 }
 
 // fn(0) ... fn(n - 1) on up to 32 threads: the caller takes part, the rest are jobs on the process-wide worker pool
-// (no thread is created or joined per call).  fn must not throw and must not itself wait for pool jobs -- a pool
-// worker never blocks on another pool job; the callers of this function are never pool workers.
-void parallel_for(size_t n, const std::function<void(size_t)> &fn) {
-    size_t nt = (size_t)host_thread_budget();
-    if (nt > 32) nt = 32;
-    if (nt > n) nt = n;
-    if (nt <= 1) {
-        for (size_t i = 0; i < n; i++) fn(i);
-        return;
-    }
-    struct Shared {
-        std::atomic<size_t> next{0};
-        std::atomic<uint32_t> active{0};   // pool jobs of this call that have not returned yet (futex word)
-    } sh;
-    auto loop = [&sh, &fn, n]() {
+// (no thread is created or joined per call).  start() hands the loop to up to host_thread_budget() - 1 pool workers and
+// returns, so that the caller can do something else first; finish() makes the caller take part and waits for the rest
+// (asleep, not spinning: the stragglers may need this core).  fn must not throw and must not itself wait for pool
+// jobs -- a pool worker never blocks on another pool job; the callers are never pool workers.
+struct BackgroundFor {
+    std::atomic<size_t> next{0};
+    std::atomic<uint32_t> active{0};   // pool jobs of this call that have not returned yet (futex word)
+    size_t n = 0;
+    std::function<void(size_t)> fn;
+    const char *what = "parallel_for jobs";
+    void loop() {
         for (;;) {
-            const size_t i = sh.next.fetch_add(1, std::memory_order_relaxed);
+            const size_t i = next.fetch_add(1, std::memory_order_relaxed);
             if (i >= n) return;
             fn(i);
         }
-    };
-    for (size_t t = 1; t < nt; t++) {
-        sh.active.fetch_add(1, std::memory_order_relaxed);
-        if (!WorkerPool::get().submit([&sh, loop]() {
-                loop();
-                if (sh.active.fetch_sub(1, std::memory_order_acq_rel) == 1) futex_wake(&sh.active, INT_MAX);
-            }))
-            sh.active.fetch_sub(1, std::memory_order_relaxed);
     }
-    loop();
-    wait_host_work_done(&sh.active, "parallel_for jobs");   // (asleep, not spinning: the stragglers may need this core)
+    void start() {
+        size_t nt = (size_t)host_thread_budget();
+        if (nt > 32) nt = 32;
+        if (nt > n) nt = n;
+        for (size_t t = 1; t < nt; t++) {
+            active.fetch_add(1, std::memory_order_relaxed);
+            if (!WorkerPool::get().submit([this]() {
+                    loop();
+                    if (active.fetch_sub(1, std::memory_order_acq_rel) == 1) futex_wake(&active, INT_MAX);
+                }))
+                active.fetch_sub(1, std::memory_order_relaxed);
+        }
+    }
+    void finish() {
+        loop();
+        wait_host_work_done(&active, what);
+    }
+    // an early return: nothing is picked up any more, and nothing fn reads may die before the workers are through
+    ~BackgroundFor() {
+        next.store(n, std::memory_order_relaxed);
+        wait_host_work_done(&active, what);
+    }
+};
+
+// the form whose caller has nothing else to do meanwhile
+void parallel_for(size_t n, const std::function<void(size_t)> &fn) {
+    BackgroundFor bf;
+    bf.n = n;
+    bf.fn = fn;
+    bf.start();
+    bf.finish();
 }
 
 // Several variable-base lincombs sum_i k_i P_i in ONE launch.  Job j takes n points starting at
@@ -1937,6 +1957,247 @@ extern "C" C_KZG_RET verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commit
         });
         if (ret == C_KZG_OK) *ok = all_ok.load() != 0;
         return ret;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// ckzg_hip_verify_cell_kzg_proof_batch_groups: many cell batches in one call, one verdict per group
+// ------------------------------------------------------------------------------------------
+
+// One group through the single-batch path: (status, ok) = (return value, *ok) of verify_cell_kzg_proof_batch on it
+static C_KZG_RET verify_one_cell_group(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                       const uint64_t *cell_indices, const Cell *cells, const Bytes48 *proofs_bytes, uint64_t n,
+                                       const KZGSettings *s) {
+    *ok = false;
+    *status = (uint8_t)C_KZG_OK;
+    if (n == 0) {
+        *ok = true;
+        return C_KZG_OK;
+    }
+    bool res = false;
+    C_KZG_RET r = C_KZG_OK;
+    for (uint64_t i = 0; i < n; i++) {
+        if (cell_indices[i] >= CELLS_PER_EXT_BLOB) r = C_KZG_BADARGS;
+    }
+    if (r == C_KZG_OK) r = verify_cells_on(ctx, &res, commitments_bytes, cell_indices, cells, proofs_bytes, n, s);
+    if (r == C_KZG_OK) *ok = res;
+    if (r == C_KZG_BADARGS) *status = (uint8_t)C_KZG_BADARGS;
+    return r;
+}
+
+// G groups over start[G] cells (start[0] = 0) on one device, as one chunk.  Everything that costs latency rather than
+// work is paid once for the chunk: the points are validated in one launch each (the commitments deduplicated across
+// the whole chunk), the cells converted in one, and after the groups' challenges have been hashed on the host pool the
+// segmented kernels of verify.hip make every group's scalars, aggregate and interpolate its columns and run the two
+// sums of every group -- final_g = sum w_j C_j + sum r^i h^64 proof_i - sum interp_g[k] [s^k]_1 and
+// proof_lc_g = sum r^i proof_i -- in ONE pass of the ladder kernels.  The 2 G points come back and every valid group
+// gets its own two-pairing check on the host pool.  Validation flags are folded into per-group status: an invalid
+// point, index or field element marks the groups that use it and says nothing about the others.
+static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                       const uint64_t *cell_indices, const Cell *cells, const Bytes48 *proofs_bytes,
+                                       const uint64_t *start, size_t G, const KZGSettings *s) {
+    const size_t N = (size_t)start[G], l = FIELD_ELEMENTS_PER_CELL;
+    for (size_t g = 0; g < G; g++) {
+        ok[g] = false;
+        status[g] = (uint8_t)C_KZG_OK;
+    }
+    if (N == 0) {
+        for (size_t g = 0; g < G; g++) ok[g] = true;
+        return C_KZG_OK;
+    }
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    Trace tr("verify_cell_groups");
+    auto stage = [&](const char *name) -> bool {   // (a traced call waits after every stage, so that the marks are the stages' times)
+        if (tr.on && dev::sync_stream(ctx->stream) != hipSuccess) return false;
+        tr.mark(name);
+        return true;
+    };
+    std::vector<uint8_t> invalid(G, 0);
+    // the chunk's distinct commitments: validated once, however many groups repeat them
+    std::vector<uint32_t> cell_commit(N);
+    std::vector<Bytes48> uniq;
+    {
+        std::unordered_map<std::string_view, uint32_t> ids;
+        ids.reserve(256);
+        for (size_t i = 0; i < N; i++) {
+            auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(commitments_bytes[i].bytes), 48), (uint32_t)uniq.size());
+            if (it.second) uniq.push_back(commitments_bytes[i]);
+            cell_commit[i] = it.first->second;
+        }
+    }
+    const size_t ncu = uniq.size();
+    for (size_t i = 0, g = 0; i < N; i++) {
+        while (i >= start[g + 1]) g++;
+        if (cell_indices[i] >= CELLS_PER_EXT_BLOB) invalid[g] = 1;
+    }
+    static const size_t quad_max = (size_t)dev::ab_knob("CKZG_HIP_QUAD_MAX", 8192);
+    CellGroupsPlan plan;
+    build_cell_groups_plan(plan, start, G, cell_commit.data(), ncu, cell_indices, quad_max);
+    const size_t P = plan.P, R = plan.R, total = plan.total, nparts = total / plan.per();
+    const size_t R_ntt = (R + 63) / 64 * 64;   // fr_ntt_batch works on whole tiles of 4096 elements: zero rows behind the last one
+    // One SHA-256 stream per group (eip7594.c:390-482 on the group's slice, its commitments deduplicated within the
+    // group), on the host pool, underneath the copies and the validation below.
+    std::vector<Bytes48> pair_bytes(P);
+    for (size_t j = 0; j < P; j++) pair_bytes[j] = uniq[plan.pair_commit[j]];
+    std::vector<Fr> r(G, Fr::zero());
+    BackgroundFor hashes;
+    hashes.what = "cell group transcript hash jobs";
+    hashes.n = G;
+    hashes.fn = [&](size_t g) {
+        const size_t a = (size_t)start[g], n = (size_t)(start[g + 1] - start[g]);
+        if (n == 0) return;
+        compute_verify_cell_kzg_proof_batch_challenge((fr_t *)&r[g], pair_bytes.data() + plan.pair_off[g],
+                                                      plan.pair_off[g + 1] - plan.pair_off[g], plan.cell_pair.data() + a,
+                                                      cell_indices + a, cells + a, proofs_bytes + a, n);
+    };
+    hashes.start();
+    // the index maps, one upload
+    std::vector<uint32_t> maps;
+    maps.reserve(4 * N + 4 * G + 2 * P + 2 * R + total + 8);
+    auto put = [&maps](const std::vector<uint32_t> &v) {
+        const size_t at = maps.size();
+        maps.insert(maps.end(), v.begin(), v.end());
+        return at;
+    };
+    const size_t m_grp = put(plan.cell_grp), m_col = put(plan.cell_col), m_gd = put(plan.gd), m_pstart = put(plan.pair_start),
+                 m_pmem = put(plan.pair_members), m_pterm = put(plan.pair_term), m_rstart = put(plan.row_start),
+                 m_rorder = put(plan.row_order), m_rcol = put(plan.row_col), m_grows = put(plan.grp_rows), m_src = put(plan.term_src);
+    const size_t npool = N + ncu + l;   // proofs, the chunk's distinct commitments, g1_values_monomial[0..63]
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin((N + ncu) * (48 + 2) + npool * sizeof(G1Affine) + N * BYTES_PER_CELL + (N * l + N + R_ntt * l + G) * sizeof(Fr) + N * 4 +
+                 maps.size() * 4 + total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) +
+                 (2 * G + 1) * 4 + 20 * 256));
+    ArenaTrim trim(ar);
+    ABuf<uint8_t> d_ptb(ar, (N + ncu) * 48), d_st(ar, N + ncu), d_st2(ar, N + ncu), d_cells(ar, N * BYTES_PER_CELL);
+    ABuf<G1Affine> d_pool(ar, npool), d_jobpts(ar, total), d_out(ar, 2 * G);
+    ABuf<Fr> d_cellfr(ar, N * l), d_rp(ar, N), d_rows(ar, R_ntt * l), d_r(ar, G);
+    ABuf<uint32_t> d_bad(ar, N), d_maps(ar, maps.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1);
+    ABuf<G1XYZZ> d_part(ar, nparts);
+    OKM(d_ptb.p && d_st.p && d_st2.p && d_cells.p && d_pool.p && d_jobpts.p && d_out.p && d_cellfr.p && d_rp.p && d_rows.p &&
+        d_r.p && d_bad.p && d_maps.p && d_sc.p && d_off.p && d_part.p);
+    OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, 2 * (N + ncu) + N * 4));
+    uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[0]), *h_st2 = h_st + (N + ncu);
+    uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
+    OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess &&
+        dev::ensure_event(ctx->flags_ev) == hipSuccess);
+    // whatever path leaves this function, both streams must be idle before the arena is reused
+    StreamDrain drain_main{ctx->stream}, drain{ctx->copy_stream};
+    // (all copies from pageable memory first: such a copy returns only when it is done, so it must not queue behind
+    // the validation kernels)
+    OKB(hipMemcpyAsync(d_ptb.p, proofs_bytes, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_ptb.p + N * 48, uniq.data(), ncu * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_cells.p, cells, N * BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_maps.p, maps.data(), maps.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    // decompression here, the subgroup test (~1 ms of dependent doublings) on the second stream, next to everything
+    // below; its flags are ordered by an event of their own (subgroup_ev) and read after the sums, before the pairings.
+    // A point outside the subgroup makes the sums of the groups that use it meaningless, not unsafe: discarded.
+    RC(dev::decompress_g1_batch_device(ctx, d_pool.p, d_st.p, d_ptb.p, N + ncu));
+    OKB(hipMemcpyAsync(h_st, d_st.p, N + ncu, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
+    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
+    RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pool.p, N + ncu, ctx->copy_stream));
+    OKB(hipMemcpyAsync(h_st2, d_st2.p, N + ncu, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
+    OKB(hipMemsetAsync(d_bad.p, 0, N * 4, ctx->stream) == hipSuccess);
+    RC(dev::bytes_to_fr_batch(ctx, d_cellfr.p, d_bad.p, d_cells.p, N * l, (uint32_t)l));
+    OKB(hipMemcpyAsync(h_bad, d_bad.p, N * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
+    // the jobs' points, gathered by index: the commitments and the 64 setup points are shared between groups
+    OKB(hipMemcpyAsync(d_pool.p + N + ncu, ctx->d_mono, l * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
+    RC(dev::group_gather_points_enqueue(ctx, d_jobpts.p, d_pool.p, d_maps.p + m_src, total));
+    OKB(hipMemsetAsync(d_sc.p, 0, total * 32, ctx->stream) == hipSuccess);
+    if (R_ntt > R) OKB(hipMemsetAsync(d_rows.p + R * l, 0, (R_ntt - R) * l * sizeof(Fr), ctx->stream) == hipSuccess);
+    OKB(stage("copies and validation (underneath the transcript hashes)"));
+    hashes.finish();
+    tr.mark("hashes");
+    OKB(hipMemcpyAsync(d_r.p, r.data(), G * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    RC(dev::group_rlc_scalars_enqueue(ctx, d_rp.p, d_sc.p, d_maps.p + m_grp, d_maps.p + m_col, d_maps.p + m_gd, d_r.p,
+                                      d_maps.p + m_pstart, d_maps.p + m_pmem, d_maps.p + m_pterm, N, G, P));
+    OKB(stage("scalars"));
+    // per row: cell data is in bit-reversed order -> DIT inverse NTT(64) gives the interpolation polynomial over the
+    // row's coset; the group's rows are summed with their own coset scaling (eip7594.c:661-752)
+    RC(dev::group_cell_aggregate_device(ctx, d_rows.p, d_cellfr.p, d_rp.p, d_maps.p + m_rstart, d_maps.p + m_rorder, N, R));
+    RC(dev::fr_ntt_batch(ctx, d_rows.p, R_ntt, 6, false, true, true));
+    RC(dev::group_interp_sum_device(ctx, d_sc.p, d_rows.p, d_maps.p + m_grows, d_maps.p + m_rcol, d_maps.p + m_gd, G));
+    OKB(stage("aggregation"));
+    RC(dev::lincomb_multi_device(ctx, d_out.p, d_part.p, d_off.p, d_jobpts.p, d_sc.p, total, plan.part_off.data(), (int)(2 * G),
+                                 plan.quad));
+    std::vector<G1Affine> sums(2 * G);
+    OKB(d_out.down(sums.data(), 2 * G));
+    tr.mark("sums");
+    // the validation flags, folded into per-group status
+    OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
+    for (size_t i = 0; i < N; i++) {
+        const size_t c = N + cell_commit[i];
+        if (h_st[i] || h_st2[i] || h_st[c] || h_st2[c] || h_bad[i]) invalid[plan.cell_grp[i]] = 1;
+    }
+    // e(final_g, [1]_2) * e(-proof_lc_g, [s^64]_2) == 1, one check per valid group, on the host pool
+    std::vector<uint32_t> todo;
+    for (size_t g = 0; g < G; g++) {
+        if (start[g + 1] == start[g])
+            ok[g] = true;
+        else if (invalid[g])
+            status[g] = (uint8_t)C_KZG_BADARGS;
+        else
+            todo.push_back((uint32_t)g);
+    }
+    parallel_for(todo.size(), [&](size_t t) {
+        const size_t g = todo[t];
+        ok[g] = pairing_product_is_one(sums[2 * g], pg->gen, jac_to_affine_fast(jac_neg(jac_from_affine(sums[2 * g + 1]))), pg->s64);
+    });
+    tr.mark("pairings");
+    for (size_t g = 0; g < G; g++) {
+        if (status[g]) return C_KZG_BADARGS;
+    }
+    return C_KZG_OK;
+}
+
+extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                                                const uint64_t *cell_indices, const Cell *cells,
+                                                                const Bytes48 *proofs_bytes, const uint64_t *group_start,
+                                                                uint64_t num_groups, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_groups == 0) return C_KZG_OK;
+        if (!ok || !group_start || group_start[0] != 0) return C_KZG_BADARGS;
+        for (uint64_t g = 0; g < num_groups; g++) {
+            if (group_start[g + 1] < group_start[g]) return C_KZG_BADARGS;
+        }
+        if (group_start[num_groups] != 0 && (!commitments_bytes || !cell_indices || !cells || !proofs_bytes)) return C_KZG_BADARGS;
+        std::vector<uint8_t> own_status;
+        if (!status) {
+            own_status.resize(num_groups);
+            status = own_status.data();
+        }
+        // Whole groups are the unit of splitting: contiguous runs of groups per device, and on a device chunks of at most
+        // CKZG_HIP_CELL_GROUPS_CHUNK_CELLS cells / _CHUNK_GROUPS groups (what one pass keeps in HBM).  A chunk of one group
+        // -- a call of one group, or a group larger than a chunk -- is the single-batch call.
+        return for_each_device_shard(s, num_groups, 16, [&](dev::DeviceCtx *ctx, uint64_t glo, uint64_t ghi) {
+            C_KZG_RET ret = C_KZG_OK;
+            std::vector<uint64_t> start;
+            for (uint64_t g0 = glo; g0 < ghi;) {
+                uint64_t g1 = g0 + 1;
+                while (g1 < ghi && g1 - g0 < CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS &&
+                       group_start[g1 + 1] - group_start[g0] <= CKZG_HIP_CELL_GROUPS_CHUNK_CELLS)
+                    g1++;
+                const uint64_t a = group_start[g0];
+                C_KZG_RET r;
+                if (g1 - g0 == 1) {
+                    r = verify_one_cell_group(ctx, ok + g0, status + g0, commitments_bytes + a, cell_indices + a, cells + a,
+                                              proofs_bytes + a, group_start[g1] - a, s);
+                } else {
+                    start.resize(g1 - g0 + 1);
+                    for (uint64_t g = g0; g <= g1; g++) start[g - g0] = group_start[g] - a;
+                    r = verify_cell_groups_on(ctx, ok + g0, status + g0, commitments_bytes + a, cell_indices + a, cells + a,
+                                              proofs_bytes + a, start.data(), (size_t)(g1 - g0), s);
+                }
+                if (r != C_KZG_OK && r != C_KZG_BADARGS) return r;
+                ret = worse(ret, r);
+                g0 = g1;
+            }
+            return ret;
+        });
     });
 }
 

@@ -534,6 +534,22 @@ int cell_aggregate_device(DeviceCtx *ctx, Fr *d_agg, const Fr *d_cell_fr, const 
                           const uint32_t *d_order, size_t n_cells);
 // interpolation-polynomial coefficients summed over the 128 columns, as canonical MSM scalars
 int interp_sum_device(DeviceCtx *ctx, Fr *d_interp, const Fr *d_cols);
+// The same steps segmented by group (ckzg_hip_verify_cell_kzg_proof_batch_groups; index maps: cell_groups_plan.hpp,
+// whose field names the parameters carry).  All enqueue-only, on ctx->stream.  d_sc: the scalars of every job
+// ([total][8], zeroed by the caller), d_r: the groups' challenges (Montgomery).
+//   d_rp[n] <- r_g^(i - start_g); d_sc <- the same on each cell's proof in B_g, times h_k^64 in A_g, and the
+//   per-(group, commitment) weights on the pairs' terms
+int group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_cell_grp, const uint32_t *d_cell_col,
+                              const uint32_t *d_gd, const Fr *d_r, const uint32_t *d_pair_start, const uint32_t *d_pair_members,
+                              const uint32_t *d_pair_term, size_t n, size_t ngroups, size_t npairs);
+//   rows[t][j] = sum over the cells i of row t (CSR: row_start[nrows + 1], row_order[n]) of rp[i] * cell_fr[i][j]
+int group_cell_aggregate_device(DeviceCtx *ctx, Fr *d_rows, const Fr *d_cell_fr, const Fr *d_rp, const uint32_t *d_row_start,
+                                const uint32_t *d_row_order, size_t n_cells, size_t nrows);
+//   d_sc <- minus the interpolation coefficients of each group, summed over its rows (after the rows' inverse NTTs)
+int group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, const uint32_t *d_grp_rows, const uint32_t *d_row_col,
+                            const uint32_t *d_gd, size_t ngroups);
+//   d_out[t] <- d_pool[term_src[t]], infinity for a padding term
+int group_gather_points_enqueue(DeviceCtx *ctx, G1Affine *d_out, const G1Affine *d_pool, const uint32_t *d_term_src, size_t total);
 int fr_mul_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n, size_t period);
 int fr_div_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n);
 // pairing.hip: verify_kzg_proof for n independent items (ckzg_api2.hip: verify_point_proofs_on).  Enqueue-only, on

@@ -189,6 +189,30 @@ C_KZG_RET ckzg_hip_verify_kzg_proof_batch(bool *ok, uint8_t *status, const Bytes
                                           const Bytes32 *zs_bytes, const Bytes32 *ys_bytes,
                                           const Bytes48 *proofs_bytes, uint64_t n, const KZGSettings *s);
 
+/* verify_cell_kzg_proof_batch (src/eip7594/eip7594.c:825-974) over num_groups independent batches in one call, one
+ * verdict per group -- the shape of a PeerDAS node, which verifies every column sidecar of a block on its own to know
+ * which one is bad.  The four input arrays are flat, group_start[num_groups] entries long; group g is the slice
+ * [group_start[g], group_start[g + 1]).  group_start has num_groups + 1 entries, starts at 0 and does not decrease.
+ * For every g, (status[g], ok[g]) is exactly (return value, *ok) of
+ *   verify_cell_kzg_proof_batch(&ok, commitments + a, cell_indices + a, cells + a, proofs + a, b - a, s)
+ * with a = group_start[g], b = group_start[g + 1]: an empty group is true with status 0; a cell index >= 128, a
+ * non-canonical field element in a cell, or a commitment or proof that is not a valid G1 point gives that group
+ * status 1 (C_KZG_BADARGS) and ok = false and says nothing about the other groups, whose verdicts are still computed
+ * and written.  Every group has the reference's challenge for its slice (commitments deduplicated within the group,
+ * its own transcript); no randomness is shared between groups, and every valid group gets its own pairing check.
+ * Returns C_KZG_BADARGS if any group is invalid, or if group_start is malformed (first entry not 0, or decreasing:
+ * nothing is written then); C_KZG_OK otherwise; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  status may be
+ * NULL; num_groups == 0 is C_KZG_OK and writes nothing.
+ * Whole groups are the unit of work: several devices take contiguous runs of groups, and on a device the groups are
+ * processed in chunks of at most CKZG_HIP_CELL_GROUPS_CHUNK_CELLS cells and CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS groups;
+ * a group is never cut.  A group larger than a chunk, and a call of one group, go through the single-batch path. */
+#define CKZG_HIP_CELL_GROUPS_CHUNK_CELLS 16384
+#define CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS 8192
+C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                                      const uint64_t *cell_indices, const Cell *cells,
+                                                      const Bytes48 *proofs_bytes, const uint64_t *group_start,
+                                                      uint64_t num_groups, const KZGSettings *s);
+
 /* verify_blob_kzg_proof_batch (src/eip4844/eip4844.c:775-844) with blobs, commitments and proofs resident in HBM
  * (device pointers on one GPU: n Blob, n Bytes48, n Bytes48).  Point validation, bytes -> field elements, the
  * Fiat-Shamir challenges (SHA-256 of every blob, on the GPU), the evaluations and the three random-linear-combination

@@ -1,0 +1,188 @@
+"""ckzg_hip_verify_cell_kzg_proof_batch_groups without a GPU: the symbol is declared and exported, a settings struct
+without GPU state gives C_KZG_ERROR (no CPU fallback), the binding checks its arguments, and the segmented scalar,
+aggregation and interpolation arithmetic of verify.hip -- replayed on the host over the index maps the product builds
+(csrc/cell_groups_plan.hpp, through libhost_shim.so) -- gives, group by group, the two sums whose pairing check is the
+oracle's verdict for that group."""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT, SHIM_SO
+from kzg_ctypes import HIP_SO, Kzg, KzgError, KZGSettings, TRUSTED_SETUP
+from test_abi_exports import declared_symbols
+
+R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+NAME = "ckzg_hip_verify_cell_kzg_proof_batch_groups"
+
+
+def test_symbol_declared_and_exported():
+    assert NAME in declared_symbols()
+    assert "    %s;\n" % NAME in open(os.path.join(ROOT, "c-kzg-4844_amd", "exports.map")).read()
+    assert hasattr(C.CDLL(HIP_SO), NAME)
+
+
+def test_zeroed_settings_give_error_and_no_cpu_fallback():
+    f = getattr(C.CDLL(HIP_SO), NAME)
+    f.restype = C.c_int
+    s = KZGSettings()
+    ok, st = (C.c_bool * 2)(), (C.c_uint8 * 2)()
+    start = (C.c_uint64 * 3)(0, 1, 2)
+    idx = (C.c_uint64 * 2)(0, 1)
+    assert f(ok, st, bytes(96), idx, bytes(4096), bytes(96), start, C.c_uint64(2), C.byref(s)) == 2
+    assert f(None, None, None, None, None, None, None, C.c_uint64(0), C.byref(s)) == 2
+
+
+def test_binding_checks_its_arguments():
+    api = Kzg.__new__(Kzg)   # no library: every check below fails before a call is made
+    cell, p48 = bytes(2048), bytes(48)
+    for groups in ([([p48], [0], [cell])],                      # not four lists
+                   [([p48], [0, 1], [cell], [p48])],            # list lengths
+                   [([p48], [0], [cell[:-1]], [p48])],          # a short cell
+                   [([p48[:-1]], [0], [cell], [p48])],          # a short commitment
+                   [([p48], [0], [cell], [p48 + b"0"])],        # a long proof
+                   [([p48], [-1], [cell], [p48])]):             # an index that is no uint64
+        with pytest.raises(KzgError):
+            api.verify_cell_kzg_proof_batch_groups(groups)
+
+
+# ---- the replay ----
+
+@pytest.fixture(scope="module")
+def h():
+    if not os.path.exists(SHIM_SO):
+        subprocess.check_call(["make", "-C", os.path.join(ROOT, "c-kzg-4844_amd"), "csrc/libhost_shim.so"])
+    lib = C.CDLL(SHIM_SO)
+    assert hasattr(lib, "hs_cell_groups_replay")
+    lib.hs_cell_groups_replay.restype = C.c_long
+    return lib
+
+
+def _limbs(v):
+    return (C.c_uint32 * 8)(*[(v >> (32 * i)) & 0xffffffff for i in range(8)])
+
+
+def _g1(h, b48):
+    """compressed point -> Jacobian (Z = 1), in the shim's representation"""
+    aff = C.create_string_buffer(96)
+    assert h.hs_g1_uncompress(aff, b48) == 0
+    if aff.raw == bytes(96):
+        return bytes(144)
+    gen = C.create_string_buffer(144)
+    h.hs_g1_generator(gen)
+    return aff.raw + gen.raw[96:]
+
+
+def _g2(h, b96):
+    aff = C.create_string_buffer(192)
+    assert h.hs_g2_uncompress(aff, b96) == 0
+    gen = C.create_string_buffer(288)
+    h.hs_g2_generator(gen)
+    return aff.raw + gen.raw[192:]
+
+
+def _lincomb(h, pts, scalars):
+    acc = bytes(144)
+    for p, k in zip(pts, scalars):
+        if k == 0 or p == bytes(144):
+            continue
+        t = C.create_string_buffer(144)
+        h.hs_g1_mul(t, p, _limbs(k), 255)
+        out = C.create_string_buffer(144)
+        h.hs_g1_add_jac(out, acc, t.raw)
+        acc = out.raw
+    return acc
+
+
+def _material(oracle):
+    out = []
+    for b in range(2):
+        blob = b"".join(b"\x00" + hashlib.sha256(b"cellgroups%d/%d" % (b, j)).digest()[:31] for j in range(4096))
+        cells, proofs = oracle.compute_cells_and_kzg_proofs(blob)
+        out.append((oracle.blob_to_kzg_commitment(blob), cells, proofs))
+    return out
+
+
+def test_host_replay_of_the_segmented_arithmetic_matches_the_oracle(h, oracle):
+    mat = _material(oracle)
+
+    def cell(b, col):
+        return (mat[b][0], col, mat[b][1][col], mat[b][2][col])
+
+    # shared and unshared columns, two commitments in a group, a repeated (column, blob) pair, an empty group, a
+    # wrong proof, a group of one
+    groups = [[cell(0, 3), cell(0, 5), cell(1, 3)],
+              [],
+              [cell(1, 5), cell(1, 7), cell(1, 7), cell(0, 127)],
+              [cell(0, 9), (mat[1][0], 9, mat[1][1][9], mat[0][2][9]), cell(1, 10)],
+              [cell(0, 100)]]
+    want = [oracle.verify_cell_kzg_proof_batch(*[[t[k] for t in g] for k in range(4)]) for g in groups]
+    assert want == [True, True, True, False, True]
+    flat = [t for g in groups for t in g]
+    n, G = len(flat), len(groups)
+    start = [0]
+    for g in groups:
+        start.append(start[-1] + len(g))
+    uniq = []
+    for t in flat:
+        if t[0] not in uniq:
+            uniq.append(t[0])
+    cell_commit = [uniq.index(t[0]) for t in flat]
+    # every group's challenge: the oracle's, over the slice with its commitments deduplicated within the group
+    rs = []
+    for g in groups:
+        if not g:
+            rs.append(0)
+            continue
+        loc = []
+        for t in g:
+            if t[0] not in loc:
+                loc.append(t[0])
+        rs.append(int.from_bytes(oracle.compute_verify_cell_kzg_proof_batch_challenge(
+            loc, [loc.index(t[0]) for t in g], [t[1] for t in g], [t[2] for t in g], [t[3] for t in g]), "big"))
+    w = pow(7, (R - 1) // 8192, R)
+    roots, x = [], 1
+    for _ in range(8193):
+        roots.append(x)
+        x = x * w % R
+    le = lambda vals: b"".join(v.to_bytes(32, "little") for v in vals)
+    cells_raw = le(int.from_bytes(t[2][32 * j:32 * j + 32], "big") for t in flat for j in range(64))
+    lines = open(TRUSTED_SETUP).read().split()
+    assert lines[0] == "4096" and lines[1] == "65"
+    g2 = lines[2 + 4096:2 + 4096 + 65]
+    mono = lines[2 + 4096 + 65:2 + 4096 + 65 + 64]
+    pool = [_g1(h, t[3]) for t in flat] + [_g1(h, c) for c in uniq] + [_g1(h, bytes.fromhex(m)) for m in mono]
+    g2_gen, g2_s64 = _g2(h, bytes.fromhex(g2[0])), _g2(h, bytes.fromhex(g2[64]))
+    for quad_max in (8192, 0):   # both paddings of the jobs: 8 terms and 32
+        cap = 4096
+        sc = (C.c_uint32 * (cap * 8))()
+        src = (C.c_uint32 * cap)()
+        part_off = (C.c_uint32 * (2 * G + 1))()
+        info = (C.c_uint32 * 4)()
+        total = h.hs_cell_groups_replay(sc, src, part_off, info, C.c_size_t(cap), (C.c_uint64 * (G + 1))(*start), C.c_size_t(G),
+                                        (C.c_uint32 * n)(*cell_commit), C.c_size_t(len(uniq)),
+                                        (C.c_uint64 * n)(*[t[1] for t in flat]), cells_raw, le(rs), le(roots),
+                                        C.c_size_t(quad_max))
+        per = 8 if quad_max else 32
+        assert total > 0 and total % 64 == 0 and info[0] == total and info[1] == (1 if quad_max else 0)
+        # pairs: (0: c0, c1) (2: c1, c0) (3: c0, c1) (4: c0); rows: 2 + 3 + 2 + 1
+        assert info[2] == 7 and info[3] == 8
+        scal = [sum(sc[8 * t + i] << (32 * i) for i in range(8)) for t in range(total)]
+        got = []
+        for g in range(G):
+            sums = []
+            for job in (2 * g, 2 * g + 1):
+                lo, hi = part_off[job] * per, part_off[job + 1] * per
+                assert all(src[t] < len(pool) or (src[t] == 0xffffffff and scal[t] == 0) for t in range(lo, hi))
+                terms = [t for t in range(lo, hi) if src[t] != 0xffffffff]
+                sums.append(_lincomb(h, [pool[src[t]] for t in terms], [scal[t] for t in terms]))
+            if not groups[g]:
+                assert sums == [bytes(144)] * 2
+                got.append(True)
+            else:
+                assert len([t for t in range(part_off[2 * g] * per, part_off[2 * g + 1] * per) if src[t] != 0xffffffff]) == \
+                    len({t[0] for t in groups[g]}) + len(groups[g]) + 64
+                got.append(h.hs_pairings_verify(sums[0], g2_gen, sums[1], g2_s64) == 1)
+        assert got == want, (quad_max, got)
