@@ -226,6 +226,43 @@ class Kzg:
                   for i in range(CELLS_PER_EXT_BLOB)] for b in range(nb)] if want_proofs else None
         return out_c, out_p
 
+    def recover_cells_and_kzg_proofs_rows(self, rows, want_cells=True, want_proofs=True):
+        """ckzg_hip_recover_cells_and_kzg_proofs_rows: one recover_cells_and_kzg_proofs per row, in one call; the rows
+        may hold different cells.  rows is a list of (cell_indices, cells) tuples.  Returns (cells_per_row,
+        proofs_per_row, status): status[r] is the row's C_KZG_RET (1 = C_KZG_BADARGS) and the entries of an invalid row
+        are None, as is a whole list that was not asked for."""
+        _check(want_cells or want_proofs, "no output requested")
+        nr = len(rows)
+        start, flat_idx, flat_cells = [0], [], []
+        for row in rows:
+            _check(len(row) == 2, "a row is (cell_indices, cells)")
+            cell_indices, cells = row
+            _check(len(cell_indices) == len(cells), "list lengths")
+            for c in cells:
+                _check(len(c) == BYTES_PER_CELL, "cell")
+            for i in cell_indices:
+                _check(isinstance(i, int) and 0 <= i < 1 << 64, "cell index")
+            flat_idx.extend(cell_indices)
+            flat_cells.extend(cells)
+            start.append(start[-1] + len(cells))
+        cs, ps = BYTES_PER_CELL * CELLS_PER_EXT_BLOB, 48 * CELLS_PER_EXT_BLOB
+        rc = C.create_string_buffer(max(nr, 1) * cs) if want_cells else None
+        rp = C.create_string_buffer(max(nr, 1) * ps) if want_proofs else None
+        st = (C.c_uint8 * max(nr, 1))()
+        ret = self._fn("ckzg_hip_recover_cells_and_kzg_proofs_rows")(
+            rc, rp, st, (C.c_uint64 * max(start[-1], 1))(*flat_idx), b"".join(flat_cells),
+            (C.c_uint64 * (nr + 1))(*start), C.c_uint64(nr), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_recover_cells_and_kzg_proofs_rows -> C_KZG_RET %d" % ret)
+        status = [int(v) for v in st[:nr]]
+        craw = rc.raw if want_cells else b""
+        praw = rp.raw if want_proofs else b""
+        out_c = [None if status[r] else [craw[r * cs + i * BYTES_PER_CELL: r * cs + (i + 1) * BYTES_PER_CELL]
+                                         for i in range(CELLS_PER_EXT_BLOB)] for r in range(nr)] if want_cells else None
+        out_p = [None if status[r] else [praw[r * ps + i * 48: r * ps + (i + 1) * 48]
+                                         for i in range(CELLS_PER_EXT_BLOB)] for r in range(nr)] if want_proofs else None
+        return out_c, out_p, status
+
     def verify_cell_kzg_proof_batch(self, commitments, cell_indices, cells, proofs):
         n = len(cells)
         _check(len(commitments) == n and len(cell_indices) == n and len(proofs) == n, "list lengths")

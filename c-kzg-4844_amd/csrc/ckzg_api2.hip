@@ -13,6 +13,7 @@
 #include <unordered_map>
 #include "cell_groups_plan.hpp"
 #include "combiner.hpp"
+#include "recover_rows_plan.hpp"
 
 using namespace ckzg;
 using namespace ckzg::host;
@@ -1624,6 +1625,151 @@ extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_batch(Cell *recovered
                                     recovered_proofs ? recovered_proofs + lo * CELLS_PER_EXT_BLOB : nullptr,
                                     status ? status + lo : nullptr, cell_indices, cells + lo * num_cells, num_cells,
                                     hi - lo, s);
+        });
+    });
+}
+
+// recover_batch_on for rows that hold different cells: caller rows [lo, hi) of the call on one device.  The plan
+// (recover_rows_plan.hpp) names the valid rows, their distinct sets and every cell's place; per chunk the GPU makes the
+// per-cell values of Z and 1 / Z for each distinct set (recover_set_factors.hpp) and all rows of the chunk, whatever
+// they hold, go through the five transforms of recover_cells (recovery.c:200-365) and one FK20 batch together.  No
+// field arithmetic on the host.  A chunk whose rows all hold 128 cells skips the transforms like the uniform call.
+static C_KZG_RET recover_rows_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs, uint8_t *status,
+                                 const uint64_t *cell_indices, const Cell *cells, const uint64_t *row_start, uint64_t lo,
+                                 uint64_t hi) {
+    const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
+    const size_t CH = 512;   // as recover_batch_on
+    RecoverRowsPlan plan;
+    build_recover_rows_plan(plan, cell_indices, row_start + lo, hi - lo, CH);
+    C_KZG_RET result = plan.any_invalid ? C_KZG_BADARGS : C_KZG_OK;
+    if (status) {
+        for (uint64_t r = lo; r < hi; r++) status[r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
+    }
+    if (plan.chunks.empty()) return result;
+    const size_t m = plan.max_rows, mc = plan.max_cells, ms = plan.max_sets;
+    const bool piped = m > 8;
+    const int nbuf = piped ? 2 : 1;
+    std::vector<uint32_t> bad(m), meta;
+    Arena &ar = ctx->api_arena;
+    // image(s) + Fr + flags + set ids per row; input + target per cell; mask + 2 x 128 factors per set; proofs
+    OKM(ar.begin(m * (nbuf * n * 32 + n * sizeof(Fr) + 4 + 4) + mc * (BYTES_PER_CELL + 4) +
+                 ms * (16 + 2 * CELLS_PER_EXT_BLOB * sizeof(Fr)) +
+                 (recovered_proofs ? m * (nbuf * CELLS_PER_EXT_BLOB * 48 + FIELD_ELEMENTS_PER_BLOB * sizeof(Fr)) : 0) + 4096));
+    ArenaTrim trim(ar);
+    ABuf<uint8_t> d_img0(ar, m * n * 32), d_img1(ar, piped ? m * n * 32 : 1), d_in(ar, mc * BYTES_PER_CELL);
+    ABuf<uint8_t> d_pr0(ar, recovered_proofs ? m * CELLS_PER_EXT_BLOB * 48 : 1);
+    ABuf<uint8_t> d_pr1(ar, recovered_proofs && piped ? m * CELLS_PER_EXT_BLOB * 48 : 1);
+    ABuf<Fr> d_e(ar, m * n), d_poly(ar, recovered_proofs ? m * FIELD_ELEMENTS_PER_BLOB : 1);
+    ABuf<Fr> d_zdom(ar, ms * CELLS_PER_EXT_BLOB), d_zinv(ar, ms * CELLS_PER_EXT_BLOB);
+    ABuf<uint32_t> d_bad(ar, m), d_meta(ar, m + mc + 4 * ms);   // meta: row_set [k] | cell_dst [cells] | set_mask [4 sets]
+    OKM(d_img0.p && d_img1.p && d_in.p && d_pr0.p && d_pr1.p && d_e.p && d_poly.p && d_zdom.p && d_zinv.p && d_bad.p &&
+        d_meta.p);
+    uint8_t *img_buf[2] = {d_img0.p, piped ? d_img1.p : d_img0.p}, *pr_buf[2] = {d_pr0.p, piped ? d_pr1.p : d_pr0.p};
+    // the pipe's page-locked staging, taken here so that running out of it is C_KZG_MALLOC like every other allocation
+    if (piped) OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, OutPipe::PIECE));
+    OutPipe pipe(ctx);
+    struct Drain {  // nothing may still read the arena or the plan when this function leaves, on any path
+        dev::DeviceCtx *c;
+        OutPipe &p;
+        ~Drain() {
+            (void)p.finish();
+            (void)dev::sync_stream(c->stream);
+        }
+    } drain{ctx, pipe};
+    std::vector<size_t> mark;
+    // the outputs of a chunk go back run by run: device rows are packed, caller rows keep the gaps of invalid rows
+    auto give_back = [&](const RecoverRowsChunk &ch, const uint8_t *d_src, uint8_t *h_dst, size_t per_row) -> bool {
+        for (const RecoverRowsRun &run : ch.runs) {
+            const uint8_t *src = d_src + run.dev_row * per_row;
+            uint8_t *dst = h_dst + (size_t)(lo + run.caller_row) * per_row;
+            if (piped) {
+                if (!pipe.push(src, dst, run.rows * per_row)) return false;
+            } else if (hipMemcpy(dst, src, run.rows * per_row, hipMemcpyDeviceToHost) != hipSuccess) {
+                return false;
+            }
+        }
+        return true;
+    };
+    OKB(hipEventRecord(ctx->ev[1], ctx->stream) == hipSuccess);
+    for (size_t chunk = 0; chunk < plan.chunks.size(); chunk++) {
+        const RecoverRowsChunk &ch = plan.chunks[chunk];
+        const size_t k = ch.rows(), nc = ch.cells(), ns = ch.sets();
+        uint8_t *d_img = img_buf[chunk & 1], *d_proofs = pr_buf[chunk & 1];
+        const uint32_t *d_row_set = d_meta.p, *d_cell_dst = d_meta.p + k, *d_set_mask = d_meta.p + k + nc;
+        if (piped && chunk >= 2) pipe.wait_for(mark[chunk - 2]);
+        meta.clear();
+        meta.insert(meta.end(), ch.row_set.begin(), ch.row_set.end());
+        meta.insert(meta.end(), ch.cell_dst.begin(), ch.cell_dst.end());
+        meta.insert(meta.end(), ch.set_mask.begin(), ch.set_mask.end());
+        // (the stream was drained at the end of the chunk before: nothing reads d_meta or `meta` any more)
+        OKB(hipMemcpyAsync(d_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        for (const RecoverRowsRun &run : ch.runs) {
+            OKB(hipMemcpyAsync(d_in.p + (size_t)run.dev_cell * BYTES_PER_CELL, cells + run.src_cell,
+                               (size_t)run.cells * BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        }
+        OKB(hipMemsetAsync(d_img, 0, k * n * 32, ctx->stream) == hipSuccess);
+        OKB(hipMemsetAsync(d_bad.p, 0, k * 4, ctx->stream) == hipSuccess);
+        if (!ch.all_full) RC(dev::recover_set_factors_enqueue(ctx, d_zdom.p, d_zinv.p, d_set_mask, ns));
+        RC(dev::scatter_cells_rows_enqueue(ctx, d_img, d_in.p, d_cell_dst, nc));
+        RC(dev::bytes_to_fr_batch(ctx, d_e.p, d_bad.p, d_img, k * n, (uint32_t)n));
+        if (!ch.all_full) {
+            RC(dev::fr_mul_cell_factor_enqueue(ctx, d_e.p, d_zdom.p, d_row_set, k));   // (E * Z)(w^i)
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));               // -> coefficients
+            RC(dev::fr_mul_inplace_device(ctx, d_e.p, ctx->d_shift, k * n, n));        // coset_fft: scale by 7^i ...
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));              // ... and transform
+            RC(dev::fr_mul_cell_factor_enqueue(ctx, d_e.p, d_zinv.p, d_row_set, k));   // recovery.c:322-328
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));               // coset_ifft ...
+            RC(dev::fr_mul_inplace_device(ctx, d_e.p, ctx->d_unshift, k * n, n));      // ... unscale by 7^-i
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));              // evaluations, cell order
+            if (recovered_cells) RC(dev::fr_to_bytes_batch(ctx, d_img, d_e.p, k * n));
+        }
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+        OKB(d_bad.down(bad.data(), k));
+        for (size_t i = 0; i < k; i++) {
+            if (!bad[i]) continue;   // a field element >= r: the row's output is unspecified
+            if (status) status[lo + ch.row_caller[i]] = (uint8_t)C_KZG_BADARGS;
+            result = C_KZG_BADARGS;
+        }
+        if (recovered_cells) OKB(give_back(ch, d_img, reinterpret_cast<uint8_t *>(recovered_cells), n * 32));
+        if (recovered_proofs) {
+            // cell order is bit-reversed evaluation order: DIT inverse gives the coefficients
+            // (poly_lagrange_to_monomial over 8192 points, eip7594.c:270); FK20 reads the low 4096
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));
+            OKB(hipMemcpy2DAsync(d_poly.p, FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), d_e.p, n * sizeof(Fr),
+                                 FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), k, hipMemcpyDeviceToDevice,
+                                 ctx->stream) == hipSuccess);
+            RC(dev::fk20_proofs_device(ctx, d_proofs, d_poly.p, k));
+            if (!piped) OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+            OKB(give_back(ch, d_proofs, reinterpret_cast<uint8_t *>(recovered_proofs), CELLS_PER_EXT_BLOB * 48));
+        }
+        mark.push_back(pipe.pushed_count());
+    }
+    OKB(hipEventRecord(ctx->ev[4], ctx->stream) == hipSuccess);
+    if (pipe.finish() != C_KZG_OK) return C_KZG_ERROR;
+    OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+    {   // ckzg_hip_last_kernel_ms: as recover_batch_on
+        float ms_dev;
+        if (hipEventElapsedTime(&ms_dev, ctx->ev[1], ctx->ev[4]) == hipSuccess) ctx->last_ms[3] = ms_dev;
+        if (recovered_proofs) dev::fk20_collect_times(ctx);
+        (void)hipGetLastError();
+    }
+    return result;
+}
+
+extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs,
+                                                                uint8_t *status, const uint64_t *cell_indices,
+                                                                const Cell *cells, const uint64_t *row_start,
+                                                                uint64_t num_rows, const KZGSettings *s) {
+    // eip7594.c:177-304 once per row [row_start[r], row_start[r + 1]) of the flat arrays
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_rows == 0) return C_KZG_OK;
+        if (recovered_cells == NULL && recovered_proofs == NULL) return C_KZG_BADARGS;
+        if (!recover_rows_start_ok(row_start, num_rows)) return C_KZG_BADARGS;
+        if (row_start[num_rows] != 0 && (cell_indices == NULL || cells == NULL)) return C_KZG_BADARGS;
+        // whole rows are the unit of splitting: contiguous runs of rows per device, chunks of rows on a device
+        return for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return recover_rows_on(ctx, recovered_cells, recovered_proofs, status, cell_indices, cells, row_start, lo, hi);
         });
     });
 }

@@ -552,6 +552,15 @@ int group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, co
 int group_gather_points_enqueue(DeviceCtx *ctx, G1Affine *d_out, const G1Affine *d_pool, const uint32_t *d_term_src, size_t total);
 int fr_mul_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n, size_t period);
 int fr_div_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n);
+// The rows form of recovery (ckzg_hip_recover_cells_and_kzg_proofs_rows; index maps: recover_rows_plan.hpp).  All
+// enqueue-only, on ctx->stream.
+//   d_z_domain[s][128], d_z_coset_inv[s][128] <- Z over the domain and 1 / Z over the coset of set s, per cell
+int recover_set_factors_enqueue(DeviceCtx *ctx, Fr *d_z_domain, Fr *d_z_coset_inv, const uint32_t *d_set_mask, size_t nsets);
+//   cell i (2048 B) -> image[cell_dst[i]] (cell_dst = device row * 128 + column; zero-filled by the caller)
+int scatter_cells_rows_enqueue(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *d_cells, const uint32_t *d_cell_dst,
+                               size_t ncells);
+//   a[row][p] *= f[row_set[row]][p / 64] over nrows rows of 8192
+int fr_mul_cell_factor_enqueue(DeviceCtx *ctx, Fr *d_a, const Fr *d_f, const uint32_t *d_row_set, size_t nrows);
 // pairing.hip: verify_kzg_proof for n independent items (ckzg_api2.hip: verify_point_proofs_on).  Enqueue-only, on
 // ctx->stream.  d_pts: commitments [0, n), proofs [n, 2n), decompressed; d_st_dec / d_st_sub: their 2n flags from
 // decompress_g1_batch_device / subgroup_g1_batch_device; d_z32 / d_y32: n x 32 big-endian bytes.  Writes the check's

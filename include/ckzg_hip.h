@@ -239,6 +239,26 @@ C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_batch(Cell *recovered_cells, KZG
                                                       const Cell *cells, uint64_t num_cells,
                                                       uint64_t num_blobs, const KZGSettings *s);
 
+/* The same for rows that hold DIFFERENT cells (a block whose rows arrived by different roads: whole blobs from the
+ * mempool, 64-odd columns, a few extra cells, a column dropped for one row only): one call, one status per row.
+ * cell_indices and cells are flat, row_start has num_rows + 1 entries, starts at 0 and does not decrease, and row r is
+ * the slice [row_start[r], row_start[r + 1]).  Outputs are [num_rows][128]; either may be NULL, not both.  For every
+ * r, status[r] (optional) and the row's outputs are the return value and the outputs of
+ *     recover_cells_and_kzg_proofs(cells_out, proofs_out, cell_indices + a, cells + a, b - a, s)
+ * with a = row_start[r], b = row_start[r + 1]:
+ *   - a row with fewer than 64 or more than 128 cells, an index >= 128 or indices not strictly ascending has status
+ *     C_KZG_BADARGS; its output rows are not written, it costs no device work and the other rows are recovered;
+ *   - a row with a non-canonical field element has status C_KZG_BADARGS and unspecified output;
+ *   - a row with all 128 cells returns its cells unchanged, and their proofs.
+ * Returns C_KZG_BADARGS if any row is invalid, or if row_start is malformed or both outputs are NULL (nothing is
+ * written then); C_KZG_OK otherwise (also for num_rows == 0); C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.
+ * The distinct sets of cells of the call are found on the host (a hash map over 128-bit masks); their vanishing
+ * polynomials are evaluated per cell on the GPU and all rows share the transforms and one FK20 batch. */
+C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs,
+                                                     uint8_t *status, const uint64_t *cell_indices,
+                                                     const Cell *cells, const uint64_t *row_start,
+                                                     uint64_t num_rows, const KZGSettings *s);
+
 /* g1_lincomb_fast (src/common/lincomb.c:65-123) on the GPU: out = sum_i coeffs[i] * p[i] over `len` points in
  * the reference's in-memory forms (g1_t Jacobian, fr_t Montgomery); the empty sum is the identity.  The
  * library's own verify_*_batch paths call the same kernels on points they have already validated; here every
