@@ -173,6 +173,34 @@ class Kzg:
                    b"".join(commitments), b"".join(proofs), C.c_uint64(n), self.sp)
         return ok.value
 
+    def verify_blob_kzg_proof_batch_groups(self, groups):
+        """ckzg_hip_verify_blob_kzg_proof_batch_groups: one verify_blob_kzg_proof_batch per group, in one call.  groups
+        is a list of (blobs, commitments, proofs) tuples.  Returns (ok, status): ok[g] is the group's verdict and
+        status[g] its C_KZG_RET (1 = C_KZG_BADARGS: invalid point or field element)."""
+        g = len(groups)
+        start = [0]
+        flat = ([], [], [])
+        for grp in groups:
+            _check(len(grp) == 3, "a group is (blobs, commitments, proofs)")
+            blobs, commitments, proofs = grp
+            n = len(blobs)
+            _check(len(commitments) == n and len(proofs) == n, "list lengths")
+            for b in blobs:
+                _check(len(b) == BYTES_PER_BLOB, "blob")
+            for c in list(commitments) + list(proofs):
+                _check(len(c) == 48, "commitment/proof")
+            for dst, src in zip(flat, grp):
+                dst.extend(src)
+            start.append(start[-1] + n)
+        ok = (C.c_bool * max(g, 1))()
+        st = (C.c_uint8 * max(g, 1))()
+        ret = self._fn("ckzg_hip_verify_blob_kzg_proof_batch_groups")(
+            ok, st, b"".join(flat[0]), b"".join(flat[1]), b"".join(flat[2]), (C.c_uint64 * (g + 1))(*start), C.c_uint64(g),
+            self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_verify_blob_kzg_proof_batch_groups -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:g]], [int(v) for v in st[:g]]
+
     # ---- EIP-7594 (src/eip7594/eip7594.h:35-57) ----
     def compute_cells_and_kzg_proofs(self, blob, want_cells=True, want_proofs=True):
         _check(len(blob) == BYTES_PER_BLOB, "blob")

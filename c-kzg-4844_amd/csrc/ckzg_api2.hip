@@ -11,6 +11,7 @@
 #include <optional>
 #include <string_view>
 #include <unordered_map>
+#include "blob_groups_plan.hpp"
 #include "cell_groups_plan.hpp"
 #include "combiner.hpp"
 #include "recover_rows_plan.hpp"
@@ -2337,6 +2338,231 @@ extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8
                     for (uint64_t g = g0; g <= g1; g++) start[g - g0] = group_start[g] - a;
                     r = verify_cell_groups_on(ctx, ok + g0, status + g0, commitments_bytes + a, cell_indices + a, cells + a,
                                               proofs_bytes + a, start.data(), (size_t)(g1 - g0), s);
+                }
+                if (r != C_KZG_OK && r != C_KZG_BADARGS) return r;
+                ret = worse(ret, r);
+                g0 = g1;
+            }
+            return ret;
+        });
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// ckzg_hip_verify_blob_kzg_proof_batch_groups: many blob batches in one call, one verdict per group
+// ------------------------------------------------------------------------------------------
+
+// One group through the single-batch path: (status, ok) = (return value, *ok) of verify_blob_kzg_proof_batch on it
+static C_KZG_RET verify_one_blob_group(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Blob *blobs, const Bytes48 *cb,
+                                       const Bytes48 *pb, uint64_t n, const KZGSettings *s) {
+    *ok = false;
+    *status = (uint8_t)C_KZG_OK;
+    if (n == 0) {
+        *ok = true;
+        return C_KZG_OK;
+    }
+    bool res = false;
+    C_KZG_RET r = verify_blobs_core(&res, blobs, cb, pb, n, s, ctx);
+    if (r == C_KZG_OK) *ok = res;
+    if (r == C_KZG_BADARGS) *status = (uint8_t)C_KZG_BADARGS;
+    return r;
+}
+
+// G groups over start[G] blobs (start[0] = 0) on one device, as one chunk.  Everything but the batch challenge is per
+// blob already -- point validation, the challenges z_i, the evaluations y_i -- and runs over all N blobs as in one
+// batch; then every group of two or more blobs gets the reference's challenge for its own slice (eip4844.c:597-680),
+// hashed on the host pool, and the segmented kernels of verify.hip make every group's scalars where z, y and the
+// powers already are (only the G challenges cross PCIe) for the two sums of every group --
+// A_g = sum r^i C_i + sum r^i z_i proof_i - [sum r^i y_i] G and B_g = sum r^i proof_i -- in ONE pass of the ladder
+// kernels.  The 2 G points come back and every valid group gets its own two-pairing check on the host pool.
+// Validation flags are folded into per-group status: an invalid point or blob marks its own group only.
+// Plain streams only: the compute-unit partition of the single-batch path stays out of this call.
+static C_KZG_RET verify_blob_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Blob *blobs, const Bytes48 *cb,
+                                       const Bytes48 *pb, const uint64_t *start, size_t G, const KZGSettings *s) {
+    const size_t N = (size_t)start[G];
+    for (size_t g = 0; g < G; g++) {
+        ok[g] = false;
+        status[g] = (uint8_t)C_KZG_OK;
+    }
+    if (N == 0) {
+        for (size_t g = 0; g < G; g++) ok[g] = true;
+        return C_KZG_OK;
+    }
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    Trace tr("verify_blob_groups");
+    auto stage = [&](const char *name) -> bool {   // (a traced call waits after every stage, so that the marks are the stages' times)
+        if (tr.on && dev::sync_stream(ctx->stream) != hipSuccess) return false;
+        tr.mark(name);
+        return true;
+    };
+    static const size_t quad_max = (size_t)dev::ab_knob("CKZG_HIP_QUAD_MAX", 8192);
+    BlobGroupsPlan plan;
+    build_blob_groups_plan(plan, start, G, quad_max);
+    const size_t total = plan.total, nparts = total / plan.per();
+    // the index maps, one upload
+    std::vector<uint32_t> maps;
+    maps.reserve(N + 3 * G + 1 + total);
+    auto put = [&maps](const std::vector<uint32_t> &v) {
+        const size_t at = maps.size();
+        maps.insert(maps.end(), v.begin(), v.end());
+        return at;
+    };
+    const size_t m_grp = put(plan.blob_grp), m_gd = put(plan.gd), m_src = put(plan.term_src);
+    const bool gpu_sha = challenges_on_gpu(N);   // (option "gpu_sha_min", as in the single batch)
+    std::vector<Fr> z(N), r(G, Fr::zero());
+    const size_t npool = 2 * N + 1;   // commitments, proofs, the generator
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(N * (size_t)BYTES_PER_BLOB + 2 * N * (48 + 2) + npool * sizeof(G1Affine) + (3 * N + G) * sizeof(Fr) + N * 4 +
+                 maps.size() * 4 + total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) +
+                 (2 * G + 1) * 4 + 20 * 256));
+    ArenaTrim trim(ar);
+    ABuf<uint8_t> d_ptb(ar, 2 * N * 48), d_st(ar, 2 * N), d_st2(ar, 2 * N), d_blobs(ar, N * (size_t)BYTES_PER_BLOB);
+    ABuf<G1Affine> d_pool(ar, npool), d_jobpts(ar, total), d_out(ar, 2 * G);
+    ABuf<Fr> d_z(ar, N), d_y(ar, N), d_ry(ar, N), d_r(ar, G);
+    ABuf<uint32_t> d_bad(ar, N), d_maps(ar, maps.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1);
+    ABuf<G1XYZZ> d_part(ar, nparts);
+    OKM(d_ptb.p && d_st.p && d_st2.p && d_blobs.p && d_pool.p && d_jobpts.p && d_out.p && d_z.p && d_y.p && d_ry.p && d_r.p &&
+        d_bad.p && d_maps.p && d_sc.p && d_off.p && d_part.p);
+    // what the host needs back lands in page-locked memory: evaluations | challenges, and blob flags | point flags
+    OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, N * 2 * sizeof(Fr)));
+    const Fr *h_y = static_cast<const Fr *>(ctx->h_out[0]), *h_z = h_y + N;
+    uint8_t *h1 = static_cast<uint8_t *>(ctx->h_out[1]);
+    const uint32_t *h_bad = reinterpret_cast<const uint32_t *>(h1);
+    const uint8_t *h_st = h1 + N * 4, *h_st2 = h_st + 2 * N;
+    OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess);
+    // whatever path leaves this function, both streams must be idle before the arena is reused
+    StreamDrain drain_main{ctx->stream}, drain{ctx->copy_stream};
+    // The challenges z_i on the host pool (one SHA-256 over 131,152 bytes per blob), underneath the copies below.
+    // (declared after everything its jobs touch: an early return waits for them first)
+    BackgroundFor hashes;
+    hashes.what = "blob group challenge hash jobs";
+    hashes.n = gpu_sha ? 0 : N;
+    hashes.fn = [&](size_t i) { z[i] = challenge_from_bytes(blobs[i].bytes, cb[i].bytes); };
+    hashes.start();
+    // The small copies from pageable memory first, then the one long copy, the blobs' (a chunk is at most 128 MiB: the
+    // size at which the single batch, too, validates underneath its copy -- plan_verify: split_validation).  Such a
+    // copy returns only when it is done, so the only kernel it queues behind is the short decompression; the subgroup
+    // test (~1 ms of dependent doublings) runs on the second stream underneath it and next to everything below.  Its
+    // flags are ordered by an event of their own (subgroup_ev) and read after the sums, before the pairings.  A point
+    // outside the subgroup makes the sums of its group meaningless, not unsafe: discarded.
+    OKB(hipMemcpyAsync(d_ptb.p, cb, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_ptb.p + N * 48, pb, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_maps.p, maps.data(), maps.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    RC(dev::decompress_g1_batch_device(ctx, d_pool.p, d_st.p, d_ptb.p, 2 * N));
+    OKB(hipMemcpyAsync(h1 + N * 4, d_st.p, 2 * N, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
+    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
+    RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pool.p, 2 * N, ctx->copy_stream));
+    OKB(hipMemcpyAsync(h1 + N * 4 + 2 * N, d_st2.p, 2 * N, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_blobs.p, blobs, N * (size_t)BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    // the jobs' points, gathered by index; the generator is g1_values_monomial[0]
+    OKB(hipMemcpyAsync(d_pool.p + 2 * N, ctx->d_mono, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
+    RC(dev::group_gather_points_enqueue(ctx, d_jobpts.p, d_pool.p, d_maps.p + m_src, total));
+    OKB(hipMemsetAsync(d_sc.p, 0, total * 32, ctx->stream) == hipSuccess);
+    OKB(hipMemsetAsync(d_bad.p, 0, N * 4, ctx->stream) == hipSuccess);
+    OKB(stage("copies and validation (underneath them the challenge hashes on the host)"));
+    if (gpu_sha) {
+        RC(dev::sha256_challenges_device(ctx, d_z.p, d_blobs.p, d_ptb.p, N));
+        OKB(hipMemcpyAsync(static_cast<uint8_t *>(ctx->h_out[0]) + N * sizeof(Fr), d_z.p, N * sizeof(Fr), hipMemcpyDeviceToHost,
+                           ctx->stream) == hipSuccess);
+    } else {
+        hashes.finish();
+        OKB(hipMemcpyAsync(d_z.p, z.data(), N * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    }
+    OKB(stage("challenges"));
+    RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p, d_bad.p, d_blobs.p, d_z.p, N));
+    OKB(hipMemcpyAsync(ctx->h_out[0], d_y.p, N * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(h1, d_bad.p, N * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+    tr.mark("evaluation");
+    // One SHA-256 stream per group of two or more blobs (eip4844.c:597-680 on the group's slice), on the host pool.
+    // Valid compressed encodings are canonical, so the input bytes are the re-compressed bytes; an invalid group's
+    // challenge is never used.
+    const Fr *zs = gpu_sha ? h_z : z.data();
+    parallel_for(G, [&](size_t g) {
+        const size_t a = (size_t)start[g], n = (size_t)(start[g + 1] - start[g]);
+        if (n < 2) return;   // r^0 = 1: a group of one is the single check (eip4844.c:797)
+        uint8_t digest[32];
+        host_batch_digest(digest, n, cb + a, pb + a, zs + a, h_y + a);
+        r[g] = fr_from_bytes_reduce(digest);
+    });
+    tr.mark("transcripts");
+    OKB(hipMemcpyAsync(d_r.p, r.data(), G * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    RC(dev::blob_group_scalars_enqueue(ctx, d_sc.p, d_ry.p, d_maps.p + m_grp, d_maps.p + m_gd, d_r.p, d_z.p, d_y.p, N, G));
+    OKB(stage("scalars"));
+    RC(dev::lincomb_multi_device(ctx, d_out.p, d_part.p, d_off.p, d_jobpts.p, d_sc.p, total, plan.part_off.data(), (int)(2 * G),
+                                 plan.quad));
+    std::vector<G1Affine> sums(2 * G);
+    OKB(d_out.down(sums.data(), 2 * G));
+    tr.mark("sums");
+    // the validation flags, folded into per-group status
+    OKB(dev::sync_event(ctx->subgroup_ev) == hipSuccess);
+    std::vector<uint8_t> invalid(G, 0);
+    for (size_t i = 0; i < N; i++) {
+        if (h_st[i] || h_st2[i] || h_st[N + i] || h_st2[N + i] || h_bad[i]) invalid[plan.blob_grp[i]] = 1;
+    }
+    // e(A_g, [1]_2) * e(-B_g, [s]_2) == 1, one check per valid group, on the host pool
+    std::vector<uint32_t> todo;
+    for (size_t g = 0; g < G; g++) {
+        if (start[g + 1] == start[g])
+            ok[g] = true;
+        else if (invalid[g])
+            status[g] = (uint8_t)C_KZG_BADARGS;
+        else
+            todo.push_back((uint32_t)g);
+    }
+    parallel_for(todo.size(), [&](size_t t) {
+        const size_t g = todo[t];
+        ok[g] = pairing_product_is_one(sums[2 * g], pg->gen, jac_to_affine_fast(jac_neg(jac_from_affine(sums[2 * g + 1]))), pg->s1);
+    });
+    tr.mark("pairings");
+    for (size_t g = 0; g < G; g++) {
+        if (status[g]) return C_KZG_BADARGS;
+    }
+    return C_KZG_OK;
+}
+
+extern "C" C_KZG_RET ckzg_hip_verify_blob_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Blob *blobs,
+                                                                const Bytes48 *commitments_bytes, const Bytes48 *proofs_bytes,
+                                                                const uint64_t *group_start, uint64_t num_groups,
+                                                                const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_groups == 0) return C_KZG_OK;
+        if (!ok || !group_start || group_start[0] != 0) return C_KZG_BADARGS;
+        for (uint64_t g = 0; g < num_groups; g++) {
+            if (group_start[g + 1] < group_start[g]) return C_KZG_BADARGS;
+        }
+        if (group_start[num_groups] != 0 && (!blobs || !commitments_bytes || !proofs_bytes)) return C_KZG_BADARGS;
+        std::vector<uint8_t> own_status;
+        if (!status) {
+            own_status.resize(num_groups);
+            status = own_status.data();
+        }
+        // Whole groups are the unit of splitting: contiguous runs of groups per device, and on a device chunks of at most
+        // CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS blobs / _CHUNK_GROUPS groups (what one pass keeps in HBM: 128 MiB of blobs), one
+        // after another.  A chunk of one group -- a call of one group, or a group larger than a chunk -- is the
+        // single-batch call.
+        return for_each_device_shard(s, num_groups, 16, [&](dev::DeviceCtx *ctx, uint64_t glo, uint64_t ghi) {
+            C_KZG_RET ret = C_KZG_OK;
+            std::vector<uint64_t> start;
+            for (uint64_t g0 = glo; g0 < ghi;) {
+                uint64_t g1 = g0 + 1;
+                while (g1 < ghi && g1 - g0 < CKZG_HIP_BLOB_GROUPS_CHUNK_GROUPS &&
+                       group_start[g1 + 1] - group_start[g0] <= CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS)
+                    g1++;
+                const uint64_t a = group_start[g0];
+                C_KZG_RET r;
+                if (g1 - g0 == 1) {
+                    r = verify_one_blob_group(ctx, ok + g0, status + g0, blobs + a, commitments_bytes + a, proofs_bytes + a,
+                                              group_start[g1] - a, s);
+                } else {
+                    start.resize(g1 - g0 + 1);
+                    for (uint64_t g = g0; g <= g1; g++) start[g - g0] = group_start[g] - a;
+                    r = verify_blob_groups_on(ctx, ok + g0, status + g0, blobs + a, commitments_bytes + a, proofs_bytes + a,
+                                              start.data(), (size_t)(g1 - g0), s);
                 }
                 if (r != C_KZG_OK && r != C_KZG_BADARGS) return r;
                 ret = worse(ret, r);

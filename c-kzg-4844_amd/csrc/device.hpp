@@ -550,6 +550,12 @@ int group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, co
                             const uint32_t *d_gd, size_t ngroups);
 //   d_out[t] <- d_pool[term_src[t]], infinity for a padding term
 int group_gather_points_enqueue(DeviceCtx *ctx, G1Affine *d_out, const G1Affine *d_pool, const uint32_t *d_term_src, size_t total);
+// Blob verification by groups (ckzg_hip_verify_blob_kzg_proof_batch_groups; index maps: blob_groups_plan.hpp, whose
+// field names the parameters carry).  Enqueue-only, on ctx->stream: k_blob_group_scalars, then k_blob_group_ysum.
+//   d_sc <- r_g^(i - start_g) on blob i's commitment in A_g and on its proof in B_g, times z_i on its proof in A_g, and
+//   minus the group's sum of r_g^(i - start_g) y_i on A_g's generator term; d_ry[n]: scratch for the summands
+int blob_group_scalars_enqueue(DeviceCtx *ctx, uint32_t *d_sc, Fr *d_ry, const uint32_t *d_blob_grp, const uint32_t *d_gd,
+                               const Fr *d_r, const Fr *d_z, const Fr *d_y, size_t n, size_t ngroups);
 int fr_mul_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n, size_t period);
 int fr_div_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n);
 // The rows form of recovery (ckzg_hip_recover_cells_and_kzg_proofs_rows; index maps: recover_rows_plan.hpp).  All

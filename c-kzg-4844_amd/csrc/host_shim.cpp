@@ -693,6 +693,63 @@ extern "C" long hs_cell_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_t
     return (long)p.total;
 }
 
+// ---- ckzg_hip_verify_blob_kzg_proof_batch_groups: the segmented scalar arithmetic of verify.hip
+// (k_blob_group_scalars, k_blob_group_ysum) replayed element by element over the index maps the product builds
+// (blob_groups_plan.hpp), so that the maps can be checked without a GPU (tests/test_blob_groups_cpu.py).  Field
+// elements cross as canonical little-endian limbs: z [N], y [N], r [G].  Out: the plan's sizes in info (total, quad),
+// term_src [total], part_off [2 G + 1] and the jobs' scalars sc [total][8].  Returns the number of terms, or -1 if it
+// exceeds cap_terms. ----
+#include "blob_groups_plan.hpp"
+extern "C" long hs_blob_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_t *part_off, uint32_t *info, size_t cap_terms,
+                                      const uint64_t *start, size_t G, const uint32_t *z_raw, const uint32_t *y_raw,
+                                      const uint32_t *r_raw, size_t quad_max_terms) {
+    BlobGroupsPlan p;
+    build_blob_groups_plan(p, start, G, quad_max_terms);
+    if (p.total > cap_terms) return -1;
+    const size_t N = p.N;
+    info[0] = (uint32_t)p.total;
+    info[1] = p.quad ? 1 : 0;
+    for (size_t t = 0; t < p.total; t++) term_src[t] = p.term_src[t];
+    for (size_t j = 0; j <= 2 * G; j++) part_off[j] = p.part_off[j];
+    for (size_t t = 0; t < p.total * 8; t++) sc[t] = 0;
+    auto fr_at = [](const uint32_t *raw, size_t i) { return from_raw<FrParams>(raw + i * 8); };
+    const uint32_t *gd = p.gd.data();
+    // k_blob_group_scalars
+    std::vector<Fr> ry(N);
+    for (size_t i = 0; i < N; i++) {
+        const uint32_t g = p.blob_grp[i], a = gd[g], off = (uint32_t)i - a, ng = gd[g + 1] - a;
+        Fr base = fr_at(r_raw, g), pw = Fr::one();
+        for (uint32_t e = off; e; e >>= 1) {
+            if (e & 1u) pw = mul(pw, base);
+            base = mul(base, base);
+        }
+        ry[i] = mul(pw, fr_at(y_raw, i));
+        const size_t tc = (size_t)gd[G + 1 + g] + off, tp = tc + ng, tb = (size_t)gd[2 * G + 1 + g] + off;
+        to_raw<FrParams>(sc + tc * 8, pw);
+        to_raw<FrParams>(sc + tp * 8, mul(pw, fr_at(z_raw, i)));
+        to_raw<FrParams>(sc + tb * 8, pw);
+    }
+    // k_blob_group_ysum: lane l of the group's wave takes blobs a + l, a + l + 64, ...; then the butterfly
+    for (size_t g = 0; g < G; g++) {
+        const uint32_t a = gd[g], b = gd[g + 1];
+        if (a == b) continue;
+        Fr lane[64];
+        for (uint32_t l = 0; l < 64; l++) {
+            lane[l] = Fr::zero();
+            for (uint32_t i = a + l; i < b; i += 64) lane[l] = add(lane[l], ry[i]);
+        }
+        if (b - a > 1) {
+            for (uint32_t m = 32; m >= 1; m >>= 1) {
+                Fr nxt[64];
+                for (uint32_t l = 0; l < 64; l++) nxt[l] = add(lane[l], lane[l ^ m]);
+                for (uint32_t l = 0; l < 64; l++) lane[l] = nxt[l];
+            }
+        }
+        to_raw<FrParams>(sc + ((size_t)gd[G + 1 + g] + 2 * (size_t)(b - a)) * 8, neg(lane[0]));
+    }
+    return (long)p.total;
+}
+
 // ---- ckzg_hip_recover_cells_and_kzg_proofs_rows: the index maps the product builds (recover_rows_plan.hpp) laid
 // out per caller row and per caller cell, and the per-cell factor arithmetic of k_recover_set_factors
 // (recover_set_factors.hpp: the very function the kernel calls) replayed for one set, so that both can be checked

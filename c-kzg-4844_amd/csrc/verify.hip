@@ -1080,6 +1080,83 @@ int group_gather_points_enqueue(DeviceCtx *ctx, G1Affine *d_out, const G1Affine 
 }
 
 // ------------------------------------------------------------------------------------------
+// blob verification by groups (ckzg_hip_verify_blob_kzg_proof_batch_groups).  The index maps are the host's
+// (blob_groups_plan.hpp); gd is its group table start[G + 1] | first term of A_g [G] | first term of B_g [G], and sc
+// the scalar vector of all jobs as above.
+// ------------------------------------------------------------------------------------------
+
+// Blob i of group g = [a, b) gets r_g^(i - a) by square-and-multiply from its offset (below the chunk limit: ten
+// squarings at most; r_g^0 = 1 whatever r_g, so a group of one needs no challenge): in canonical limbs on its
+// commitment in A_g and on its proof in B_g, times z_i on its proof in A_g, and times y_i into ry for the group's sum.
+__global__ void k_blob_group_scalars(uint32_t *sc, Fr *ry, const uint32_t *blob_grp, const uint32_t *gd, const Fr *r, const Fr *z,
+                                     const Fr *y, uint32_t n, uint32_t ngroups) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t g = blob_grp[i], a = gd[g], off = i - a, ng = gd[g + 1] - a;
+    Fr base = vld_fr(r + g), pw = Fr::one();
+#pragma unroll 1
+    for (uint32_t e = off; e; e >>= 1) {
+        if (e & 1u) pw = mul(pw, base);
+        base = mul(base, base);
+    }
+    vst_fr(ry + i, mul(pw, vld_fr(y + i)));
+    uint32_t p[8], pz[8];
+    to_raw<FrParams>(p, pw);
+    to_raw<FrParams>(pz, mul(pw, vld_fr(z + i)));
+    const size_t tc = (size_t)gd[ngroups + 1 + g] + off, tp = tc + ng, tb = (size_t)gd[2 * ngroups + 1 + g] + off;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        sc[tc * 8 + k] = p[k];
+        sc[tp * 8 + k] = pz[k];
+        sc[tb * 8 + k] = p[k];
+    }
+}
+
+// -sum_i r_g^(i - a) y_i in canonical limbs onto the generator's term of A_g.  One WAVE per group, four groups per
+// workgroup: groups range from one blob to a whole chunk, so a lane per group would walk a 1,000-blob group alone and
+// a workgroup per group would leave three waves of four idle on every one-blob group.  The wave's lanes stride over
+// the group's blobs and fold their partial sums with a butterfly over the limbs (six modular additions); a group of
+// one skips the fold.
+constexpr int YSUM_WAVES = 4;
+__global__ __launch_bounds__(64 * YSUM_WAVES) void k_blob_group_ysum(uint32_t *sc, const Fr *ry, const uint32_t *gd,
+                                                                    uint32_t ngroups) {
+    const uint32_t g = blockIdx.x * YSUM_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (g >= ngroups) return;   // (wave-uniform)
+    const uint32_t a = gd[g], b = gd[g + 1];
+    if (a == b) return;         // an empty group has no terms
+    Fr acc = Fr::zero();
+    for (uint32_t i = a + lane; i < b; i += 64) acc = add(acc, vld_fr(ry + i));
+    if (b - a > 1) {
+#pragma unroll 1
+        for (int m = 32; m >= 1; m >>= 1) {
+            Fr o;
+#pragma unroll
+            for (int k = 0; k < 8; k++) o.l[k] = (uint32_t)__shfl_xor((int)acc.l[k], m, 64);
+            acc = add(acc, o);
+        }
+    }
+    if (lane == 0) {
+        uint32_t raw[8];
+        to_raw<FrParams>(raw, neg(acc));
+        const size_t t = (size_t)gd[ngroups + 1 + g] + 2 * (size_t)(b - a);
+#pragma unroll
+        for (int k = 0; k < 8; k++) sc[t * 8 + k] = raw[k];
+    }
+}
+
+int blob_group_scalars_enqueue(DeviceCtx *ctx, uint32_t *d_sc, Fr *d_ry, const uint32_t *d_blob_grp, const uint32_t *d_gd,
+                               const Fr *d_r, const Fr *d_z, const Fr *d_y, size_t n, size_t ngroups) {
+    if (!n) return 0;
+    if (n >= ((size_t)1 << 31)) return 2;
+    hipLaunchKernelGGL(k_blob_group_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_sc, d_ry, d_blob_grp, d_gd,
+                       d_r, d_z, d_y, (uint32_t)n, (uint32_t)ngroups);
+    hipLaunchKernelGGL(k_blob_group_ysum, dim3((unsigned)((ngroups + YSUM_WAVES - 1) / YSUM_WAVES)), dim3(64 * YSUM_WAVES), 0,
+                       ctx->stream, d_sc, d_ry, d_gd, (uint32_t)ngroups);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // element-wise Fr helpers
 // ------------------------------------------------------------------------------------------
 

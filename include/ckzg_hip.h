@@ -213,6 +213,32 @@ C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status,
                                                       const Bytes48 *proofs_bytes, const uint64_t *group_start,
                                                       uint64_t num_groups, const KZGSettings *s);
 
+/* verify_blob_kzg_proof_batch (src/eip4844/eip4844.c:775-844) over num_groups independent batches in one call, one
+ * verdict per group -- a transaction pool validating blob transactions of 1-9 blobs each, a syncing node validating
+ * the blob sidecars of a range of blocks: callers that must know WHICH batch is bad.  Host pointers.  The three input
+ * arrays are flat, group_start[num_groups] entries long; group g is the slice [group_start[g], group_start[g + 1]).
+ * group_start has num_groups + 1 entries, starts at 0 and does not decrease.  For every g, (status[g], ok[g]) is
+ * exactly (return value, *ok) of
+ *   verify_blob_kzg_proof_batch(&ok, blobs + a, commitments + a, proofs + a, b - a, s)
+ * with a = group_start[g], b = group_start[g + 1]: an empty group is true with status 0; a commitment or proof that is
+ * not a valid G1 point, or a non-canonical field element in a blob, gives that group status 1 (C_KZG_BADARGS) and
+ * ok = false and says nothing about the other groups, whose verdicts are still computed and written.  Every group of
+ * two or more blobs has the reference's batch challenge for its slice (eip4844.c:597-680), a group of one is the
+ * single-blob check; no randomness is shared between groups, and every valid group gets its own pairing check.
+ * Returns C_KZG_BADARGS if any group is invalid, or if group_start is malformed (first entry not 0, or decreasing:
+ * nothing is written then); C_KZG_OK otherwise; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  status may be
+ * NULL; num_groups == 0 is C_KZG_OK and writes nothing.
+ * Whole groups are the unit of work: several devices take contiguous runs of groups, and on a device the groups are
+ * processed, one chunk after another, in chunks of at most CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS blobs and
+ * CKZG_HIP_BLOB_GROUPS_CHUNK_GROUPS groups; a group is never cut.  A group larger than a chunk, and a call of one
+ * group, go through the single-batch path. */
+#define CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS 1024
+#define CKZG_HIP_BLOB_GROUPS_CHUNK_GROUPS 1024
+C_KZG_RET ckzg_hip_verify_blob_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Blob *blobs,
+                                                      const Bytes48 *commitments_bytes, const Bytes48 *proofs_bytes,
+                                                      const uint64_t *group_start, uint64_t num_groups,
+                                                      const KZGSettings *s);
+
 /* verify_blob_kzg_proof_batch (src/eip4844/eip4844.c:775-844) with blobs, commitments and proofs resident in HBM
  * (device pointers on one GPU: n Blob, n Bytes48, n Bytes48).  Point validation, bytes -> field elements, the
  * Fiat-Shamir challenges (SHA-256 of every blob, on the GPU), the evaluations and the three random-linear-combination
