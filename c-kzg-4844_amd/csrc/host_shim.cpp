@@ -811,3 +811,21 @@ extern "C" void hs_recover_set_factors(uint32_t *z_domain, uint32_t *z_coset_inv
         to_raw<FrParams>(z_coset_inv + 8 * c, fr_inv_safegcd(zc));
     }
 }
+
+// ---- raw-limb entry points: the F28 operations at the bound combinations the group law instantiates
+// (f28_test_ops.hpp), limbs taken as they come so that a test can pass lazily reduced operands at the edge of
+// their bounds.  n items of 14 words per operand; returns 0, or 1 for an operation number past the list. ----
+#include "f28_test_ops.hpp"
+extern "C" const char *hs_f28_ops() { return f28test::desc(); }
+extern "C" int hs_f28_run(int op, uint32_t *out, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                          int n) {
+    for (int i = 0; i < n; i++)
+        if (!f28test::run(op, out + 14 * i, a + 14 * i, b + 14 * i, c + 14 * i, d + 14 * i)) return 1;
+    return 0;
+}
+
+// ---- the plain NAF of the pipelined G1-FFT ladders (naf2.hpp): n scalars of 4 words -> n * NAF2_LEN digits ----
+#include "naf2.hpp"
+extern "C" void hs_naf2_128(int8_t *out, const uint32_t *k, int n) {
+    for (int i = 0; i < n; i++) quad::naf2_128(out + quad::NAF2_LEN * i, k + 4 * i);
+}

@@ -1,0 +1,54 @@
+"""What can be said about the device test shim (tests/native/dev_shim.hip) and the generated inline-asm product
+without a GPU: libdev_shim.so cross-compiles for gfx950 and exports every ds_plain_* / ds_asm_* pair that
+tests/test_gpu_dev_arith.py binds, both forms and the host shim carry the same list of F28 instantiations, and the
+committed csrc/fp28_asm_cols.inc is byte for byte what tools/gen_fp28_asm.py emits."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import pytest
+
+from conftest import ROOT, SHIM_SO
+from test_gpu_dev_arith import DEV_SHIM_SO, FORMS, SHIM_FUNCTIONS
+
+PKG = os.path.join(ROOT, "c-kzg-4844_amd")
+
+
+@pytest.fixture(scope="module")
+def dev_shim_path():
+    if not os.path.exists(DEV_SHIM_SO):
+        subprocess.check_call(["make", "-C", PKG, "-j", "2", "libdev_shim.so"])
+    return DEV_SHIM_SO
+
+
+def test_dev_shim_builds_and_exports_both_forms(dev_shim_path):
+    out = subprocess.check_output(["nm", "-D", "--defined-only", dev_shim_path], text=True)
+    names = {line.split()[-1] for line in out.splitlines() if line.strip()}
+    for form in FORMS:
+        for fn in SHIM_FUNCTIONS:
+            assert "ds_%s_%s" % (form, fn) in names, (form, fn)
+    # the test aid stays out of the product
+    if not os.path.exists(os.path.join(PKG, "libckzg_hip.so")):
+        subprocess.check_call(["make", "-C", PKG, "-j", "4", "libckzg_hip.so"])
+    prod = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(PKG, "libckzg_hip.so")], text=True)
+    assert "ds_plain_" not in prod and "ds_asm_" not in prod
+
+
+def test_all_shims_list_the_same_instantiations(dev_shim_path):
+    if not os.path.exists(SHIM_SO):
+        subprocess.check_call(["make", "-C", PKG, "csrc/libhost_shim.so"])
+    d, h = C.CDLL(dev_shim_path), C.CDLL(SHIM_SO)
+    h.hs_f28_ops.restype = C.c_char_p
+    want = h.hs_f28_ops()
+    assert want
+    for form in FORMS:
+        fn = getattr(d, "ds_%s_f28_ops" % form)
+        fn.restype = C.c_char_p
+        assert fn() == want, form
+
+
+def test_generated_asm_product_matches_its_generator():
+    got = subprocess.check_output([sys.executable, os.path.join(ROOT, "tools", "gen_fp28_asm.py")])
+    with open(os.path.join(PKG, "csrc", "fp28_asm_cols.inc"), "rb") as f:
+        assert got == f.read()

@@ -9,10 +9,9 @@ import subprocess
 
 import pytest
 
+import arith_cases as ac
+from arith_cases import LAMBDA, P, R   # the case scripts are shared with the device tests (tests/arith_cases.py)
 from conftest import ORACLE_SO, ROOT, SHIM_SO
-
-P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
-R = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
 
 
 @pytest.fixture(scope="module")
@@ -186,7 +185,7 @@ def test_fast_fp12_routines_match_the_generic_product(libs):
 def test_fp28_field_ops_match_oracle(libs):
     o, h = libs
     rnd = random.Random(9)
-    edge = [0, 1, P - 1, P - 2, (P - 1) // 2, 2 ** 380, P - 3]
+    edge = ac.FP_EDGES
     for k in range(400):
         a = edge[k % 7] if k < 49 else rnd.randrange(P)
         b = edge[(k // 7) % 7] if k < 49 else rnd.randrange(P)
@@ -301,20 +300,7 @@ def test_xyzz28_sign_alternating_accumulation(libs):
         return a.raw
 
     base = [_omul(o, g, rnd.randrange(R)) for _ in range(12)]
-    # (index into base, subtract?) scripts
-    scripts = [
-        [(0, 0)], [(0, 1)], [(0, 0), (1, 0)], [(0, 1), (1, 0)], [(0, 0), (1, 1), (2, 0)],
-        [(0, 0), (0, 0)], [(0, 1), (0, 1)],                       # doubling as 2nd addition (stored sign "-")
-        [(0, 0), (1, 0), (0, 0)],
-        [(0, 0), (0, 1)], [(0, 1), (0, 0), (3, 0)],               # cancel, then restart
-        [(0, 0), (1, 0), (1, 1), (0, 1), (2, 1), (3, 0)],         # cancel in the middle of a chain
-        [(i % 12, rnd.randrange(2)) for i in range(150)],
-        [(rnd.randrange(12), rnd.randrange(2)) for i in range(200)],
-    ]
-    # P + Q where P = acc exactly (doubling at a later, even/odd position)
-    for pos in (2, 3):
-        sc = [(i, 0) for i in range(pos)]
-        scripts.append(("dbl", sc))
+    scripts = ac.alternation_scripts(rnd)   # (index into base, subtract?) scripts
     for sc in scripts:
         special = None
         if isinstance(sc, tuple):
@@ -379,7 +365,7 @@ def test_xyzz28_full_add_mul_neg(libs):
         assert o.og1_is_inf(r)
         h.hs_g1_neg28(r, p1)
         assert o.og1_equal(r, n1)
-        k = [0, 1, 15, 16, R - 1, R][t] if t < 6 else rnd.randrange(R)
+        k = ac.W4_SCALARS[t] if t < 6 else rnd.randrange(R)
         kk = (C.c_uint32 * 8)(*[(k >> (32 * i)) & 0xffffffff for i in range(8)])
         h.hs_g1_mul28(r, p1, kk)
         assert o.og1_equal(r, _omul(o, p1, k))
@@ -388,7 +374,7 @@ def test_xyzz28_full_add_mul_neg(libs):
     pt = _buf(144)
     pt[48:96] = (2 * r384 % P).to_bytes(48, "little")
     pt[96:144] = (r384 % P).to_bytes(48, "little")
-    for k in (3, 6, 7, R, R + 1, 4):
+    for k in ac.ORDER3_SCALARS:
         kk = (C.c_uint32 * 8)(*[(k >> (32 * i)) & 0xffffffff for i in range(8)])
         r = _buf(144)
         h.hs_g1_mul28(r, pt, kk)
@@ -405,7 +391,8 @@ def test_jacobian_28bit_formulas(libs):
     inf = _buf(144)
     for t in range(10):
         p1, p2 = _omul(o, g, rnd.randrange(1, R)), _omul(o, g, rnd.randrange(1, R))
-        for a, b, neg in ((p1, p2, 0), (p1, p2, 1), (p1, p1, 0), (p1, p1, 1), (inf, p2, 0), (inf, p2, 1)):
+        named = {"p1": p1, "p2": p2, "inf": inf}
+        for a, b, neg in ((named[x], named[y], sg) for x, y, sg in ac.JAC_ADD_TUPLES):
             ref, r, bb = _buf(144), _buf(144), _buf(144)
             bb.raw = b.raw
             if neg:
@@ -413,7 +400,7 @@ def test_jacobian_28bit_formulas(libs):
             o.og1_add(ref, a, bb)
             h.hs_g1_jac28_add(r, a, b, neg)
             assert o.og1_equal(r, ref), (t, neg)
-        n = [1, 2, 5, 64, 131, 300][t % 6]
+        n = ac.DBL_CHAIN_LENGTHS[t % 6]
         ref, r = _buf(144), _buf(144)
         ref.raw = p1.raw
         for _ in range(n):
@@ -427,13 +414,11 @@ def test_glv_split_and_glv_scalar_mul(libs):
     ladder [k1]P + [k2]phi(P) of the G1 FFT equals [k]P for subgroup points."""
     o, h = libs
     rnd = random.Random(29)
-    lam = (0xd201000000010000 ** 2 - 1)
+    lam = LAMBDA
     assert (lam * lam + lam + 1) == R
     g = _buf(144)
     h.hs_g1_generator(g)
-    w = pow(7, (R - 1) // 8192, R)
-    ks = [0, 1, lam - 1, lam, lam + 1, R - 1, R - 2, 2 ** 128, 2 ** 128 - 1, lam * lam, lam * lam + lam]
-    ks += [pow(w, 64 * i, R) for i in range(0, 129, 7)] + [rnd.randrange(R) for _ in range(40)]
+    ks = ac.glv_scalars(rnd)
     p1 = _omul(o, g, rnd.randrange(1, R))
     for n, k in enumerate(ks):
         kk = (C.c_uint32 * 8)(*[(k >> (32 * i)) & 0xffffffff for i in range(8)])
@@ -538,17 +523,12 @@ def test_endomorphism_subgroup_test_is_exact(libs):
     r384 = pow(2, 384, P)
 
     def curve_point(x0):
-        x = x0
-        while True:
-            rhs = (x * x * x + 4) % P
-            y = pow(rhs, (P + 1) // 4, P)
-            if y * y % P == rhs:
-                pt = _buf(144)
-                pt[0:48] = (x * r384 % P).to_bytes(48, "little")
-                pt[48:96] = (y * r384 % P).to_bytes(48, "little")
-                pt[96:144] = (r384 % P).to_bytes(48, "little")
-                return pt
-            x += 1
+        x, y = ac.curve_point_xy(x0)
+        pt = _buf(144)
+        pt[0:48] = (x * r384 % P).to_bytes(48, "little")
+        pt[48:96] = (y * r384 % P).to_bytes(48, "little")
+        pt[96:144] = (r384 % P).to_bytes(48, "little")
+        return pt
 
     def check(pt, expect=None):
         a = _buf(96)
@@ -593,9 +573,6 @@ def test_safegcd_inverse_matches_fermat_and_python(libs):
         if a < 2 ** 20 or a > P - 4:
             h.hs_fp28_inv(r2, ab)  # sliding-window Fermat ladder
             assert r1.raw == r2.raw
-
-
-LAMBDA = 0xd201000000010000 ** 2 - 1
 
 
 def test_glv_split_signed_and_window_recoding(libs):
