@@ -7,24 +7,22 @@
 //           reference deduplicates that slice's commitments (eip7594.c:345-376), so a pair's index inside its group is
 //           the commitment index the group's transcript hashes;
 //   rows    the distinct (group, column) pairs: one aggregated column each (eip7594.c:661-683), at most N of them;
-//   jobs    two linear combinations per group, laid out job after job and padded to a whole partial of the ladder
-//           kernels:  A_g = [its commitments | its proofs | the 64 setup points of the interpolation commitment]
+//   jobs    two linear combinations per group, in the layout of group_jobs.hpp:
+//                     A_g = [its commitments | its proofs | the 64 setup points of the interpolation commitment]
 //                     B_g = [its proofs]
 //           A_g's scalars are the weights, r^i h_k^64 and the negated interpolation coefficients, B_g's are r^i.
-//           An empty group has two empty jobs (the empty sum: infinity).
 // Points are named by their index in the chunk's pool [N proofs | the chunk's distinct commitments | 64 setup points].
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
+#include "group_jobs.hpp"
+
 namespace ckzg {
 
-constexpr uint32_t CELL_GROUPS_NO_POINT = 0xffffffffu;   // a padding term: the point at infinity, scalar 0
-
-struct CellGroupsPlan {
-    size_t N = 0, G = 0, P = 0, R = 0, total = 0;   // cells, groups, pairs, rows, terms of all jobs (padded)
-    bool quad = false;                              // jobs padded to 8 terms (four-lane ladders) or to 32
+struct CellGroupsPlan : GroupJobs {
+    size_t N = 0, G = 0, P = 0, R = 0;              // cells, groups, pairs, rows
     std::vector<uint32_t> cell_grp, cell_col;       // [N] group and column (< 128) of each cell
     std::vector<uint64_t> cell_pair;                // [N] index of the cell's commitment inside its group (the transcript's)
     std::vector<uint32_t> pair_off;                 // [G + 1] first pair of each group
@@ -36,9 +34,6 @@ struct CellGroupsPlan {
     std::vector<uint32_t> grp_rows;                 // [G + 1] first row of each group
     // [4 G + 1]: start[G + 1] | first term of A_g [G] | distinct commitments of g [G] | first term of B_g [G]
     std::vector<uint32_t> gd;
-    std::vector<uint32_t> term_src;                 // [total] pool index of each term's point, or CELL_GROUPS_NO_POINT
-    std::vector<uint32_t> part_off;                 // [2 G + 1] first partial of each job (A_0, B_0, A_1, ...)
-    size_t per() const { return quad ? 8 : 32; }
 };
 
 // start: G + 1 entries from 0 to N; cell_commit[i] < num_commits: the chunk-wide id of cell i's commitment;
@@ -58,9 +53,9 @@ inline void build_cell_groups_plan(CellGroupsPlan &p, const uint64_t *start, siz
     p.row_col.clear();
     std::vector<uint32_t> cell_row(N), cell_pair_abs(N);
     // stamps: which group last saw this commitment / column, and the pair / row it opened for it
-    std::vector<uint32_t> seen_c(num_commits, CELL_GROUPS_NO_POINT), slot_c(num_commits, 0);
+    std::vector<uint32_t> seen_c(num_commits, 0xffffffffu), slot_c(num_commits, 0);
     uint32_t seen_col[128], slot_col[128];
-    for (int c = 0; c < 128; c++) seen_col[c] = CELL_GROUPS_NO_POINT;
+    for (int c = 0; c < 128; c++) seen_col[c] = 0xffffffffu;
     for (size_t g = 0; g < G; g++) {
         p.pair_off[g] = (uint32_t)p.pair_commit.size();
         p.grp_rows[g] = (uint32_t)p.row_col.size();
@@ -100,48 +95,32 @@ inline void build_cell_groups_plan(CellGroupsPlan &p, const uint64_t *start, siz
     csr(p.pair_start, p.pair_members, cell_pair_abs, P);
     csr(p.row_start, p.row_order, cell_row, R);
     // the jobs
-    auto padded = [](size_t n, size_t per) { return (n + per - 1) / per * per; };
-    size_t total8 = 0;
-    for (size_t g = 0; g < G; g++) {
-        const size_t n = (size_t)(start[g + 1] - start[g]), nc = p.pair_off[g + 1] - p.pair_off[g];
-        if (n) total8 += padded(nc + n + 64, 8) + padded(n, 8);
-    }
-    p.quad = total8 <= quad_max_terms;
-    const size_t per = p.per();
     p.gd.assign(4 * G + 1, 0);
-    p.part_off.assign(2 * G + 1, 0);
     p.pair_term.resize(P);
-    p.term_src.clear();
     uint32_t *gstart = p.gd.data(), *term_a = gstart + G + 1, *ncs = term_a + G, *term_b = ncs + G;
+    for (size_t g = 0; g <= G; g++) gstart[g] = (uint32_t)start[g];
+    for (size_t g = 0; g < G; g++) ncs[g] = p.pair_off[g + 1] - p.pair_off[g];
     const uint32_t pool_commit = (uint32_t)N, pool_setup = (uint32_t)(N + num_commits);
-    for (size_t g = 0; g < G; g++) {
-        const size_t a = (size_t)start[g], n = (size_t)(start[g + 1] - start[g]), nc = p.pair_off[g + 1] - p.pair_off[g];
-        gstart[g] = (uint32_t)a;
-        ncs[g] = (uint32_t)nc;
-        term_a[g] = (uint32_t)p.term_src.size();
-        p.part_off[2 * g] = (uint32_t)(p.term_src.size() / per);
-        if (n) {
-            for (size_t j = 0; j < nc; j++) {
-                p.pair_term[p.pair_off[g] + j] = (uint32_t)p.term_src.size();
-                p.term_src.push_back(pool_commit + p.pair_commit[p.pair_off[g] + j]);
+    lay_out_group_jobs(
+        p, G, quad_max_terms, term_a, term_b,
+        [&](size_t g, bool b) -> size_t {
+            const size_t n = gstart[g + 1] - gstart[g];
+            return !n ? 0 : b ? n : ncs[g] + n + 64;
+        },
+        [&](size_t g, bool b, GroupJobTerms &out) {
+            const uint32_t a = gstart[g], n = gstart[g + 1] - a;
+            if (!n) return;
+            if (!b) {
+                for (uint32_t j = p.pair_off[g]; j < p.pair_off[g + 1]; j++) {
+                    p.pair_term[j] = out.at();
+                    out.put(pool_commit + p.pair_commit[j]);
+                }
             }
-            for (size_t i = 0; i < n; i++) p.term_src.push_back((uint32_t)(a + i));
-            for (uint32_t k = 0; k < 64; k++) p.term_src.push_back(pool_setup + k);
-            p.term_src.resize(padded(p.term_src.size(), per), CELL_GROUPS_NO_POINT);
-        }
-        term_b[g] = (uint32_t)p.term_src.size();
-        p.part_off[2 * g + 1] = (uint32_t)(p.term_src.size() / per);
-        if (n) {
-            for (size_t i = 0; i < n; i++) p.term_src.push_back((uint32_t)(a + i));
-            p.term_src.resize(padded(p.term_src.size(), per), CELL_GROUPS_NO_POINT);
-        }
-    }
-    gstart[G] = (uint32_t)N;
-    p.total = p.term_src.size();
-    p.part_off[2 * G] = (uint32_t)(p.total / per);
-    // the ladder kernels take a multiple of 64 terms
-    p.term_src.resize(padded(p.total, 64), CELL_GROUPS_NO_POINT);
-    p.total = p.term_src.size();
+            for (uint32_t i = 0; i < n; i++) out.put(a + i);
+            if (!b) {
+                for (uint32_t k = 0; k < 64; k++) out.put(pool_setup + k);
+            }
+        });
 }
 
 }  // namespace ckzg

@@ -15,6 +15,7 @@
 #include "cell_groups_plan.hpp"
 #include "combiner.hpp"
 #include "recover_rows_plan.hpp"
+#include "slice_starts.hpp"
 
 using namespace ckzg;
 using namespace ckzg::host;
@@ -1766,7 +1767,7 @@ extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_
         if (!settings_of(s)) return C_KZG_ERROR;
         if (num_rows == 0) return C_KZG_OK;
         if (recovered_cells == NULL && recovered_proofs == NULL) return C_KZG_BADARGS;
-        if (!recover_rows_start_ok(row_start, num_rows)) return C_KZG_BADARGS;
+        if (!slice_starts_ok(row_start, num_rows)) return C_KZG_BADARGS;
         if (row_start[num_rows] != 0 && (cell_indices == NULL || cells == NULL)) return C_KZG_BADARGS;
         // whole rows are the unit of splitting: contiguous runs of rows per device, chunks of rows on a device
         return for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
@@ -2108,13 +2109,13 @@ extern "C" C_KZG_RET verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commit
 }
 
 // ------------------------------------------------------------------------------------------
-// ckzg_hip_verify_cell_kzg_proof_batch_groups: many cell batches in one call, one verdict per group
+// Verification by groups (ckzg_hip_verify_cell_kzg_proof_batch_groups, ckzg_hip_verify_blob_kzg_proof_batch_groups):
+// what the two calls share.  Each call keeps what is its own -- its plan, arena, hashing and scalar kernels.
 // ------------------------------------------------------------------------------------------
 
-// One group through the single-batch path: (status, ok) = (return value, *ok) of verify_cell_kzg_proof_batch on it
-static C_KZG_RET verify_one_cell_group(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
-                                       const uint64_t *cell_indices, const Cell *cells, const Bytes48 *proofs_bytes, uint64_t n,
-                                       const KZGSettings *s) {
+// One group through a single-batch call one(&verdict): (status, ok) = (its return value, its verdict)
+template <class One>
+static C_KZG_RET verify_one_group(bool *ok, uint8_t *status, uint64_t n, One &&one) {
     *ok = false;
     *status = (uint8_t)C_KZG_OK;
     if (n == 0) {
@@ -2122,15 +2123,135 @@ static C_KZG_RET verify_one_cell_group(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
         return C_KZG_OK;
     }
     bool res = false;
-    C_KZG_RET r = C_KZG_OK;
-    for (uint64_t i = 0; i < n; i++) {
-        if (cell_indices[i] >= CELLS_PER_EXT_BLOB) r = C_KZG_BADARGS;
-    }
-    if (r == C_KZG_OK) r = verify_cells_on(ctx, &res, commitments_bytes, cell_indices, cells, proofs_bytes, n, s);
+    C_KZG_RET r = one(&res);
     if (r == C_KZG_OK) *ok = res;
     if (r == C_KZG_BADARGS) *status = (uint8_t)C_KZG_BADARGS;
     return r;
 }
+
+// The entry point of a grouped call over flat arrays of units (cells, blobs); have_data: none of the call's data
+// pointers is null.  Whole groups are the unit of splitting: contiguous runs of groups per device, and on a device
+// chunks of at most max_units units / max_groups groups (what one pass keeps in HBM), one after another.  A chunk of
+// one group -- a call of one group, or a group larger than a chunk -- is the single-batch call:
+//     one(ctx, ok, status, a, n)           one group: n units from unit a
+//     many(ctx, ok, status, a, start, G)   G groups from unit a; start[G + 1] is their part of group_start, rebased to a
+// both with ok / status of their first group.
+template <class One, class Many>
+static C_KZG_RET verify_groups_entry(bool *ok, uint8_t *status, const uint64_t *group_start, uint64_t num_groups, bool have_data,
+                                     const KZGSettings *s, uint64_t max_groups, uint64_t max_units, One &&one, Many &&many) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_groups == 0) return C_KZG_OK;
+        if (!ok || !slice_starts_ok(group_start, num_groups)) return C_KZG_BADARGS;
+        if (group_start[num_groups] != 0 && !have_data) return C_KZG_BADARGS;
+        std::vector<uint8_t> own_status;
+        if (!status) {
+            own_status.resize(num_groups);
+            status = own_status.data();
+        }
+        return for_each_device_shard(s, num_groups, 16, [&](dev::DeviceCtx *ctx, uint64_t glo, uint64_t ghi) {
+            C_KZG_RET ret = C_KZG_OK;
+            std::vector<uint64_t> start;
+            for (uint64_t g0 = glo; g0 < ghi;) {
+                uint64_t g1 = g0 + 1;
+                while (g1 < ghi && g1 - g0 < max_groups && group_start[g1 + 1] - group_start[g0] <= max_units) g1++;
+                const uint64_t a = group_start[g0];
+                C_KZG_RET r;
+                if (g1 - g0 == 1) {
+                    r = one(ctx, ok + g0, status + g0, a, group_start[g1] - a);
+                } else {
+                    start.resize(g1 - g0 + 1);
+                    for (uint64_t g = g0; g <= g1; g++) start[g - g0] = group_start[g] - a;
+                    r = many(ctx, ok + g0, status + g0, a, start.data(), (size_t)(g1 - g0));
+                }
+                if (r != C_KZG_OK && r != C_KZG_BADARGS) return r;
+                ret = worse(ret, r);
+                g0 = g1;
+            }
+            return ret;
+        });
+    });
+}
+
+// A trace whose stages are the stages' times: a traced call waits for the stream after every stage
+struct StagedTrace : Trace {
+    hipStream_t stream;
+    StagedTrace(const char *what, hipStream_t st) : Trace(what), stream(st) {}
+    bool stage(const char *name) {
+        if (on && dev::sync_stream(stream) != hipSuccess) return false;
+        mark(name);
+        return true;
+    }
+};
+
+// The index maps of a plan, one behind the other: one upload
+struct IndexMaps {
+    std::vector<uint32_t> words;
+    size_t put(const std::vector<uint32_t> &v) {   // -> where v starts
+        const size_t at = words.size();
+        words.insert(words.end(), v.begin(), v.end());
+        return at;
+    }
+    bool upload(uint32_t *d, hipStream_t stream) const {
+        return hipMemcpyAsync(d, words.data(), words.size() * 4, hipMemcpyHostToDevice, stream) == hipSuccess;
+    }
+};
+
+// n compressed points validated over two streams: decompression on the call's stream, the subgroup test (~1 ms of
+// dependent doublings) on the second stream, next to whatever the caller enqueues after this.  pts_ev: the points are
+// decompressed (and the first flags home); the subgroup flags are ordered by an event of their own (subgroup_ev) and
+// read after the sums, before the pairings.  A point outside the subgroup makes the sums of the groups that use it
+// meaningless, not unsafe: discarded.
+static C_KZG_RET validate_points_two_streams(dev::DeviceCtx *ctx, G1Affine *d_pts, uint8_t *d_st, uint8_t *d_st2,
+                                             const uint8_t *d_in48, size_t n, uint8_t *h_st, uint8_t *h_st2) {
+    RC(dev::decompress_g1_batch_device(ctx, d_pts, d_st, d_in48, n));
+    OKB(hipMemcpyAsync(h_st, d_st, n, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
+    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
+    RC(dev::subgroup_g1_batch_device(ctx, d_st2, d_pts, n, ctx->copy_stream));
+    OKB(hipMemcpyAsync(h_st2, d_st2, n, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
+    return C_KZG_OK;
+}
+
+// The two sums of every group in ONE pass of the ladder kernels over the plan's jobs; the 2 G points come back
+static C_KZG_RET group_sums(dev::DeviceCtx *ctx, std::vector<G1Affine> &sums, const GroupJobs &jobs, size_t G,
+                            const ABuf<G1Affine> &d_out, G1XYZZ *d_part, uint32_t *d_off, const G1Affine *d_jobpts,
+                            const uint32_t *d_sc) {
+    RC(dev::lincomb_multi_device(ctx, d_out.p, d_part, d_off, d_jobpts, d_sc, jobs.total, jobs.part_off.data(), (int)(2 * G),
+                                 jobs.quad));
+    sums.resize(2 * G);
+    OKB(d_out.down(sums.data(), 2 * G));
+    return C_KZG_OK;
+}
+
+// Verdicts and status from the folded validation flags and the sums: an empty group is valid, an invalid one gets
+// C_KZG_BADARGS, every other one its own check e(sums[2 g], [1]_2) * e(-sums[2 g + 1], q2) == 1 on the host pool
+static C_KZG_RET settle_groups(bool *ok, uint8_t *status, const uint64_t *start, size_t G, const std::vector<uint8_t> &invalid,
+                               const std::vector<G1Affine> &sums, const PreparedG2 *pg, const G2Prepared &q2, Trace &tr) {
+    std::vector<uint32_t> todo;
+    for (size_t g = 0; g < G; g++) {
+        if (start[g + 1] == start[g])
+            ok[g] = true;
+        else if (invalid[g])
+            status[g] = (uint8_t)C_KZG_BADARGS;
+        else
+            todo.push_back((uint32_t)g);
+    }
+    parallel_for(todo.size(), [&](size_t t) {
+        const size_t g = todo[t];
+        ok[g] = pairing_product_is_one(sums[2 * g], pg->gen, jac_to_affine_fast(jac_neg(jac_from_affine(sums[2 * g + 1]))), q2);
+    });
+    tr.mark("pairings");
+    for (size_t g = 0; g < G; g++) {
+        if (status[g]) return C_KZG_BADARGS;
+    }
+    return C_KZG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// ckzg_hip_verify_cell_kzg_proof_batch_groups: many cell batches in one call, one verdict per group
+// ------------------------------------------------------------------------------------------
 
 // G groups over start[G] cells (start[0] = 0) on one device, as one chunk.  Everything that costs latency rather than
 // work is paid once for the chunk: the points are validated in one launch each (the commitments deduplicated across
@@ -2154,12 +2275,7 @@ static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     }
     const PreparedG2 *pg = prepared_of(ctx);
     if (!pg) return C_KZG_ERROR;
-    Trace tr("verify_cell_groups");
-    auto stage = [&](const char *name) -> bool {   // (a traced call waits after every stage, so that the marks are the stages' times)
-        if (tr.on && dev::sync_stream(ctx->stream) != hipSuccess) return false;
-        tr.mark(name);
-        return true;
-    };
+    StagedTrace tr("verify_cell_groups", ctx->stream);
     std::vector<uint8_t> invalid(G, 0);
     // the chunk's distinct commitments: validated once, however many groups repeat them
     std::vector<uint32_t> cell_commit(N);
@@ -2200,26 +2316,22 @@ static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     };
     hashes.start();
     // the index maps, one upload
-    std::vector<uint32_t> maps;
-    maps.reserve(4 * N + 4 * G + 2 * P + 2 * R + total + 8);
-    auto put = [&maps](const std::vector<uint32_t> &v) {
-        const size_t at = maps.size();
-        maps.insert(maps.end(), v.begin(), v.end());
-        return at;
-    };
-    const size_t m_grp = put(plan.cell_grp), m_col = put(plan.cell_col), m_gd = put(plan.gd), m_pstart = put(plan.pair_start),
-                 m_pmem = put(plan.pair_members), m_pterm = put(plan.pair_term), m_rstart = put(plan.row_start),
-                 m_rorder = put(plan.row_order), m_rcol = put(plan.row_col), m_grows = put(plan.grp_rows), m_src = put(plan.term_src);
+    IndexMaps maps;
+    maps.words.reserve(4 * N + 4 * G + 2 * P + 2 * R + total + 8);
+    const size_t m_grp = maps.put(plan.cell_grp), m_col = maps.put(plan.cell_col), m_gd = maps.put(plan.gd),
+                 m_pstart = maps.put(plan.pair_start), m_pmem = maps.put(plan.pair_members), m_pterm = maps.put(plan.pair_term),
+                 m_rstart = maps.put(plan.row_start), m_rorder = maps.put(plan.row_order), m_rcol = maps.put(plan.row_col),
+                 m_grows = maps.put(plan.grp_rows), m_src = maps.put(plan.term_src);
     const size_t npool = N + ncu + l;   // proofs, the chunk's distinct commitments, g1_values_monomial[0..63]
     Arena &ar = ctx->api_arena;
     OKM(ar.begin((N + ncu) * (48 + 2) + npool * sizeof(G1Affine) + N * BYTES_PER_CELL + (N * l + N + R_ntt * l + G) * sizeof(Fr) + N * 4 +
-                 maps.size() * 4 + total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) +
+                 maps.words.size() * 4 + total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) +
                  (2 * G + 1) * 4 + 20 * 256));
     ArenaTrim trim(ar);
     ABuf<uint8_t> d_ptb(ar, (N + ncu) * 48), d_st(ar, N + ncu), d_st2(ar, N + ncu), d_cells(ar, N * BYTES_PER_CELL);
     ABuf<G1Affine> d_pool(ar, npool), d_jobpts(ar, total), d_out(ar, 2 * G);
     ABuf<Fr> d_cellfr(ar, N * l), d_rp(ar, N), d_rows(ar, R_ntt * l), d_r(ar, G);
-    ABuf<uint32_t> d_bad(ar, N), d_maps(ar, maps.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1);
+    ABuf<uint32_t> d_bad(ar, N), d_maps(ar, maps.words.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1);
     ABuf<G1XYZZ> d_part(ar, nparts);
     OKM(d_ptb.p && d_st.p && d_st2.p && d_cells.p && d_pool.p && d_jobpts.p && d_out.p && d_cellfr.p && d_rp.p && d_rows.p &&
         d_r.p && d_bad.p && d_maps.p && d_sc.p && d_off.p && d_part.p);
@@ -2235,17 +2347,8 @@ static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     OKB(hipMemcpyAsync(d_ptb.p, proofs_bytes, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     OKB(hipMemcpyAsync(d_ptb.p + N * 48, uniq.data(), ncu * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     OKB(hipMemcpyAsync(d_cells.p, cells, N * BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemcpyAsync(d_maps.p, maps.data(), maps.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    // decompression here, the subgroup test (~1 ms of dependent doublings) on the second stream, next to everything
-    // below; its flags are ordered by an event of their own (subgroup_ev) and read after the sums, before the pairings.
-    // A point outside the subgroup makes the sums of the groups that use it meaningless, not unsafe: discarded.
-    RC(dev::decompress_g1_batch_device(ctx, d_pool.p, d_st.p, d_ptb.p, N + ncu));
-    OKB(hipMemcpyAsync(h_st, d_st.p, N + ncu, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
-    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
-    RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pool.p, N + ncu, ctx->copy_stream));
-    OKB(hipMemcpyAsync(h_st2, d_st2.p, N + ncu, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
-    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
+    OKB(maps.upload(d_maps.p, ctx->stream));
+    RC(validate_points_two_streams(ctx, d_pool.p, d_st.p, d_st2.p, d_ptb.p, N + ncu, h_st, h_st2));
     OKB(hipMemsetAsync(d_bad.p, 0, N * 4, ctx->stream) == hipSuccess);
     RC(dev::bytes_to_fr_batch(ctx, d_cellfr.p, d_bad.p, d_cells.p, N * l, (uint32_t)l));
     OKB(hipMemcpyAsync(h_bad, d_bad.p, N * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
@@ -2255,23 +2358,21 @@ static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     RC(dev::group_gather_points_enqueue(ctx, d_jobpts.p, d_pool.p, d_maps.p + m_src, total));
     OKB(hipMemsetAsync(d_sc.p, 0, total * 32, ctx->stream) == hipSuccess);
     if (R_ntt > R) OKB(hipMemsetAsync(d_rows.p + R * l, 0, (R_ntt - R) * l * sizeof(Fr), ctx->stream) == hipSuccess);
-    OKB(stage("copies and validation (underneath the transcript hashes)"));
+    OKB(tr.stage("copies and validation (underneath the transcript hashes)"));
     hashes.finish();
     tr.mark("hashes");
     OKB(hipMemcpyAsync(d_r.p, r.data(), G * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     RC(dev::group_rlc_scalars_enqueue(ctx, d_rp.p, d_sc.p, d_maps.p + m_grp, d_maps.p + m_col, d_maps.p + m_gd, d_r.p,
                                       d_maps.p + m_pstart, d_maps.p + m_pmem, d_maps.p + m_pterm, N, G, P));
-    OKB(stage("scalars"));
+    OKB(tr.stage("scalars"));
     // per row: cell data is in bit-reversed order -> DIT inverse NTT(64) gives the interpolation polynomial over the
     // row's coset; the group's rows are summed with their own coset scaling (eip7594.c:661-752)
     RC(dev::group_cell_aggregate_device(ctx, d_rows.p, d_cellfr.p, d_rp.p, d_maps.p + m_rstart, d_maps.p + m_rorder, N, R));
     RC(dev::fr_ntt_batch(ctx, d_rows.p, R_ntt, 6, false, true, true));
     RC(dev::group_interp_sum_device(ctx, d_sc.p, d_rows.p, d_maps.p + m_grows, d_maps.p + m_rcol, d_maps.p + m_gd, G));
-    OKB(stage("aggregation"));
-    RC(dev::lincomb_multi_device(ctx, d_out.p, d_part.p, d_off.p, d_jobpts.p, d_sc.p, total, plan.part_off.data(), (int)(2 * G),
-                                 plan.quad));
-    std::vector<G1Affine> sums(2 * G);
-    OKB(d_out.down(sums.data(), 2 * G));
+    OKB(tr.stage("aggregation"));
+    std::vector<G1Affine> sums;
+    RC(group_sums(ctx, sums, plan, G, d_out, d_part.p, d_off.p, d_jobpts.p, d_sc.p));
     tr.mark("sums");
     // the validation flags, folded into per-group status
     OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
@@ -2280,93 +2381,35 @@ static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
         if (h_st[i] || h_st2[i] || h_st[c] || h_st2[c] || h_bad[i]) invalid[plan.cell_grp[i]] = 1;
     }
     // e(final_g, [1]_2) * e(-proof_lc_g, [s^64]_2) == 1, one check per valid group, on the host pool
-    std::vector<uint32_t> todo;
-    for (size_t g = 0; g < G; g++) {
-        if (start[g + 1] == start[g])
-            ok[g] = true;
-        else if (invalid[g])
-            status[g] = (uint8_t)C_KZG_BADARGS;
-        else
-            todo.push_back((uint32_t)g);
-    }
-    parallel_for(todo.size(), [&](size_t t) {
-        const size_t g = todo[t];
-        ok[g] = pairing_product_is_one(sums[2 * g], pg->gen, jac_to_affine_fast(jac_neg(jac_from_affine(sums[2 * g + 1]))), pg->s64);
-    });
-    tr.mark("pairings");
-    for (size_t g = 0; g < G; g++) {
-        if (status[g]) return C_KZG_BADARGS;
-    }
-    return C_KZG_OK;
+    return settle_groups(ok, status, start, G, invalid, sums, pg, pg->s64, tr);
 }
 
 extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
                                                                 const uint64_t *cell_indices, const Cell *cells,
                                                                 const Bytes48 *proofs_bytes, const uint64_t *group_start,
                                                                 uint64_t num_groups, const KZGSettings *s) {
-    return guarded([&]() -> C_KZG_RET {
-        if (!settings_of(s)) return C_KZG_ERROR;
-        if (num_groups == 0) return C_KZG_OK;
-        if (!ok || !group_start || group_start[0] != 0) return C_KZG_BADARGS;
-        for (uint64_t g = 0; g < num_groups; g++) {
-            if (group_start[g + 1] < group_start[g]) return C_KZG_BADARGS;
-        }
-        if (group_start[num_groups] != 0 && (!commitments_bytes || !cell_indices || !cells || !proofs_bytes)) return C_KZG_BADARGS;
-        std::vector<uint8_t> own_status;
-        if (!status) {
-            own_status.resize(num_groups);
-            status = own_status.data();
-        }
-        // Whole groups are the unit of splitting: contiguous runs of groups per device, and on a device chunks of at most
-        // CKZG_HIP_CELL_GROUPS_CHUNK_CELLS cells / _CHUNK_GROUPS groups (what one pass keeps in HBM).  A chunk of one group
-        // -- a call of one group, or a group larger than a chunk -- is the single-batch call.
-        return for_each_device_shard(s, num_groups, 16, [&](dev::DeviceCtx *ctx, uint64_t glo, uint64_t ghi) {
-            C_KZG_RET ret = C_KZG_OK;
-            std::vector<uint64_t> start;
-            for (uint64_t g0 = glo; g0 < ghi;) {
-                uint64_t g1 = g0 + 1;
-                while (g1 < ghi && g1 - g0 < CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS &&
-                       group_start[g1 + 1] - group_start[g0] <= CKZG_HIP_CELL_GROUPS_CHUNK_CELLS)
-                    g1++;
-                const uint64_t a = group_start[g0];
-                C_KZG_RET r;
-                if (g1 - g0 == 1) {
-                    r = verify_one_cell_group(ctx, ok + g0, status + g0, commitments_bytes + a, cell_indices + a, cells + a,
-                                              proofs_bytes + a, group_start[g1] - a, s);
-                } else {
-                    start.resize(g1 - g0 + 1);
-                    for (uint64_t g = g0; g <= g1; g++) start[g - g0] = group_start[g] - a;
-                    r = verify_cell_groups_on(ctx, ok + g0, status + g0, commitments_bytes + a, cell_indices + a, cells + a,
-                                              proofs_bytes + a, start.data(), (size_t)(g1 - g0), s);
+    // chunks of at most CKZG_HIP_CELL_GROUPS_CHUNK_CELLS cells / _CHUNK_GROUPS groups
+    return verify_groups_entry(
+        ok, status, group_start, num_groups, commitments_bytes && cell_indices && cells && proofs_bytes, s,
+        CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS, CKZG_HIP_CELL_GROUPS_CHUNK_CELLS,
+        [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, uint64_t n) {
+            // (status, ok) = (return value, *ok) of verify_cell_kzg_proof_batch on the group
+            return verify_one_group(ok, status, n, [&](bool *res) {
+                for (uint64_t i = 0; i < n; i++) {
+                    if (cell_indices[a + i] >= CELLS_PER_EXT_BLOB) return C_KZG_BADARGS;
                 }
-                if (r != C_KZG_OK && r != C_KZG_BADARGS) return r;
-                ret = worse(ret, r);
-                g0 = g1;
-            }
-            return ret;
+                return verify_cells_on(ctx, res, commitments_bytes + a, cell_indices + a, cells + a, proofs_bytes + a, n, s);
+            });
+        },
+        [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, const uint64_t *start, size_t G) {
+            return verify_cell_groups_on(ctx, ok, status, commitments_bytes + a, cell_indices + a, cells + a, proofs_bytes + a,
+                                         start, G, s);
         });
-    });
 }
 
 // ------------------------------------------------------------------------------------------
 // ckzg_hip_verify_blob_kzg_proof_batch_groups: many blob batches in one call, one verdict per group
 // ------------------------------------------------------------------------------------------
-
-// One group through the single-batch path: (status, ok) = (return value, *ok) of verify_blob_kzg_proof_batch on it
-static C_KZG_RET verify_one_blob_group(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Blob *blobs, const Bytes48 *cb,
-                                       const Bytes48 *pb, uint64_t n, const KZGSettings *s) {
-    *ok = false;
-    *status = (uint8_t)C_KZG_OK;
-    if (n == 0) {
-        *ok = true;
-        return C_KZG_OK;
-    }
-    bool res = false;
-    C_KZG_RET r = verify_blobs_core(&res, blobs, cb, pb, n, s, ctx);
-    if (r == C_KZG_OK) *ok = res;
-    if (r == C_KZG_BADARGS) *status = (uint8_t)C_KZG_BADARGS;
-    return r;
-}
 
 // G groups over start[G] blobs (start[0] = 0) on one device, as one chunk.  Everything but the batch challenge is per
 // blob already -- point validation, the challenges z_i, the evaluations y_i -- and runs over all N blobs as in one
@@ -2390,37 +2433,27 @@ static C_KZG_RET verify_blob_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     }
     const PreparedG2 *pg = prepared_of(ctx);
     if (!pg) return C_KZG_ERROR;
-    Trace tr("verify_blob_groups");
-    auto stage = [&](const char *name) -> bool {   // (a traced call waits after every stage, so that the marks are the stages' times)
-        if (tr.on && dev::sync_stream(ctx->stream) != hipSuccess) return false;
-        tr.mark(name);
-        return true;
-    };
+    StagedTrace tr("verify_blob_groups", ctx->stream);
     static const size_t quad_max = (size_t)dev::ab_knob("CKZG_HIP_QUAD_MAX", 8192);
     BlobGroupsPlan plan;
     build_blob_groups_plan(plan, start, G, quad_max);
     const size_t total = plan.total, nparts = total / plan.per();
     // the index maps, one upload
-    std::vector<uint32_t> maps;
-    maps.reserve(N + 3 * G + 1 + total);
-    auto put = [&maps](const std::vector<uint32_t> &v) {
-        const size_t at = maps.size();
-        maps.insert(maps.end(), v.begin(), v.end());
-        return at;
-    };
-    const size_t m_grp = put(plan.blob_grp), m_gd = put(plan.gd), m_src = put(plan.term_src);
+    IndexMaps maps;
+    maps.words.reserve(N + 3 * G + 1 + total);
+    const size_t m_grp = maps.put(plan.blob_grp), m_gd = maps.put(plan.gd), m_src = maps.put(plan.term_src);
     const bool gpu_sha = challenges_on_gpu(N);   // (option "gpu_sha_min", as in the single batch)
     std::vector<Fr> z(N), r(G, Fr::zero());
     const size_t npool = 2 * N + 1;   // commitments, proofs, the generator
     Arena &ar = ctx->api_arena;
     OKM(ar.begin(N * (size_t)BYTES_PER_BLOB + 2 * N * (48 + 2) + npool * sizeof(G1Affine) + (3 * N + G) * sizeof(Fr) + N * 4 +
-                 maps.size() * 4 + total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) +
+                 maps.words.size() * 4 + total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) +
                  (2 * G + 1) * 4 + 20 * 256));
     ArenaTrim trim(ar);
     ABuf<uint8_t> d_ptb(ar, 2 * N * 48), d_st(ar, 2 * N), d_st2(ar, 2 * N), d_blobs(ar, N * (size_t)BYTES_PER_BLOB);
     ABuf<G1Affine> d_pool(ar, npool), d_jobpts(ar, total), d_out(ar, 2 * G);
     ABuf<Fr> d_z(ar, N), d_y(ar, N), d_ry(ar, N), d_r(ar, G);
-    ABuf<uint32_t> d_bad(ar, N), d_maps(ar, maps.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1);
+    ABuf<uint32_t> d_bad(ar, N), d_maps(ar, maps.words.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1);
     ABuf<G1XYZZ> d_part(ar, nparts);
     OKM(d_ptb.p && d_st.p && d_st2.p && d_blobs.p && d_pool.p && d_jobpts.p && d_out.p && d_z.p && d_y.p && d_ry.p && d_r.p &&
         d_bad.p && d_maps.p && d_sc.p && d_off.p && d_part.p);
@@ -2429,7 +2462,7 @@ static C_KZG_RET verify_blob_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     const Fr *h_y = static_cast<const Fr *>(ctx->h_out[0]), *h_z = h_y + N;
     uint8_t *h1 = static_cast<uint8_t *>(ctx->h_out[1]);
     const uint32_t *h_bad = reinterpret_cast<const uint32_t *>(h1);
-    const uint8_t *h_st = h1 + N * 4, *h_st2 = h_st + 2 * N;
+    uint8_t *h_st = h1 + N * 4, *h_st2 = h_st + 2 * N;
     OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess);
     // whatever path leaves this function, both streams must be idle before the arena is reused
     StreamDrain drain_main{ctx->stream}, drain{ctx->copy_stream};
@@ -2443,26 +2476,18 @@ static C_KZG_RET verify_blob_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     // The small copies from pageable memory first, then the one long copy, the blobs' (a chunk is at most 128 MiB: the
     // size at which the single batch, too, validates underneath its copy -- plan_verify: split_validation).  Such a
     // copy returns only when it is done, so the only kernel it queues behind is the short decompression; the subgroup
-    // test (~1 ms of dependent doublings) runs on the second stream underneath it and next to everything below.  Its
-    // flags are ordered by an event of their own (subgroup_ev) and read after the sums, before the pairings.  A point
-    // outside the subgroup makes the sums of its group meaningless, not unsafe: discarded.
+    // test runs on the second stream underneath it and next to everything below.
     OKB(hipMemcpyAsync(d_ptb.p, cb, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     OKB(hipMemcpyAsync(d_ptb.p + N * 48, pb, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemcpyAsync(d_maps.p, maps.data(), maps.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    RC(dev::decompress_g1_batch_device(ctx, d_pool.p, d_st.p, d_ptb.p, 2 * N));
-    OKB(hipMemcpyAsync(h1 + N * 4, d_st.p, 2 * N, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
-    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
-    RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pool.p, 2 * N, ctx->copy_stream));
-    OKB(hipMemcpyAsync(h1 + N * 4 + 2 * N, d_st2.p, 2 * N, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
-    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
+    OKB(maps.upload(d_maps.p, ctx->stream));
+    RC(validate_points_two_streams(ctx, d_pool.p, d_st.p, d_st2.p, d_ptb.p, 2 * N, h_st, h_st2));
     OKB(hipMemcpyAsync(d_blobs.p, blobs, N * (size_t)BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     // the jobs' points, gathered by index; the generator is g1_values_monomial[0]
     OKB(hipMemcpyAsync(d_pool.p + 2 * N, ctx->d_mono, sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
     RC(dev::group_gather_points_enqueue(ctx, d_jobpts.p, d_pool.p, d_maps.p + m_src, total));
     OKB(hipMemsetAsync(d_sc.p, 0, total * 32, ctx->stream) == hipSuccess);
     OKB(hipMemsetAsync(d_bad.p, 0, N * 4, ctx->stream) == hipSuccess);
-    OKB(stage("copies and validation (underneath them the challenge hashes on the host)"));
+    OKB(tr.stage("copies and validation (underneath them the challenge hashes on the host)"));
     if (gpu_sha) {
         RC(dev::sha256_challenges_device(ctx, d_z.p, d_blobs.p, d_ptb.p, N));
         OKB(hipMemcpyAsync(static_cast<uint8_t *>(ctx->h_out[0]) + N * sizeof(Fr), d_z.p, N * sizeof(Fr), hipMemcpyDeviceToHost,
@@ -2471,7 +2496,7 @@ static C_KZG_RET verify_blob_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
         hashes.finish();
         OKB(hipMemcpyAsync(d_z.p, z.data(), N * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     }
-    OKB(stage("challenges"));
+    OKB(tr.stage("challenges"));
     RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p, d_bad.p, d_blobs.p, d_z.p, N));
     OKB(hipMemcpyAsync(ctx->h_out[0], d_y.p, N * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
     OKB(hipMemcpyAsync(h1, d_bad.p, N * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
@@ -2491,11 +2516,9 @@ static C_KZG_RET verify_blob_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     tr.mark("transcripts");
     OKB(hipMemcpyAsync(d_r.p, r.data(), G * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     RC(dev::blob_group_scalars_enqueue(ctx, d_sc.p, d_ry.p, d_maps.p + m_grp, d_maps.p + m_gd, d_r.p, d_z.p, d_y.p, N, G));
-    OKB(stage("scalars"));
-    RC(dev::lincomb_multi_device(ctx, d_out.p, d_part.p, d_off.p, d_jobpts.p, d_sc.p, total, plan.part_off.data(), (int)(2 * G),
-                                 plan.quad));
-    std::vector<G1Affine> sums(2 * G);
-    OKB(d_out.down(sums.data(), 2 * G));
+    OKB(tr.stage("scalars"));
+    std::vector<G1Affine> sums;
+    RC(group_sums(ctx, sums, plan, G, d_out, d_part.p, d_off.p, d_jobpts.p, d_sc.p));
     tr.mark("sums");
     // the validation flags, folded into per-group status
     OKB(dev::sync_event(ctx->subgroup_ev) == hipSuccess);
@@ -2504,73 +2527,26 @@ static C_KZG_RET verify_blob_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
         if (h_st[i] || h_st2[i] || h_st[N + i] || h_st2[N + i] || h_bad[i]) invalid[plan.blob_grp[i]] = 1;
     }
     // e(A_g, [1]_2) * e(-B_g, [s]_2) == 1, one check per valid group, on the host pool
-    std::vector<uint32_t> todo;
-    for (size_t g = 0; g < G; g++) {
-        if (start[g + 1] == start[g])
-            ok[g] = true;
-        else if (invalid[g])
-            status[g] = (uint8_t)C_KZG_BADARGS;
-        else
-            todo.push_back((uint32_t)g);
-    }
-    parallel_for(todo.size(), [&](size_t t) {
-        const size_t g = todo[t];
-        ok[g] = pairing_product_is_one(sums[2 * g], pg->gen, jac_to_affine_fast(jac_neg(jac_from_affine(sums[2 * g + 1]))), pg->s1);
-    });
-    tr.mark("pairings");
-    for (size_t g = 0; g < G; g++) {
-        if (status[g]) return C_KZG_BADARGS;
-    }
-    return C_KZG_OK;
+    return settle_groups(ok, status, start, G, invalid, sums, pg, pg->s1, tr);
 }
 
 extern "C" C_KZG_RET ckzg_hip_verify_blob_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Blob *blobs,
                                                                 const Bytes48 *commitments_bytes, const Bytes48 *proofs_bytes,
                                                                 const uint64_t *group_start, uint64_t num_groups,
                                                                 const KZGSettings *s) {
-    return guarded([&]() -> C_KZG_RET {
-        if (!settings_of(s)) return C_KZG_ERROR;
-        if (num_groups == 0) return C_KZG_OK;
-        if (!ok || !group_start || group_start[0] != 0) return C_KZG_BADARGS;
-        for (uint64_t g = 0; g < num_groups; g++) {
-            if (group_start[g + 1] < group_start[g]) return C_KZG_BADARGS;
-        }
-        if (group_start[num_groups] != 0 && (!blobs || !commitments_bytes || !proofs_bytes)) return C_KZG_BADARGS;
-        std::vector<uint8_t> own_status;
-        if (!status) {
-            own_status.resize(num_groups);
-            status = own_status.data();
-        }
-        // Whole groups are the unit of splitting: contiguous runs of groups per device, and on a device chunks of at most
-        // CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS blobs / _CHUNK_GROUPS groups (what one pass keeps in HBM: 128 MiB of blobs), one
-        // after another.  A chunk of one group -- a call of one group, or a group larger than a chunk -- is the
-        // single-batch call.
-        return for_each_device_shard(s, num_groups, 16, [&](dev::DeviceCtx *ctx, uint64_t glo, uint64_t ghi) {
-            C_KZG_RET ret = C_KZG_OK;
-            std::vector<uint64_t> start;
-            for (uint64_t g0 = glo; g0 < ghi;) {
-                uint64_t g1 = g0 + 1;
-                while (g1 < ghi && g1 - g0 < CKZG_HIP_BLOB_GROUPS_CHUNK_GROUPS &&
-                       group_start[g1 + 1] - group_start[g0] <= CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS)
-                    g1++;
-                const uint64_t a = group_start[g0];
-                C_KZG_RET r;
-                if (g1 - g0 == 1) {
-                    r = verify_one_blob_group(ctx, ok + g0, status + g0, blobs + a, commitments_bytes + a, proofs_bytes + a,
-                                              group_start[g1] - a, s);
-                } else {
-                    start.resize(g1 - g0 + 1);
-                    for (uint64_t g = g0; g <= g1; g++) start[g - g0] = group_start[g] - a;
-                    r = verify_blob_groups_on(ctx, ok + g0, status + g0, blobs + a, commitments_bytes + a, proofs_bytes + a,
-                                              start.data(), (size_t)(g1 - g0), s);
-                }
-                if (r != C_KZG_OK && r != C_KZG_BADARGS) return r;
-                ret = worse(ret, r);
-                g0 = g1;
-            }
-            return ret;
+    // chunks of at most CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS blobs (128 MiB of them) / _CHUNK_GROUPS groups
+    return verify_groups_entry(
+        ok, status, group_start, num_groups, blobs && commitments_bytes && proofs_bytes, s, CKZG_HIP_BLOB_GROUPS_CHUNK_GROUPS,
+        CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS,
+        [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, uint64_t n) {
+            // (status, ok) = (return value, *ok) of verify_blob_kzg_proof_batch on the group
+            return verify_one_group(ok, status, n, [&](bool *res) {
+                return verify_blobs_core(res, blobs + a, commitments_bytes + a, proofs_bytes + a, n, s, ctx);
+            });
+        },
+        [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, const uint64_t *start, size_t G) {
+            return verify_blob_groups_on(ctx, ok, status, blobs + a, commitments_bytes + a, proofs_bytes + a, start, G, s);
         });
-    });
 }
 
 // ------------------------------------------------------------------------------------------

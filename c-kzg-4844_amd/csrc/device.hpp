@@ -534,9 +534,9 @@ int cell_aggregate_device(DeviceCtx *ctx, Fr *d_agg, const Fr *d_cell_fr, const 
                           const uint32_t *d_order, size_t n_cells);
 // interpolation-polynomial coefficients summed over the 128 columns, as canonical MSM scalars
 int interp_sum_device(DeviceCtx *ctx, Fr *d_interp, const Fr *d_cols);
-// The same steps segmented by group (ckzg_hip_verify_cell_kzg_proof_batch_groups; index maps: cell_groups_plan.hpp,
-// whose field names the parameters carry).  All enqueue-only, on ctx->stream.  d_sc: the scalars of every job
-// ([total][8], zeroed by the caller), d_r: the groups' challenges (Montgomery).
+// The same steps segmented by group (ckzg_hip_verify_cell_kzg_proof_batch_groups; index maps: cell_groups_plan.hpp over
+// the job layout of group_jobs.hpp, whose field names the parameters carry).  All enqueue-only, on ctx->stream.
+// d_sc: the scalars of every job ([total][8], zeroed by the caller), d_r: the groups' challenges (Montgomery).
 //   d_rp[n] <- r_g^(i - start_g); d_sc <- the same on each cell's proof in B_g, times h_k^64 in A_g, and the
 //   per-(group, commitment) weights on the pairs' terms
 int group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_cell_grp, const uint32_t *d_cell_col,
@@ -550,8 +550,8 @@ int group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, co
                             const uint32_t *d_gd, size_t ngroups);
 //   d_out[t] <- d_pool[term_src[t]], infinity for a padding term
 int group_gather_points_enqueue(DeviceCtx *ctx, G1Affine *d_out, const G1Affine *d_pool, const uint32_t *d_term_src, size_t total);
-// Blob verification by groups (ckzg_hip_verify_blob_kzg_proof_batch_groups; index maps: blob_groups_plan.hpp, whose
-// field names the parameters carry).  Enqueue-only, on ctx->stream: k_blob_group_scalars, then k_blob_group_ysum.
+// Blob verification by groups (ckzg_hip_verify_blob_kzg_proof_batch_groups; index maps: blob_groups_plan.hpp, over the
+// same job layout).  Enqueue-only, on ctx->stream: k_blob_group_scalars, then k_blob_group_ysum.
 //   d_sc <- r_g^(i - start_g) on blob i's commitment in A_g and on its proof in B_g, times z_i on its proof in A_g, and
 //   minus the group's sum of r_g^(i - start_g) y_i on A_g's generator term; d_ry[n]: scratch for the summands
 int blob_group_scalars_enqueue(DeviceCtx *ctx, uint32_t *d_sc, Fr *d_ry, const uint32_t *d_blob_grp, const uint32_t *d_gd,

@@ -764,7 +764,7 @@ extern "C" long hs_recover_rows_plan(uint8_t *valid, uint32_t *row_chunk, uint32
                                      uint32_t *row_mask, uint32_t *cell_pos, uint32_t *cell_dst, uint32_t *chunk_info,
                                      size_t cap_chunks, const uint64_t *cell_indices, const uint64_t *row_start,
                                      uint64_t num_rows, size_t chunk_rows) {
-    if (!recover_rows_start_ok(row_start, num_rows)) return -1;
+    if (!slice_starts_ok(row_start, num_rows)) return -1;
     RecoverRowsPlan p;
     build_recover_rows_plan(p, cell_indices, row_start, num_rows, chunk_rows);
     if (p.chunks.size() > cap_chunks) return -2;

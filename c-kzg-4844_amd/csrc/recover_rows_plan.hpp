@@ -19,6 +19,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "slice_starts.hpp"
+
 namespace ckzg {
 
 struct RecoverRowsRun {
@@ -44,15 +46,6 @@ struct RecoverRowsPlan {
     size_t max_rows = 0, max_cells = 0, max_sets = 0;   // over the chunks: what the device buffers must hold
 };
 
-// row_start: num_rows + 1 entries, starts at 0, does not decrease
-inline bool recover_rows_start_ok(const uint64_t *row_start, uint64_t num_rows) {
-    if (!row_start || row_start[0] != 0) return false;
-    for (uint64_t r = 0; r < num_rows; r++) {
-        if (row_start[r + 1] < row_start[r]) return false;
-    }
-    return true;
-}
-
 struct RecoverRowsMaskHash {
     size_t operator()(const std::pair<uint64_t, uint64_t> &m) const {
         uint64_t h = m.first * 0x9e3779b97f4a7c15ull ^ (m.second + 0x632be59bd9b4e019ull);
@@ -62,7 +55,7 @@ struct RecoverRowsMaskHash {
     }
 };
 
-// row_start must have passed recover_rows_start_ok
+// row_start must have passed slice_starts_ok
 inline void build_recover_rows_plan(RecoverRowsPlan &p, const uint64_t *cell_indices, const uint64_t *row_start,
                                     uint64_t num_rows, size_t chunk_rows) {
     p.valid.assign((size_t)num_rows, 0);
