@@ -829,3 +829,20 @@ extern "C" int hs_f28_run(int op, uint32_t *out, const uint32_t *a, const uint32
 extern "C" void hs_naf2_128(int8_t *out, const uint32_t *k, int n) {
     for (int i = 0; i < n; i++) quad::naf2_128(out + quad::NAF2_LEN * i, k + 4 * i);
 }
+
+// ---- raw-word entry points: Mont<Fp> / Mont<Fr>, Fr29, the safegcd inversions and the pairing tower
+// (field_test_ops.hpp).  n items; operand k of item i lies at k + width * i, the shared operands (line tables) at k.
+// Returns 0, or 1 for an operation number past the list. ----
+#include "field_test_ops.hpp"
+extern "C" const char *hs_field_ops() { return fieldtest::desc(); }
+extern "C" int hs_field_run(int op, uint32_t *out, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                            int n) {
+    return fieldtest::run_items(op, out, a, b, c, d, n) ? 0 : 1;
+}
+// the line table of a G2 point as k_pairing_check reads it: lam[68] then c[68] (host_pairing.hpp: g2_prepare)
+extern "C" void hs_g2_line_table(uint32_t *out, const G2Jac *q) {
+    G2Prepared p;
+    g2_prepare(p, g2_to_affine(*q));
+    memcpy(out, p.lam, sizeof p.lam);
+    memcpy(out + sizeof p.lam / 4, p.c, sizeof p.c);
+}

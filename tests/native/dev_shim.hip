@@ -1,7 +1,8 @@
 // dev_shim.hip -- the device-only arithmetic behind a C ABI, the counterpart of csrc/host_shim.cpp for what g++
 // never sees: the F28 product as the DEVICE compiler builds it, its inline-asm form (CKZG_F28_ASM_BLOCKS), all of
-// g1_quad.hpp (the DPP-quad group law) and the straight-line routines of g1_pipe.hpp (xyzz28_addsub_quad,
-// jac28_add_quad_pipe, naf2_128, naf_masks).  Test aid only
+// g1_quad.hpp (the DPP-quad group law), the straight-line routines of g1_pipe.hpp (xyzz28_addsub_quad,
+// jac28_add_quad_pipe, naf2_128, naf_masks), f28_inv_safegcd, and g1.hpp's complete xyzz_add / xyzz_dbl on 32-bit limbs.
+// The fields under the Fr kernels and the pairing are in dev_shim_fields.hip (one plain build, ds_dev_*).  Test aid only
 // (tests/test_gpu_dev_arith.py); never part of libckzg_hip.so.
 //
 // ONE source, compiled twice: with the product's plain flags and -D'DS(x)=ds_plain_##x', and with
@@ -20,11 +21,7 @@
 // last workgroup repeat the last item and write nothing -- the product never runs a partly filled quad either (a DPP
 // read of an inactive lane returns 0): its quad kernels pad the same way (fk20.hip k_g1_fft_twiddle_quad,
 // verify.hip k_subgroup_g1_quad).  One-lane routines run in all four lanes of the quad on the same input.
-#include <hip/hip_runtime.h>
-#include <chrono>
-#include <cstdlib>
-#include <thread>
-#include <vector>
+#include "dev_shim_common.hpp"
 #include "f28_test_ops.hpp"
 #include "g1_pipe.hpp"
 #include "dev_inline.hpp"
@@ -36,64 +33,6 @@
 using namespace ckzg;
 
 namespace {
-
-constexpr int DS_DEADLINE = 9999;   // the kernel did not finish in time (distinct from every hipError_t)
-constexpr int DS_BAD_ARG = 9998;
-constexpr int MAX_CHAIN = 512;      // no loop of a shim kernel runs longer, whatever the caller passes
-constexpr int MAX_BLOCK = 256;      // __launch_bounds__ of every kernel: the tests launch workgroups of 64 and 256 threads
-
-int pick_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return 0;
-    if (const char *v = getenv("CKZG_HIP_DEVICE")) return atoi(v);
-    if (const char *v = getenv("LOCAL_RANK")) return atoi(v) % ndev;
-    return 0;
-}
-
-struct Arg {
-    const void *in;   // host source (inputs), or null
-    void *out;        // host destination (outputs), or null
-    size_t bytes;
-    void *dev;
-};
-
-template <class Launch>
-int run_bounded(std::vector<Arg> &args, Launch &&launch) {
-    hipError_t e = hipSetDevice(pick_device());
-    if (e != hipSuccess) return (int)e;
-    hipStream_t st;
-    if ((e = hipStreamCreate(&st)) != hipSuccess) return (int)e;
-    int rc = 0;
-    for (Arg &a : args) {
-        a.dev = nullptr;
-        if ((e = hipMalloc(&a.dev, a.bytes ? a.bytes : 4)) != hipSuccess) { rc = (int)e; break; }
-        e = a.in ? hipMemcpyAsync(a.dev, a.in, a.bytes, hipMemcpyHostToDevice, st) : hipMemsetAsync(a.dev, 0, a.bytes ? a.bytes : 4, st);
-        if (e != hipSuccess) { rc = (int)e; break; }
-    }
-    if (rc == 0) {
-        launch(st);
-        if ((e = hipGetLastError()) != hipSuccess) rc = (int)e;
-    }
-    if (rc == 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            e = hipStreamQuery(st);
-            if (e == hipSuccess) break;
-            if (e != hipErrorNotReady) { rc = (int)e; break; }
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return DS_DEADLINE;   // nothing is freed under a running kernel
-            std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
-    }
-    if (rc == 0)
-        for (Arg &a : args)
-            if (a.out && (e = hipMemcpy(a.out, a.dev, a.bytes, hipMemcpyDeviceToHost)) != hipSuccess) { rc = (int)e; break; }
-    for (Arg &a : args)
-        if (a.dev) (void)hipFree(a.dev);
-    (void)hipStreamDestroy(st);
-    return rc;
-}
-
-bool geometry_ok(int n, int block) { return n > 0 && block >= 64 && block <= MAX_BLOCK && block % 64 == 0; }
 
 // ---- in-kernel conversions ----
 __device__ __forceinline__ F28<1, 1> table_coord(const Fp &v) {   // the stored form of a table coordinate (msm.hip)
@@ -135,8 +74,22 @@ __global__ __launch_bounds__(MAX_BLOCK) void DS(k_field)(int op, uint32_t *out, 
     for (int j = 0; j < 14; j++) out[14 * i + j] = o[j];
 }
 
+// ---- f28_inv_safegcd (fp28_inv.hpp; it ends in an F28 product, so it exists in both forms): one thread per item, 14
+// limbs in and out; lanes past n repeat the last item and store nothing ----
+__global__ __launch_bounds__(MAX_BLOCK) void DS(k_f28_inv)(uint32_t *out, const uint32_t *a, int n) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const bool live = i < (size_t)n;
+    if (!live) i = (size_t)n - 1;
+    F28<1, 2> x;
+    for (int j = 0; j < 14; j++) x.l[j] = a[14 * i + j];
+    const F28<1, 2> y = f28_inv_safegcd(x);
+    if (live)
+        for (int j = 0; j < 14; j++) out[14 * i + j] = y.l[j];
+}
+
 // ---- additions.  kind: 0 xyzz28_add  1 jac28_add  2 xyzz28_madd (b affine)  3 jac28_add_quad  4 jac28_add_quad_zz
-// 5 jac28_madd_quad_zz (b affine)  6 jac28_add_quad_pipe  7 xyzz28_add_quad  8 xyzz28_addsub_quad.
+// 5 jac28_madd_quad_zz (b affine)  6 jac28_add_quad_pipe  7 xyzz28_add_quad  8 xyzz28_addsub_quad
+// 9 xyzz_add (g1.hpp, 32-bit limbs: what k_point_lhs sums its ladder results with).
 // flags bit 0: add -b.  zzok (kinds 4..6): the carried square equals Z^2 of the result. ----
 __global__ __launch_bounds__(MAX_BLOCK) void DS(k_add)(int kind, G1Jac *out, uint8_t *zzok, const G1Jac *a, const G1Jac *b, const uint8_t *flags, int n) {
     int item, ql;
@@ -152,6 +105,9 @@ __global__ __launch_bounds__(MAX_BLOCK) void DS(k_add)(int kind, G1Jac *out, uin
         else if (kind == 7) quad::xyzz28_add_quad(xa, ai, neg ? xyzz28_neg(xb) : xb, bi, ql);
         else quad::xyzz28_addsub_quad(xa, ai, xb, bi, neg, ql);
         r = store_xyzz(xa, ai);
+    } else if (kind == 9) {
+        const G1XYZZ ga = xyzz_from_jac(pa), gb = xyzz_from_jac(pb);
+        r = jac_from_xyzz(xyzz_add(ga, neg ? xyzz_neg(gb) : gb));
     } else if (kind == 2) {
         if (!bi) xyzz28_madd(xa, ai, table_coord(pb.x), cneg_reduced(table_coord(pb.y), neg));
         r = store_xyzz(xa, ai);
@@ -184,7 +140,8 @@ __global__ __launch_bounds__(MAX_BLOCK) void DS(k_add)(int kind, G1Jac *out, uin
     }
 }
 
-// ---- doubling chains.  kind: 0 jac28_dbl  1 jac28_dbl_quad  2 jac28_dbl_quad_zz; steps[i] doublings of a[i] ----
+// ---- doubling chains.  kind: 0 jac28_dbl  1 jac28_dbl_quad  2 jac28_dbl_quad_zz  3 xyzz_dbl (g1.hpp, 32-bit limbs);
+// steps[i] doublings of a[i] ----
 __global__ __launch_bounds__(MAX_BLOCK) void DS(k_dbl)(int kind, G1Jac *out, uint8_t *zzok, const G1Jac *a, const uint32_t *steps, int n) {
     int item, ql;
     const bool live = quad_item(n, item, ql);
@@ -194,8 +151,10 @@ __global__ __launch_bounds__(MAX_BLOCK) void DS(k_dbl)(int kind, G1Jac *out, uin
     F28<1, 2> zz = sqr(ja.z);
     const int ns = (int)(steps[item] < (uint32_t)MAX_CHAIN ? steps[item] : (uint32_t)MAX_CHAIN);
     uint8_t ok = 1;
+    G1XYZZ ga = xyzz_from_jac(a[item]);
     for (int s = 0; s < ns; s++) {
-        if (kind == 0) jac28_dbl(ja);
+        if (kind == 3) ga = xyzz_dbl(ga);
+        else if (kind == 0) jac28_dbl(ja);
         else if (kind == 1) quad::jac28_dbl_quad(ja, ql);
         else {
             quad::jac28_dbl_quad_zz(ja, zz, ql);
@@ -203,7 +162,7 @@ __global__ __launch_bounds__(MAX_BLOCK) void DS(k_dbl)(int kind, G1Jac *out, uin
         }
     }
     if (live) {
-        out[4 * (size_t)item + ql] = store_jac(ja, ai);
+        out[4 * (size_t)item + ql] = kind == 3 ? jac_from_xyzz(ga) : store_jac(ja, ai);
         zzok[4 * (size_t)item + ql] = ok;
     }
 }
@@ -358,10 +317,20 @@ int DS(field)(int op, uint32_t *out, const uint32_t *a, const uint32_t *b, const
     });
 }
 
+int DS(f28_inv)(uint32_t *out, const uint32_t *a, int n, int block) {
+    if (!geometry_ok(n, block)) return DS_BAD_ARG;
+    const size_t bytes = (size_t)n * 14 * 4;
+    std::vector<Arg> args = {{nullptr, out, bytes}, {a, nullptr, bytes}};
+    return run_bounded(args, [&](hipStream_t st) {
+        hipLaunchKernelGGL(DS(k_f28_inv), dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, st, (uint32_t *)args[0].dev,
+                           (const uint32_t *)args[1].dev, n);
+    });
+}
+
 static unsigned quad_grid(int n, int block) { return (unsigned)((4 * (size_t)n + block - 1) / block); }
 
 int DS(g1_add)(int kind, G1Jac *out, uint8_t *zzok, const G1Jac *a, const G1Jac *b, const uint8_t *flags, int n, int block) {
-    if (!geometry_ok(n, block) || kind < 0 || kind > 8) return DS_BAD_ARG;
+    if (!geometry_ok(n, block) || kind < 0 || kind > 9) return DS_BAD_ARG;
     std::vector<Arg> args = {{nullptr, out, 4 * (size_t)n * sizeof(G1Jac)}, {nullptr, zzok, 4 * (size_t)n},
                              {a, nullptr, (size_t)n * sizeof(G1Jac)}, {b, nullptr, (size_t)n * sizeof(G1Jac)}, {flags, nullptr, (size_t)n}};
     return run_bounded(args, [&](hipStream_t st) {
@@ -371,7 +340,7 @@ int DS(g1_add)(int kind, G1Jac *out, uint8_t *zzok, const G1Jac *a, const G1Jac 
 }
 
 int DS(g1_dbl)(int kind, G1Jac *out, uint8_t *zzok, const G1Jac *a, const uint32_t *steps, int n, int block) {
-    if (!geometry_ok(n, block) || kind < 0 || kind > 2) return DS_BAD_ARG;
+    if (!geometry_ok(n, block) || kind < 0 || kind > 3) return DS_BAD_ARG;
     std::vector<Arg> args = {{nullptr, out, 4 * (size_t)n * sizeof(G1Jac)}, {nullptr, zzok, 4 * (size_t)n},
                              {a, nullptr, (size_t)n * sizeof(G1Jac)}, {steps, nullptr, (size_t)n * 4}};
     return run_bounded(args, [&](hipStream_t st) {

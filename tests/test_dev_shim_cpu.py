@@ -1,6 +1,6 @@
 """What can be said about the device test shim (tests/native/dev_shim.hip) and the generated inline-asm product
 without a GPU: libdev_shim.so cross-compiles for gfx950 and exports every ds_plain_* / ds_asm_* pair that
-tests/test_gpu_dev_arith.py binds, both forms and the host shim carry the same list of F28 instantiations, and the
+tests/test_gpu_dev_arith.py binds and the ds_dev_* functions of tests/test_gpu_fields.py, both forms and the host shim carry the same list of F28 instantiations, and the
 committed csrc/fp28_asm_cols.inc is byte for byte what tools/gen_fp28_asm.py emits."""
 import ctypes as C
 import os
@@ -10,7 +10,7 @@ import sys
 import pytest
 
 from conftest import ROOT, SHIM_SO
-from test_gpu_dev_arith import DEV_SHIM_SO, FORMS, SHIM_FUNCTIONS
+from test_gpu_dev_arith import DEV_FUNCTIONS, DEV_SHIM_SO, FORMS, SHIM_FUNCTIONS
 
 PKG = os.path.join(ROOT, "c-kzg-4844_amd")
 
@@ -28,11 +28,13 @@ def test_dev_shim_builds_and_exports_both_forms(dev_shim_path):
     for form in FORMS:
         for fn in SHIM_FUNCTIONS:
             assert "ds_%s_%s" % (form, fn) in names, (form, fn)
+    for fn in DEV_FUNCTIONS:               # tests/native/dev_shim_fields.hip: one plain build
+        assert fn in names, fn
     # the test aid stays out of the product
     if not os.path.exists(os.path.join(PKG, "libckzg_hip.so")):
         subprocess.check_call(["make", "-C", PKG, "-j", "4", "libckzg_hip.so"])
     prod = subprocess.check_output(["nm", "-D", "--defined-only", os.path.join(PKG, "libckzg_hip.so")], text=True)
-    assert "ds_plain_" not in prod and "ds_asm_" not in prod
+    assert "ds_plain_" not in prod and "ds_asm_" not in prod and "ds_dev_" not in prod
 
 
 def test_all_shims_list_the_same_instantiations(dev_shim_path):

@@ -1,6 +1,7 @@
 """The arithmetic only the GPU runs -- the F28 product as the device compiler builds it, its inline-asm form
 (CKZG_F28_ASM_BLOCKS: what msm.hip and fk20.hip run), all of g1_quad.hpp and the straight-line routines of
-g1_pipe.hpp (xyzz28_addsub_quad, jac28_add_quad_pipe, naf2_128, naf_masks) -- fed chosen inputs through tests/native/dev_shim.hip (libdev_shim.so: one source, two builds,
+g1_pipe.hpp (xyzz28_addsub_quad, jac28_add_quad_pipe, naf2_128, naf_masks), f28_inv_safegcd in both forms and g1.hpp's
+complete xyzz_add / xyzz_dbl on 32-bit limbs (what k_point_lhs sums its ladder results with) -- fed chosen inputs through tests/native/dev_shim.hip (libdev_shim.so: one source, two builds,
 ds_plain_* / ds_asm_*) and compared with exact references: Python integers for the field (tests/arith_cases.py,
 no tolerance: the product must equal (a b + q p) >> 392 limb for limb), the CPU oracle for the group law.
 
@@ -37,7 +38,9 @@ DEV_SHIM_SO = os.path.abspath(os.environ["CKZG_DEV_SHIM_SO"]) if os.environ.get(
     os.path.join(ROOT, "c-kzg-4844_amd", "libdev_shim.so")
 FORMS = ["plain", "asm"]
 # every exported function this module binds, once per form (tests/test_dev_shim_cpu.py checks the library for them)
-SHIM_FUNCTIONS = ["f28_ops", "field", "g1_add", "g1_dbl", "g1_mul", "g1_subgroup", "g1_chain", "g1_eat", "g1_reduce", "naf"]
+SHIM_FUNCTIONS = ["f28_ops", "field", "f28_inv", "g1_add", "g1_dbl", "g1_mul", "g1_subgroup", "g1_chain", "g1_eat", "g1_reduce", "naf"]
+# the one plain build of tests/native/dev_shim_fields.hip in the same library (tests/test_gpu_fields.py)
+DEV_FUNCTIONS = ["ds_dev_field_ops", "ds_dev_field"]
 ONE = (pow(2, 384, P)).to_bytes(48, "little")
 INF = bytes(144)
 BLS_X = 0xd201000000010000
@@ -177,10 +180,25 @@ def test_field_corpora(env, form, kind):
     assert ran
 
 
+@pytest.mark.parametrize("form", FORMS)
+def test_f28_inv_safegcd(env, form):
+    """f28_inv_safegcd ends in an F28 product, so it exists in both forms: the inputs of tests/field_cases.py (chosen as
+    the integer that reaches the divsteps, lanes of a wave leaving the loop after different numbers of batches)"""
+    import field_cases as fc
+    _, shim = env
+    items, wants = fc.cached_corpus("f28_inv_safegcd")
+    a = (C.c_uint32 * (14 * len(items)))(*[w for it in items for w in it[0]])
+    for count, block in ((len(items), 256), (fc.SUBSET_LEN, 64)):
+        out = (C.c_uint32 * (14 * len(items)))()
+        shim.call(form, "f28_inv", out, a, count, block)
+        fc.check("f28_inv_safegcd", wants, out, 14, count)
+
+
 # ---- additions ----
 
 ADD_KINDS = {0: "xyzz28_add", 1: "jac28_add", 2: "xyzz28_madd", 3: "jac28_add_quad", 4: "jac28_add_quad_zz",
-             5: "jac28_madd_quad_zz", 6: "jac28_add_quad_pipe", 7: "xyzz28_add_quad", 8: "xyzz28_addsub_quad"}
+             5: "jac28_madd_quad_zz", 6: "jac28_add_quad_pipe", 7: "xyzz28_add_quad", 8: "xyzz28_addsub_quad",
+             9: "xyzz_add"}               # g1.hpp's complete addition on 32-bit limbs: k_point_lhs sums its ladder results with it
 
 
 @pytest.fixture(scope="module")
@@ -206,7 +224,7 @@ def add_cases(env):
 def test_additions(env, add_cases, form, kind):
     grp, shim = env
     cases = add_cases
-    if kind not in (0, 7, 8):          # only the XYZZ forms take a second operand at infinity
+    if kind not in (0, 7, 8, 9):       # only the XYZZ forms take a second operand at infinity
         cases = [c for c in cases if c[1] != INF]
     assert len(cases) >= 37 and len(cases) % 16 != 0
     affine_b = kind in (2, 5)          # the mixed additions take an affine point
@@ -224,7 +242,7 @@ def test_additions(env, add_cases, form, kind):
 
 # ---- doublings ----
 
-DBL_KINDS = {0: "jac28_dbl", 1: "jac28_dbl_quad", 2: "jac28_dbl_quad_zz"}
+DBL_KINDS = {0: "jac28_dbl", 1: "jac28_dbl_quad", 2: "jac28_dbl_quad_zz", 3: "xyzz_dbl"}     # 3: g1.hpp, 32-bit limbs
 
 
 @pytest.fixture(scope="module")
