@@ -130,7 +130,7 @@ ProofSide verify_proof_side(const Fr &z, const G1Jac &proof, const PreparedG2 *p
 bool verify_with_proof_side(const G1Jac &commitment, const Fr &y, const ProofSide &ps, const PreparedG2 *pg) {
     G1Jac lhs = jac_add(jac_add(commitment, jac_neg(g1_gen_mul_fr(y))), ps.zp);
     host::Fp12 f = host::miller_product_prepared(jac_to_affine_fast(lhs), pg->gen, G1Affine::inf(), pg->gen);
-    return host::final_exp(host::mul(f, ps.miller)).is_one();
+    return host::is_one(host::final_exp(host::mul(f, ps.miller)));
 }
 
 bool verify_kzg_proof_impl(const G1Jac &commitment, const Fr &z, const Fr &y, const G1Jac &proof,

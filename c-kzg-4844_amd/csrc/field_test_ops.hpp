@@ -5,9 +5,12 @@
 //                    add / sub / mul that every Fr kernel (ntt.hip, verify.hip) and the whole pairing run
 //   fr29.hpp         Fr on nine 29-bit limbs, operands taken as they come (lazily reduced: limbs below 2^29, the top
 //                    one holding what is left), every K / C / L instantiation the kernels of verify.hip use
-//   fr_inv.hpp, fp28_inv.hpp, fr29_inv   the safegcd inversions
-//   pairing_dev.hpp  the tower, the Frobenius maps, the cyclotomic forms, final_exp and the two-pair Miller product
-//                    against line tables the caller passes in (k_pairing_check)
+//   fp28_inv.hpp, fr_inv.hpp, fr29_inv   the safegcd inversions: one update step and driver loop (fp28_inv.hpp) under
+//                    three repackings (28-, 32- and 29-bit limbs)
+//   tower.hpp        the tower, the Frobenius maps, the cyclotomic forms and final_exp: the ONE text of the host's and
+//                    the device's pairing.  g++ with __int128 takes its lazily reduced 64-bit Fp2 product and square,
+//                    the device compiler and a build with -U__SIZEOF_INT128__ the Karatsuba forms
+//   pairing_dev.hpp  the two-pair Miller product against line tables the caller passes in (k_pairing_check)
 // The list is the single source: every line is  X(name, WO, WA, WB, WC, WD, SHARED, statement)  -- the widths in
 // 32-bit words of the result o and of the operands a, b, c, d (0: unused); SHARED = 1: c and d are the same for every
 // item of a call (the line tables: lam[68] then c[68], Fp2 each, as pairing.hip lays them out).  desc() spells the
@@ -35,7 +38,7 @@
     X(tree_combine_##C##_call, 9, 9, 9, 9, 0, 0, st(o, ev29::tree_combine<C, false>(ld29(a), ld29(b), ld29(c))))   \
     X(tree_combine_##C##_flat, 9, 9, 9, 9, 0, 0, st(o, ev29::tree_combine<C, true>(ld29(a), ld29(b), ld29(c))))
 #define CKZG_FT_TREE_CANONICAL(L) X(tree_canonical_##L, 9, 9, 0, 0, 0, 0, st(o, ev29::tree_canonical<L>(ld29(a))))
-#define CKZG_FT_FROBENIUS(K) X(frobenius_##K, 144, 144, 0, 0, 0, 0, stt(o, pdev::frobenius<K>(ldt<pdev::Fp12>(a))))
+#define CKZG_FT_FROBENIUS(K) X(frobenius_##K, 144, 144, 0, 0, 0, 0, stt(o, tower::frobenius<K>(ldt<tower::Fp12>(a))))
 
 #define CKZG_FIELD_TEST_OPS                                                                                        \
     CKZG_FT_MONT(fp, FpParams, 12, fp_inv)                                                                         \
@@ -65,30 +68,30 @@
     X(fr_inv_safegcd, 8, 8, 0, 0, 0, 0, st(o, fr_inv_safegcd(ldm<FrParams>(a))))                                   \
     X(fr29_inv, 9, 9, 0, 0, 0, 0, st(o, fr29_inv(ld29(a))))                                                        \
     X(f28_inv_safegcd, 14, 14, 0, 0, 0, 0, st28(o, f28_inv_safegcd(ld28(a))))                                      \
-    X(fp2_mul, 24, 24, 24, 0, 0, 0, stt(o, pdev::mul(ldt<pdev::Fp2>(a), ldt<pdev::Fp2>(b))))                       \
-    X(fp2_sqr, 24, 24, 0, 0, 0, 0, stt(o, pdev::sqr(ldt<pdev::Fp2>(a))))                                           \
-    X(fp2_inv, 24, 24, 0, 0, 0, 0, stt(o, pdev::inv(ldt<pdev::Fp2>(a))))                                           \
-    X(fp2_mul_xi, 24, 24, 0, 0, 0, 0, stt(o, pdev::mul_xi(ldt<pdev::Fp2>(a))))                                     \
-    X(fp2_conj, 24, 24, 0, 0, 0, 0, stt(o, pdev::conj(ldt<pdev::Fp2>(a))))                                         \
-    X(fp2_mul_fp, 24, 24, 12, 0, 0, 0, stt(o, pdev::mul_fp(ldt<pdev::Fp2>(a), ldm<FpParams>(b))))                  \
-    X(fp6_mul, 72, 72, 72, 0, 0, 0, stt(o, pdev::mul(ldt<pdev::Fp6>(a), ldt<pdev::Fp6>(b))))                       \
-    X(fp6_inv, 72, 72, 0, 0, 0, 0, stt(o, pdev::inv(ldt<pdev::Fp6>(a))))                                           \
-    X(fp6_mul_v, 72, 72, 0, 0, 0, 0, stt(o, pdev::mul_v(ldt<pdev::Fp6>(a))))                                       \
+    X(fp2_mul, 24, 24, 24, 0, 0, 0, stt(o, tower::mul(ldt<tower::Fp2>(a), ldt<tower::Fp2>(b))))                    \
+    X(fp2_sqr, 24, 24, 0, 0, 0, 0, stt(o, tower::sqr(ldt<tower::Fp2>(a))))                                         \
+    X(fp2_inv, 24, 24, 0, 0, 0, 0, stt(o, tower::inv(ldt<tower::Fp2>(a))))                                         \
+    X(fp2_mul_xi, 24, 24, 0, 0, 0, 0, stt(o, tower::mul_xi(ldt<tower::Fp2>(a))))                                   \
+    X(fp2_conj, 24, 24, 0, 0, 0, 0, stt(o, tower::conj(ldt<tower::Fp2>(a))))                                       \
+    X(fp2_mul_fp, 24, 24, 12, 0, 0, 0, stt(o, tower::mul_fp(ldt<tower::Fp2>(a), ldm<FpParams>(b))))                \
+    X(fp6_mul, 72, 72, 72, 0, 0, 0, stt(o, tower::mul(ldt<tower::Fp6>(a), ldt<tower::Fp6>(b))))                    \
+    X(fp6_inv, 72, 72, 0, 0, 0, 0, stt(o, tower::inv(ldt<tower::Fp6>(a))))                                         \
+    X(fp6_mul_v, 72, 72, 0, 0, 0, 0, stt(o, tower::mul_v(ldt<tower::Fp6>(a))))                                     \
     X(fp6_mul_sparse01, 72, 72, 24, 24, 0, 0,                                                                      \
-      stt(o, pdev::mul_sparse01(ldt<pdev::Fp6>(a), ldt<pdev::Fp2>(b), ldt<pdev::Fp2>(c))))                         \
-    X(fp6_mul_sparse1_fp, 72, 72, 12, 0, 0, 0, stt(o, pdev::mul_sparse1_fp(ldt<pdev::Fp6>(a), ldm<FpParams>(b))))  \
-    X(fp12_mul, 144, 144, 144, 0, 0, 0, stt(o, pdev::mul(ldt<pdev::Fp12>(a), ldt<pdev::Fp12>(b))))                 \
-    X(fp12_sqr, 144, 144, 0, 0, 0, 0, stt(o, pdev::sqr(ldt<pdev::Fp12>(a))))                                       \
-    X(fp12_inv, 144, 144, 0, 0, 0, 0, stt(o, pdev::inv(ldt<pdev::Fp12>(a))))                                       \
-    X(fp12_conj, 144, 144, 0, 0, 0, 0, stt(o, pdev::conj(ldt<pdev::Fp12>(a))))                                     \
-    X(fp12_select, 144, 144, 144, 1, 0, 0, stt(o, pdev::select(c[0], ldt<pdev::Fp12>(a), ldt<pdev::Fp12>(b))))     \
-    X(fp12_is_one, 1, 144, 0, 0, 0, 0, st(o, pdev::is_one(ldt<pdev::Fp12>(a))))                                    \
+      stt(o, tower::mul_sparse01(ldt<tower::Fp6>(a), ldt<tower::Fp2>(b), ldt<tower::Fp2>(c))))                     \
+    X(fp6_mul_sparse1_fp, 72, 72, 12, 0, 0, 0, stt(o, tower::mul_sparse1_fp(ldt<tower::Fp6>(a), ldm<FpParams>(b)))) \
+    X(fp12_mul, 144, 144, 144, 0, 0, 0, stt(o, tower::mul(ldt<tower::Fp12>(a), ldt<tower::Fp12>(b))))              \
+    X(fp12_sqr, 144, 144, 0, 0, 0, 0, stt(o, tower::sqr(ldt<tower::Fp12>(a))))                                     \
+    X(fp12_inv, 144, 144, 0, 0, 0, 0, stt(o, tower::inv(ldt<tower::Fp12>(a))))                                     \
+    X(fp12_conj, 144, 144, 0, 0, 0, 0, stt(o, tower::conj(ldt<tower::Fp12>(a))))                                   \
+    X(fp12_select, 144, 144, 144, 1, 0, 0, stt(o, pdev::select(c[0], ldt<tower::Fp12>(a), ldt<tower::Fp12>(b))))   \
+    X(fp12_is_one, 1, 144, 0, 0, 0, 0, st(o, tower::is_one(ldt<tower::Fp12>(a))))                                  \
     X(fp12_mul_by_prepared_line, 144, 144, 24, 24, 24, 0,                                                          \
-      stt(o, pdev::mul_by_prepared_line(ldt<pdev::Fp12>(a), ldt<pdev::Fp2>(b), ldt<pdev::Fp2>(c), ldt<G1Affine>(d)))) \
+      stt(o, tower::mul_by_prepared_line(ldt<tower::Fp12>(a), ldt<tower::Fp2>(b), ldt<tower::Fp2>(c), ldt<G1Affine>(d)))) \
     CKZG_FT_FROBENIUS(1) CKZG_FT_FROBENIUS(2) CKZG_FT_FROBENIUS(3)                                                 \
-    X(cyclotomic_sqr, 144, 144, 0, 0, 0, 0, stt(o, pdev::cyclotomic_sqr(ldt<pdev::Fp12>(a))))                      \
-    X(pow_x, 144, 144, 0, 0, 0, 0, stt(o, pdev::pow_x(ldt<pdev::Fp12>(a))))                                        \
-    X(final_exp, 144, 144, 0, 0, 0, 0, stt(o, pdev::final_exp(ldt<pdev::Fp12>(a))))                                \
+    X(cyclotomic_sqr, 144, 144, 0, 0, 0, 0, stt(o, tower::cyclotomic_sqr(ldt<tower::Fp12>(a))))                    \
+    X(pow_x, 144, 144, 0, 0, 0, 0, stt(o, tower::pow_x(ldt<tower::Fp12>(a))))                                      \
+    X(final_exp, 144, 144, 0, 0, 0, 0, stt(o, tower::final_exp(ldt<tower::Fp12>(a))))                              \
     X(miller_product_tables, 144, 24, 24, CKZG_FT_TABLE, CKZG_FT_TABLE, 1,                                         \
       stt(o, pdev::miller_product_tables(ldt<G1Affine>(a), table(c), ldt<G1Affine>(b), table(d))))                 \
     X(pairing_product_is_one, 1, 24, 24, CKZG_FT_TABLE, CKZG_FT_TABLE, 1,                                          \
@@ -98,7 +101,7 @@ namespace ckzg {
 namespace fieldtest {
 
 constexpr int MAX_WORDS = 144;   // the widest result or per-item operand (an Fp12)
-static_assert(CKZG_FT_TABLE == 2 * pdev::MILLER_STEPS * 24, "a line table is lam[68] and c[68]");
+static_assert(CKZG_FT_TABLE == 2 * tower::MILLER_STEPS * 24, "a line table is lam[68] and c[68]");
 
 template <class P>
 HD Mont<P> ldm(const uint32_t *p) {
@@ -130,8 +133,8 @@ HD T ldt(const uint32_t *p) {
     return r;
 }
 HD pdev::LineTable table(const uint32_t *p) {
-    const pdev::Fp2 *t = reinterpret_cast<const pdev::Fp2 *>(p);
-    return {t, t + pdev::MILLER_STEPS};
+    const tower::Fp2 *t = reinterpret_cast<const tower::Fp2 *>(p);
+    return {t, t + tower::MILLER_STEPS};
 }
 template <class P>
 HD void st(uint32_t *o, const Mont<P> &v) {

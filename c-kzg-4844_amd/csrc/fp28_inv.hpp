@@ -12,6 +12,10 @@
 // exactly divisible by 2^30 at every update by adding a multiple of p, so no power of two is left
 // over; each update lets |d|, |e| grow by at most p, which 13 x 30 bits absorb for the <= 40
 // batches the iteration can take (768 divsteps suffice for 381-bit inputs; 40*30 = 1200).
+//
+// The update step and the driver loop are written once, for a modulus given as a parameter struct: Fp here, Fr on
+// 9 limbs in fr_inv.hpp (fr_inv_safegcd) and fr29.hpp (fr29_inv).  Each of the three keeps only its own repacking
+// into and out of 30-bit limbs and its own final Montgomery product.
 #pragma once
 #include "fp28.hpp"
 
@@ -85,15 +89,32 @@ HD int32_t divsteps30(int32_t eta, uint32_t f, uint32_t g, DivstepMatrix &t) {
     return eta;
 }
 
+// What the iteration needs of a modulus m on N signed 30-bit limbs: its limbs, 1/m mod 2^30, a multiple K m above the
+// bound on |d| (|d| grows by at most m per batch) and the number of batches that always suffices.
+struct Safegcd30Fp {   // p: 768 divsteps suffice for 381-bit inputs; |d| < 41 p, and 13 x 30 bits hold it
+    static constexpr int N = 13, MAXIT = 40;
+    static constexpr uint32_t MINV = FP30_PINV;
+    HD static constexpr int32_t mod(int i) { return FP30_P[i]; }
+    HD static constexpr int32_t kmod(int i) { return FP30_64P[i]; }
+};
+struct Safegcd30Fr {   // r: 738 divsteps suffice for 255-bit inputs; |d| < 27 r, and 9 x 30 bits hold 2^14 r
+    static constexpr int N = 9, MAXIT = 26;
+    static constexpr uint32_t MINV = FR30_RINV;
+    HD static constexpr int32_t mod(int i) { return FR30_R[i]; }
+    HD static constexpr int32_t kmod(int i) { return FR30_32R[i]; }
+};
+
 // (f, g) <- t * (f, g) / 2^30, exact
+template <class P>
 HD void update_fg30(int32_t *f, int32_t *g, const DivstepMatrix &t) {
+    constexpr int N = P::N;
     const int64_t M = (1 << 30) - 1;
     int64_t cf = (int64_t)t.u * f[0] + (int64_t)t.v * g[0];
     int64_t cg = (int64_t)t.q * f[0] + (int64_t)t.r * g[0];
     cf >>= 30;
     cg >>= 30;
 #pragma unroll
-    for (int i = 1; i < 13; i++) {
+    for (int i = 1; i < N; i++) {
         cf += (int64_t)t.u * f[i] + (int64_t)t.v * g[i];
         cg += (int64_t)t.q * f[i] + (int64_t)t.r * g[i];
         f[i - 1] = limb32((int32_t)(cf & M));
@@ -101,32 +122,66 @@ HD void update_fg30(int32_t *f, int32_t *g, const DivstepMatrix &t) {
         cf >>= 30;
         cg >>= 30;
     }
-    f[12] = limb32((int32_t)cf);
-    g[12] = limb32((int32_t)cg);
+    f[N - 1] = limb32((int32_t)cf);
+    g[N - 1] = limb32((int32_t)cg);
 }
 
-// (d, e) <- t * (d, e) / 2^30 mod p: a multiple of p makes the low 30 bits vanish first
+// (d, e) <- t * (d, e) / 2^30 mod m: a multiple of m makes the low 30 bits vanish first
+template <class P>
 HD void update_de30(int32_t *d, int32_t *e, const DivstepMatrix &t) {
     const int64_t M = (1 << 30) - 1;
     int64_t cd = (int64_t)t.u * d[0] + (int64_t)t.v * e[0];
     int64_t ce = (int64_t)t.q * d[0] + (int64_t)t.r * e[0];
-    const int32_t md = (int32_t)(((0u - (uint32_t)cd) * (uint32_t)FP30_PINV) & (uint32_t)M);
-    const int32_t me = (int32_t)(((0u - (uint32_t)ce) * (uint32_t)FP30_PINV) & (uint32_t)M);
-    cd += (int64_t)FP30_P[0] * md;
-    ce += (int64_t)FP30_P[0] * me;
+    const int32_t md = (int32_t)(((0u - (uint32_t)cd) * P::MINV) & (uint32_t)M);
+    const int32_t me = (int32_t)(((0u - (uint32_t)ce) * P::MINV) & (uint32_t)M);
+    cd += (int64_t)P::mod(0) * md;
+    ce += (int64_t)P::mod(0) * me;
     cd >>= 30;
     ce >>= 30;
 #pragma unroll
-    for (int i = 1; i < 13; i++) {
-        cd += (int64_t)t.u * d[i] + (int64_t)t.v * e[i] + (int64_t)FP30_P[i] * md;
-        ce += (int64_t)t.q * d[i] + (int64_t)t.r * e[i] + (int64_t)FP30_P[i] * me;
+    for (int i = 1; i < P::N; i++) {
+        cd += (int64_t)t.u * d[i] + (int64_t)t.v * e[i] + (int64_t)P::mod(i) * md;
+        ce += (int64_t)t.q * d[i] + (int64_t)t.r * e[i] + (int64_t)P::mod(i) * me;
         d[i - 1] = limb32((int32_t)(cd & M));
         e[i - 1] = limb32((int32_t)(ce & M));
         cd >>= 30;
         ce >>= 30;
     }
-    d[12] = limb32((int32_t)cd);
-    e[12] = limb32((int32_t)ce);
+    d[P::N - 1] = limb32((int32_t)cd);
+    e[P::N - 1] = limb32((int32_t)ce);
+}
+
+// The iteration itself: g = x != 0 (mod m) as 30-bit limbs (clobbered); w = 1/x mod m as a positive integer, in 30-bit
+// words with the top one holding what is left.  Batches of 30 divsteps until g = 0; then f = +1 or -1 and the result is
+// f * d, made positive by adding K m.  |d| < (MAXIT + 1) m, so w < K m + (MAXIT + 1) m: 105 p for p, 59 r for r.
+template <class P>
+HD void safegcd30(uint32_t *w, int32_t *g) {
+    constexpr int N = P::N;
+    int32_t f[N], d[N], e[N];
+    for (int i = 0; i < N; i++) {
+        f[i] = P::mod(i);
+        d[i] = 0;
+        e[i] = 0;
+    }
+    e[0] = 1;
+    int32_t eta = -1;
+    for (int it = 0; it < P::MAXIT; it++) {
+        DivstepMatrix t;
+        eta = divsteps30(eta, (uint32_t)f[0], (uint32_t)g[0], t);
+        update_de30<P>(d, e, t);
+        update_fg30<P>(f, g, t);
+        int32_t nz = 0;
+        for (int i = 0; i < N; i++) nz |= g[i];
+        if (nz == 0) break;
+    }
+    const bool negate = f[N - 1] < 0;
+    int64_t c = 0;
+    for (int i = 0; i < N; i++) {
+        c += (int64_t)P::kmod(i) + (negate ? -(int64_t)d[i] : (int64_t)d[i]);
+        w[i] = (uint32_t)(c & 0x3fffffff);
+        c >>= 30;
+    }
+    w[N - 1] += (uint32_t)(c << 30);
 }
 
 // 1/a in the 2^392 Montgomery domain; 0 for a == 0 (mod p), like the Fermat ladder
@@ -136,7 +191,7 @@ HDNI inline F28<1, 2> f28_inv_safegcd(const F28<1, 2> &a) {
         for (int j = 0; j < 14; j++) z.l[j] = 0;
         return z;
     }
-    int32_t f[13], g[13], d[13], e[13];
+    int32_t g[13];
     // 14 x 28-bit limbs (value < 2p < 2^382) -> 13 x 30-bit limbs
     for (int i = 0; i < 13; i++) {
         int bit = 30 * i, j = bit / 28, sh = bit - 28 * j;
@@ -144,31 +199,9 @@ HDNI inline F28<1, 2> f28_inv_safegcd(const F28<1, 2> &a) {
         if (j + 1 < 14) v |= a.l[j + 1] << (28 - sh);
         if (28 - sh + 28 < 30 && j + 2 < 14) v |= a.l[j + 2] << (56 - sh);
         g[i] = (int32_t)(v & 0x3fffffffu);
-        f[i] = FP30_P[i];
-        d[i] = 0;
-        e[i] = 0;
     }
-    e[0] = 1;
-    int32_t eta = -1;
-    for (int it = 0; it < 40; it++) {
-        DivstepMatrix t;
-        eta = divsteps30(eta, (uint32_t)f[0], (uint32_t)g[0], t);
-        update_de30(d, e, t);
-        update_fg30(f, g, t);
-        int32_t nz = 0;
-        for (int i = 0; i < 13; i++) nz |= g[i];
-        if (nz == 0) break;
-    }
-    // f = +1 or -1; result = f * d, made positive by adding 64p (|d| < 41p)
-    const bool negate = f[12] < 0;
-    int64_t c = 0;
-    uint32_t w[13];
-    for (int i = 0; i < 13; i++) {
-        c += (int64_t)FP30_64P[i] + (negate ? -(int64_t)d[i] : (int64_t)d[i]);
-        w[i] = (uint32_t)(c & 0x3fffffff);
-        c >>= 30;
-    }
-    w[12] += (uint32_t)(c << 30);  // value < 105p < 2^388: the top word holds what is left
+    uint32_t w[13];   // below 105p < 2^388
+    safegcd30<Safegcd30Fp>(w, g);
     // 13 x 30 -> 14 x 28
     F28<1, 128> y;
     for (int j = 0; j < 14; j++) {

@@ -162,38 +162,17 @@ HD Fr fr29_to_fr(const Fr29 &x) {
 
 // 2^261 / x for a canonical x 2^261 != 0 (safegcd, fr_inv.hpp's iteration on the same 30-bit limbs); below 2 r
 HDNI inline Fr29 fr29_inv(const Fr29 &a) {
-    int32_t f[9], g[9], d[9], e[9];
+    int32_t g[9];
     for (int i = 0; i < 9; i++) {
         const int bit = 30 * i, j = bit / 29, sh = bit - 29 * j;
         uint32_t v = a.l[j] >> sh;
         if (j + 1 < 9) v |= a.l[j + 1] << (29 - sh);
         if (29 - sh + 29 < 30 && j + 2 < 9) v |= a.l[j + 2] << (58 - sh);
         g[i] = (int32_t)(v & 0x3fffffffu);
-        f[i] = FR30_R[i];
-        d[i] = 0;
-        e[i] = 0;
     }
-    e[0] = 1;
-    int32_t eta = -1;
-    for (int it = 0; it < 26; it++) {
-        DivstepMatrix t;
-        eta = divsteps30(eta, (uint32_t)f[0], (uint32_t)g[0], t);
-        fr_update_de30(d, e, t);
-        fr_update_fg30(f, g, t);
-        int32_t nz = 0;
-        for (int i = 0; i < 9; i++) nz |= g[i];
-        if (nz == 0) break;
-    }
-    // f = +-1; f * d made positive by adding 32 r (|d| < 27 r): y = 1/(x 2^261) as an integer below 59 r < 2^261
-    const bool negate = f[8] < 0;
-    int64_t c = 0;
+    // y = 1/(x 2^261) as an integer below 59 r < 2^261
     uint32_t w[9];
-    for (int i = 0; i < 9; i++) {
-        c += (int64_t)FR30_32R[i] + (negate ? -(int64_t)d[i] : (int64_t)d[i]);
-        w[i] = (uint32_t)(c & 0x3fffffff);
-        c >>= 30;
-    }
-    w[8] += (uint32_t)(c << 30);
+    safegcd30<Safegcd30Fr>(w, g);
     Fr29 y;
     for (int j = 0; j < 9; j++) {
         const int bit = 29 * j, i = bit / 30, sh = bit - 30 * i;

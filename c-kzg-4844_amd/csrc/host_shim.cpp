@@ -4,7 +4,6 @@
 // libckzg_hip.so.
 #include <vector>
 #include "host_pairing.hpp"
-#include "pairing_dev.hpp"
 using namespace ckzg;
 using namespace ckzg::host;
 
@@ -271,7 +270,7 @@ extern "C" int hs_bench_pairing(const G1Jac *a1, const G2Jac *q1, const G1Jac *a
 extern "C" int hs_bench_final_exp(const G1Jac *a1, const G2Jac *q1, int n) {
     Fp12 f = miller_loop(g2_to_affine(*q1), jac_to_affine(*a1));
     int ones = 0;
-    for (int i = 0; i < n; i++) ones += final_exp(f).is_one() ? 1 : 0;
+    for (int i = 0; i < n; i++) ones += is_one(final_exp(f)) ? 1 : 0;
     return ones;
 }
 extern "C" void hs_bench_fp_mul(Fp *r, const Fp *a, const Fp *b, int n) {
@@ -320,7 +319,7 @@ extern "C" int hs_fp12_selftest(uint32_t seed) {
         if (!same(mul_by_prepared_line(f, lam, c, p), mul(f, l))) bad |= 2;
     }
     Fp12 a = mul(conj(f), inv(f));
-    a = mul(frobenius(a, 2), a);  // in the cyclotomic subgroup
+    a = mul(frobenius<2>(a), a);  // in the cyclotomic subgroup
     if (!same(cyclotomic_sqr(a), mul(a, a))) bad |= 4;
     if (same(cyclotomic_sqr(f), mul(f, f))) bad |= 8;
     // bit 4: the lazily reduced Fp2 product and square against the schoolbook formulas on Fp
@@ -353,7 +352,7 @@ extern "C" int hs_pairing_split(const G1Jac *a1, const G2Jac *q1, const G1Jac *a
     const G1Affine x1 = jac_to_affine(*a1), x2 = jac_to_affine(*a2);
     const Fp12 early = miller_product_prepared(x2, p2, G1Affine::inf(), p2);
     const Fp12 late = miller_product_prepared(x1, p1, G1Affine::inf(), p1);
-    const bool split = final_exp(mul(late, early)).is_one();
+    const bool split = is_one(final_exp(mul(late, early)));
     const bool fused = pairing_product_is_one(x1, p1, x2, p2);
     return (split ? 1 : 0) | ((split == fused) ? 2 : 0);
 }
@@ -564,46 +563,19 @@ extern "C" void hs_fr29_eval_tree(Fr *y, const Fr *poly, const Fr *z, const Fr *
     else eval_tree_emulate<4>(y, poly, z, brp_roots);
 }
 
-// pairing_dev.hpp (the per-lane pairing of pairing.hip: k_pairing_check) against host_pairing.hpp.  Fp12 values are
-// 576-byte Montgomery limb arrays, identical in both headers' layouts.
-static_assert(sizeof(pdev::Fp12) == sizeof(Fp12), "Fp12 layouts");
-static_assert(sizeof(pdev::Fp2) == sizeof(Fp2), "Fp2 layouts");
+// The host's pairing (host_pairing.hpp on tower.hpp, here with the lazily reduced 64-bit Fp2 forms) for
+// tests/test_point_pairing_host.py, which holds the 32-bit-body build of the same tower and the device's Miller product
+// (libfield32_shim.so) to it byte for byte.  Fp12 values are 576-byte Montgomery limb arrays.
 extern "C" {
-void hs_pd_final_exp(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::final_exp(*f); }
 void hs_host_final_exp(Fp12 *r, const Fp12 *f) { *r = final_exp(*f); }
-void hs_pd_fp12_inv(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::inv(*f); }
 void hs_host_fp12_inv(Fp12 *r, const Fp12 *f) { *r = inv(*f); }
-void hs_pd_fp12_mul(pdev::Fp12 *r, const pdev::Fp12 *a, const pdev::Fp12 *b) { *r = pdev::mul(*a, *b); }
 void hs_host_fp12_mul(Fp12 *r, const Fp12 *a, const Fp12 *b) { *r = mul(*a, *b); }
-void hs_pd_fp12_sqr(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::sqr(*f); }
-void hs_pd_cyclotomic_sqr(pdev::Fp12 *r, const pdev::Fp12 *f) { *r = pdev::cyclotomic_sqr(*f); }
-// the easy part f^((p^6-1)(p^2+1)): an element of the cyclotomic subgroup
-void hs_pd_easy_part(pdev::Fp12 *r, const pdev::Fp12 *f) {
-    const pdev::Fp12 a = pdev::mul(pdev::conj(*f), pdev::inv(*f));
-    *r = pdev::mul(pdev::frobenius<2>(a), a);
-}
-int hs_pd_is_one(const pdev::Fp12 *f) { return pdev::is_one(*f) ? 1 : 0; }
-// Miller product and full two-pair check with G2 arguments prepared by host_pairing.hpp's g2_prepare
-static pdev::LineTable pd_table(const G2Prepared &q) {
-    return {reinterpret_cast<const pdev::Fp2 *>(q.lam), reinterpret_cast<const pdev::Fp2 *>(q.c)};
-}
-void hs_pd_miller(pdev::Fp12 *r, const G1Jac *a1, const G2Jac *q1, const G1Jac *a2, const G2Jac *q2) {
-    G2Prepared p1, p2;
-    g2_prepare(p1, g2_to_affine(*q1));
-    g2_prepare(p2, g2_to_affine(*q2));
-    *r = pdev::miller_product_tables(jac_to_affine(*a1), pd_table(p1), jac_to_affine(*a2), pd_table(p2));
-}
+// Miller product with G2 arguments prepared by g2_prepare
 void hs_host_miller(Fp12 *r, const G1Jac *a1, const G2Jac *q1, const G1Jac *a2, const G2Jac *q2) {
     G2Prepared p1, p2;
     g2_prepare(p1, g2_to_affine(*q1));
     g2_prepare(p2, g2_to_affine(*q2));
     *r = miller_product_prepared(jac_to_affine(*a1), p1, jac_to_affine(*a2), p2);
-}
-int hs_pd_pairing_check(const G1Jac *a1, const G2Jac *q1, const G1Jac *a2, const G2Jac *q2) {
-    G2Prepared p1, p2;
-    g2_prepare(p1, g2_to_affine(*q1));
-    g2_prepare(p2, g2_to_affine(*q2));
-    return pdev::pairing_product_is_one(jac_to_affine(*a1), pd_table(p1), jac_to_affine(*a2), pd_table(p2)) ? 1 : 0;
 }
 }
 

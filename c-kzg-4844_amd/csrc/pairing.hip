@@ -4,7 +4,7 @@
 //     (ckzg_api2.hip: verify_kzg_proof_impl), from the validated points and the 32-byte scalars; an invalid item is
 //     replaced by infinity and zero scalars before any arithmetic, so it cannot reach another lane's result
 //   * k_pairing_check: that two-pairing check per lane against the line tables of [1]_2 and [s]_2
-//     (pairing_dev.hpp), one verdict byte per item.
+//     (pairing_dev.hpp on the tower of tower.hpp), one verdict byte per item.
 // Host glue: ckzg_api2.hip, verify_point_proofs_on.
 #include "device.hpp"
 #include "g1_28.hpp"

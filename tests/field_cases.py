@@ -1,9 +1,10 @@
 """Corpora and exact references for the operations of c-kzg-4844_amd/csrc/field_test_ops.hpp: Mont<Fp> / Mont<Fr>
-(field.hpp), Fr on 29-bit limbs (fr29.hpp), the safegcd inversions (fr_inv.hpp, fp28_inv.hpp, fr29_inv) and the pairing
-tower (pairing_dev.hpp, against tests/tower_ref.py).  Seeded and deterministic; every comparison is exact equality of
-words, or -- where a routine's result is lazily reduced and its representative is the routine's own business (fr29_inv,
-f28_inv_safegcd) -- exact congruence plus the bound its header states.  tests/test_field_corpora_cpu.py runs the
-corpora through the g++ build, tests/test_gpu_fields.py through the device build.
+(field.hpp), Fr on 29-bit limbs (fr29.hpp), the safegcd inversions (fp28_inv.hpp, fr_inv.hpp, fr29_inv) and the pairing
+tower (tower.hpp, pairing_dev.hpp, against tests/tower_ref.py).  Seeded and deterministic; every comparison is exact
+equality of words, or -- where a routine's result is lazily reduced and its representative is the routine's own
+business (fr29_inv, f28_inv_safegcd) -- exact congruence plus the bound its header states.
+tests/test_field_corpora_cpu.py runs the corpora through the g++ build, tests/test_gpu_fields.py through the device
+build.
 
 A corpus is (items, wants): items[i] = the operands (a, b, c, d) of item i as lists of 32-bit words (None: unused),
 wants[i] = the expected result words, or a function of the result words that asserts."""
@@ -678,9 +679,10 @@ _PAIRING = {}
 
 def pairing_corpus(name, h):
     """One call = one pair of tables ([b]G2, G2).  miller_product_tables: item 0 is e(G1, G2) through the second slot,
-    the others e([a]G1, [b]G2) through the first, one with both slots finite; wants = host_pairing.hpp's value byte
-    for byte, and check_miller_relation ties them together by the Python tower alone.  pairing_product_is_one: the
-    case list of test_two_pair_verdicts_match_host, 37 items, infinite and finite arguments mixed in both slots."""
+    the others e([a]G1, [b]G2) through the first, one with both slots finite; wants = the value of host_pairing.hpp's
+    branching Miller product in libhost_shim.so byte for byte, and check_miller_relation ties them together by the
+    Python tower alone.  pairing_product_is_one: the case list of test_two_pair_verdicts_match_host, 37 items, infinite
+    and finite arguments mixed in both slots."""
     if name in _PAIRING:
         return _PAIRING[name]
     pi = PairingInputs(h)

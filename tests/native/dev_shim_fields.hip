@@ -1,8 +1,9 @@
 // dev_shim_fields.hip -- the device forms of field_test_ops.hpp behind a C ABI: Mont<Fp> / Mont<Fr> on the 32-bit CIOS,
-// Fr29 (the called product fr29_mul_regs among it), the safegcd inversions and the pairing tower of pairing_dev.hpp with
-// its out-of-line products, as the DEVICE compiler builds them.  Compiled ONCE, with the product's plain flags -- what
-// pairing.o, verify.o and ntt.o are built with -- and linked into libdev_shim.so next to dev_shim.hip's two forms; its
-// exports are ds_dev_*.  Test aid only (tests/test_gpu_fields.py); never part of libckzg_hip.so.
+// Fr29 (the called product fr29_mul_regs among it), the safegcd inversions and the pairing tower of tower.hpp /
+// pairing_dev.hpp with its out-of-line products, as the DEVICE compiler builds them.  Compiled ONCE, with the product's
+// plain flags -- what pairing.o, verify.o and ntt.o are built with -- and linked into libdev_shim.so next to
+// dev_shim.hip's two forms; its exports are ds_dev_*.  Test aid only (tests/test_gpu_fields.py); never part of
+// libckzg_hip.so.
 //
 // The rules of dev_shim.hip hold: host pointers in, ONE kernel per call on a stream of its own, a polling 20 s
 // deadline (dev_shim_common.hpp), bounded loops only.  Geometry: one thread per item in workgroups of `block` threads;

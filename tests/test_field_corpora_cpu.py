@@ -1,13 +1,15 @@
 """Every operation of c-kzg-4844_amd/csrc/field_test_ops.hpp as g++ builds it (libhost_shim.so: hs_field_run), on the
 corpora of tests/field_cases.py against their exact references: Mont<Fp> / Mont<Fr> at the edge values, Fr29 on lazily
 reduced operands at the bounds fr29.hpp states, the safegcd inversions on inputs chosen as the integer that reaches the
-divsteps, and the pairing tower of pairing_dev.hpp against the Python tower of tests/tower_ref.py, which shares no code
-with host_pairing.hpp.  This validates the corpora and the references without a GPU; tests/test_gpu_fields.py runs
+divsteps, and the pairing tower of tower.hpp against the Python tower of tests/tower_ref.py, which shares no code
+with it.  This validates the corpora and the references without a GPU; tests/test_gpu_fields.py runs
 the same lists through the device build.
 
 Two host builds run every list: libhost_shim.so, where g++ takes the 64-bit-limb bodies of Mont's add / sub / mul, and
 libfield32_shim.so (tests/native/field32_shim.cpp, -U__SIZEOF_INT128__), where it takes the 32-bit CIOS bodies that
-the device compiler takes -- so a wrong carry there shows without a GPU, the tower on top of it included."""
+the device compiler takes -- so a wrong carry there shows without a GPU, the tower on top of it included.  The tower's
+Fp2 product and square differ the same way: the lazily reduced 64-bit forms in the first build, Karatsuba in the
+second."""
 import ctypes as C
 import os
 import subprocess

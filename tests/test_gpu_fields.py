@@ -1,9 +1,9 @@
 """The other half of what only the device compiler builds -- Mont<Fp> / Mont<Fr> on the 32-bit CIOS (field.hpp: what
 every Fr kernel and the whole pairing run), Fr29 with its called product fr29_mul_regs, the safegcd inversions with
-their device-only lines, and the pairing tower of pairing_dev.hpp with its out-of-line products -- fed the corpora of
-tests/field_cases.py through tests/native/dev_shim_fields.hip (libdev_shim.so: ds_dev_field, one plain build) and
-compared with the exact references that tests/test_field_corpora_cpu.py validates on the host: Python integers, and
-the Python tower of tests/tower_ref.py.  No tolerance anywhere.
+their device-only lines, and the pairing tower of tower.hpp / pairing_dev.hpp with its out-of-line products -- fed the
+corpora of tests/field_cases.py through tests/native/dev_shim_fields.hip (libdev_shim.so: ds_dev_field, one plain
+build) and compared with the exact references that tests/test_field_corpora_cpu.py validates on the host: Python
+integers, and the Python tower of tests/tower_ref.py.  No tolerance anywhere.
 
 Geometry.  One thread per item; lanes past the end repeat the last item and store nothing.  Every list runs twice:
 whole, in workgroups of 256, and its first 101 items in workgroups of 64, which leaves a wave with 37 live lanes.

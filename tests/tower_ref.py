@@ -2,8 +2,8 @@
     Fp2 = Fp[u]/(u^2 + 1),  Fp6 = Fp2[v]/(v^3 - (1 + u)),  Fp12 = Fp6[w]/(w^2 - v)
 Schoolbook products, no Karatsuba, no sparse forms, no Frobenius constants, no cyclotomic shortcut: a power is square
 and multiply, the Frobenius map is f -> f^(p^K) computed as that power, the final exponentiation is the power
-3 (p^12 - 1)/r.  It is the independent reference for c-kzg-4844_amd/csrc/pairing_dev.hpp (tests/test_field_corpora_cpu.py,
-tests/test_gpu_fields.py); nothing here is taken from host_pairing.hpp.
+3 (p^12 - 1)/r.  It is the independent reference for c-kzg-4844_amd/csrc/tower.hpp (tests/test_field_corpora_cpu.py,
+tests/test_gpu_fields.py); nothing here is taken from it.
 
 An Fp2 is a pair of integers below p, an Fp6 a triple of Fp2, an Fp12 a pair of Fp6.  On the wire an Fp is twelve
 32-bit words of x 2^384 mod p, least significant first, and a tower element its coefficients in order."""
