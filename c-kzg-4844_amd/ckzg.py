@@ -335,6 +335,36 @@ class Kzg:
             raise KzgError("ckzg_hip_verify_cell_kzg_proof_batch_groups -> C_KZG_RET %d" % ret)
         return [bool(v) for v in ok[:g]], [int(v) for v in st[:g]]
 
+    def verify_blob_cell_kzg_proof_batch_groups(self, groups):
+        """ckzg_hip_verify_blob_cell_kzg_proof_batch_groups: per group, compute_cells of every blob and one
+        verify_cell_kzg_proof_batch over all their cells, in one call.  groups is a list of (blobs, commitments,
+        cell_proofs) tuples, cell_proofs the flat list of 128 * len(blobs) proofs (blob i owns [128 i, 128 i + 128)).
+        Returns (ok, status): ok[g] is the group's verdict and status[g] its C_KZG_RET (1 = C_KZG_BADARGS: invalid
+        point or field element)."""
+        g = len(groups)
+        start = [0]
+        flat = ([], [], [])
+        for grp in groups:
+            _check(len(grp) == 3, "a group is (blobs, commitments, cell_proofs)")
+            blobs, commitments, cell_proofs = grp
+            n = len(blobs)
+            _check(len(commitments) == n and len(cell_proofs) == CELLS_PER_EXT_BLOB * n, "list lengths")
+            for b in blobs:
+                _check(len(b) == BYTES_PER_BLOB, "blob")
+            for c in list(commitments) + list(cell_proofs):
+                _check(len(c) == 48, "commitment/proof")
+            for dst, src in zip(flat, grp):
+                dst.extend(src)
+            start.append(start[-1] + n)
+        ok = (C.c_bool * max(g, 1))()
+        st = (C.c_uint8 * max(g, 1))()
+        ret = self._fn("ckzg_hip_verify_blob_cell_kzg_proof_batch_groups")(
+            ok, st, b"".join(flat[0]), b"".join(flat[1]), b"".join(flat[2]), (C.c_uint64 * (g + 1))(*start), C.c_uint64(g),
+            self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_verify_blob_cell_kzg_proof_batch_groups -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:g]], [int(v) for v in st[:g]]
+
     # ---- test-exposed internals (src/eip4844/eip4844.h:84, src/eip7594/eip7594.h:59-68) ----
     def compute_challenge(self, blob, commitment):
         _check(len(blob) == BYTES_PER_BLOB, "blob")

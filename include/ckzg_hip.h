@@ -239,6 +239,37 @@ C_KZG_RET ckzg_hip_verify_blob_kzg_proof_batch_groups(bool *ok, uint8_t *status,
                                                       const uint64_t *group_start, uint64_t num_groups,
                                                       const KZGSettings *s);
 
+/* Blobs against their CELL proofs (EIP-7594: a blob transaction on the wire carries its blobs, its commitments and
+ * 128 cell proofs per blob) over num_groups independent batches in one call, one verdict per group -- a transaction
+ * pool that must know WHICH transaction to drop.  Host pointers.  blobs and commitments_bytes are flat,
+ * group_start[num_groups] entries long; cell_proofs_bytes is 128 times that, blob i owns [128 i, 128 i + 128); group g
+ * is the blobs [group_start[g], group_start[g + 1]) = [a, b).  group_start has num_groups + 1 entries, starts at 0 and
+ * does not decrease.  For every g, (status[g], ok[g]) is exactly what the reference functions give when composed on
+ * the slice:
+ *   compute_cells_and_kzg_proofs(cells_i, NULL, &blobs[i], s) for every i in [a, b), then
+ *   verify_cell_kzg_proof_batch(&ok, C', idx', cells', cell_proofs_bytes + 128 a, 128 (b - a), s)
+ * with C'[128 (i - a) + k] = commitments_bytes[i] and idx'[128 (i - a) + k] = k: status[g] is the first return value
+ * of that sequence that is not C_KZG_OK, ok[g] the verdict, or false when the status is not OK.  An empty group is
+ * true with status 0; a non-canonical field element in a blob, or a commitment or proof that is not a valid G1 point,
+ * gives that group status 1 (C_KZG_BADARGS) and ok = false and says nothing about the other groups, whose verdicts
+ * are still computed and written.  Every group has the reference's challenge for its slice (eip7594.c:390-482,
+ * commitments deduplicated within the group, its own transcript); no randomness is shared between groups, and every
+ * valid group gets its own pairing check.  The cells are made on the device and stay there: only their bytes visit
+ * the host (page-locked staging), for the transcript hash.
+ * Returns C_KZG_BADARGS if any group is invalid, or if group_start is malformed (first entry not 0, or decreasing:
+ * nothing is written then); C_KZG_OK otherwise; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  status may be
+ * NULL; num_groups == 0 is C_KZG_OK and writes nothing.
+ * Whole groups are the unit of work: several devices take contiguous runs of groups, and on a device the groups are
+ * processed, one chunk after another, in chunks of at most CKZG_HIP_BLOB_CELL_GROUPS_CHUNK_BLOBS blobs and
+ * CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS groups; a group is never cut.  A chunk of one group -- a call of one group, or a
+ * group larger than a chunk -- has its cells made in sub-batches of at most a chunk of blobs, staged in page-locked
+ * memory (256 KB per blob), and goes through the single-batch path. */
+#define CKZG_HIP_BLOB_CELL_GROUPS_CHUNK_BLOBS 128   /* = CKZG_HIP_CELL_GROUPS_CHUNK_CELLS / 128 */
+C_KZG_RET ckzg_hip_verify_blob_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Blob *blobs,
+                                                           const Bytes48 *commitments_bytes,
+                                                           const Bytes48 *cell_proofs_bytes, const uint64_t *group_start,
+                                                           uint64_t num_groups, const KZGSettings *s);
+
 /* verify_blob_kzg_proof_batch (src/eip4844/eip4844.c:775-844) with blobs, commitments and proofs resident in HBM
  * (device pointers on one GPU: n Blob, n Bytes48, n Bytes48).  Point validation, bytes -> field elements, the
  * Fiat-Shamir challenges (SHA-256 of every blob, on the GPU), the evaluations and the three random-linear-combination
