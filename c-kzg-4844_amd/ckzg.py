@@ -153,6 +153,53 @@ class Kzg:
             raise KzgError("ckzg_hip_verify_kzg_proof_batch -> C_KZG_RET %d" % ret)
         return [bool(v) for v in ok[:n]], [int(v) for v in st[:n]]
 
+    def verify_kzg_proof_batch_locate(self, commitments, zs, ys, proofs):
+        """ckzg_hip_verify_kzg_proof_batch_locate: the verdicts of verify_kzg_proof_batch at the cost of one batch check
+        when everything verifies; a failing batch is bisected on prefix sums.  Returns (ok, status, stats): stats =
+        [host range checks, items settled by the per-lane GPU check, chunks]."""
+        n = len(commitments)
+        _check(len(zs) == n and len(ys) == n and len(proofs) == n, "list lengths")
+        for c in list(commitments) + list(proofs):
+            _check(len(c) == 48, "commitment/proof")
+        for x in list(zs) + list(ys):
+            _check(len(x) == 32, "z/y")
+        ok = (C.c_bool * max(n, 1))()
+        st = (C.c_uint8 * max(n, 1))()
+        stats = (C.c_uint64 * 3)()
+        ret = self._fn("ckzg_hip_verify_kzg_proof_batch_locate")(
+            ok, st, stats, b"".join(commitments), b"".join(zs), b"".join(ys), b"".join(proofs), C.c_uint64(n), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_verify_kzg_proof_batch_locate -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:n]], [int(v) for v in st[:n]], [int(v) for v in stats]
+
+    def verify_blob_kzg_proof_batch_locate(self, blobs, commitments, proofs):
+        """ckzg_hip_verify_blob_kzg_proof_batch_locate: one verify_blob_kzg_proof verdict per blob at the cost of one
+        batch check when everything verifies.  Returns (ok, status, stats) as verify_kzg_proof_batch_locate does."""
+        n = len(blobs)
+        _check(len(commitments) == n and len(proofs) == n, "list lengths")
+        for b in blobs:
+            _check(len(b) == BYTES_PER_BLOB, "blob")
+        for c in list(commitments) + list(proofs):
+            _check(len(c) == 48, "commitment/proof")
+        ok = (C.c_bool * max(n, 1))()
+        st = (C.c_uint8 * max(n, 1))()
+        stats = (C.c_uint64 * 3)()
+        ret = self._fn("ckzg_hip_verify_blob_kzg_proof_batch_locate")(
+            ok, st, stats, b"".join(blobs), b"".join(commitments), b"".join(proofs), C.c_uint64(n), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_verify_blob_kzg_proof_batch_locate -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:n]], [int(v) for v in st[:n]], [int(v) for v in stats]
+
+    def g1_prefix_sums(self, points):
+        """ckzg_hip_g1_prefix_sums: out[i] = points[0] + ... + points[i], each a g1_t (144 bytes, Jacobian) in and out."""
+        n = len(points)
+        for p in points:
+            _check(len(p) == 144, "g1_t")
+        out = C.create_string_buffer(144 * max(n, 1))
+        self._call("ckzg_hip_g1_prefix_sums", out, b"".join(points), C.c_uint64(n), self.sp)
+        raw = out.raw
+        return [raw[144 * i:144 * i + 144] for i in range(n)]
+
     def verify_blob_kzg_proof(self, blob, commitment, proof):
         _check(len(blob) == BYTES_PER_BLOB, "blob")
         _check(len(commitment) == 48 and len(proof) == 48, "commitment/proof")

@@ -84,6 +84,9 @@ extern std::atomic<int> g_host_threads;
 // read at call time: smallest verify_blob_kzg_proof_batch that takes the pipelined (chunked copy) form; whether the
 // verifications may build their call-time table (0: ladder sums, the path a device too full for the table takes)
 extern std::atomic<int> g_verify_pipe_min, g_verify_call_table, g_verify_cu_partition;
+// read at call time (ckzg_hip_set_option("locate_max_checks", n)): the host range checks a chunk of the *_locate calls
+// may spend on bisection before what is still open goes through the per-lane GPU check (ckzg_api.hip has the default)
+extern std::atomic<int64_t> g_locate_max_checks;
 
 // How many host threads ONE process of this library may keep busy for a call (challenge hashing, staging copies,
 // point decompression at load): the CPUs of the process's affinity mask divided by the processes that share the host.

@@ -25,6 +25,10 @@ static Options g_opts;
 std::atomic<int> g_gpu_sha_min{0};
 std::atomic<int> g_host_threads{0};
 std::atomic<int> g_verify_pipe_min{1024}, g_verify_call_table{1}, g_verify_cu_partition{1};
+// option "locate_max_checks": a crossover, measured by tools/bench_locate.py (profiles/locate_bench.json) -- the host
+// pool (256 threads) completed 20.69 range checks per ms, the per-lane pass over a full chunk of 65,536 items took
+// 74.8 ms: 1,547 checks in that time, rounded down to a power of two.  No margin.
+std::atomic<int64_t> g_locate_max_checks{1024};
 static std::atomic<int> g_commit_graph{1};   // option "commit_graph": a lone one-blob commitment goes out as one (explicitly built) graph
 static std::atomic<uint64_t> g_graph_stats[3];   // graphs built, builds that failed (plain launches instead), graph launches
 Options options_snapshot() {
@@ -70,6 +74,9 @@ extern "C" C_KZG_RET ckzg_hip_set_option(const char *key, int64_t value) {
     } else if (!strcmp(key, "verify_cu_partition")) {
         if (value != 0 && value != 1) return C_KZG_BADARGS;
         g_verify_cu_partition.store((int)value);   // read at call time
+    } else if (!strcmp(key, "locate_max_checks")) {
+        if (value < 0 || value > ((int64_t)1 << 40)) return C_KZG_BADARGS;
+        g_locate_max_checks.store(value);   // read at call time; 0: hand over as soon as a chunk's root check fails
     } else if (!strcmp(key, "commit_graph")) {
         if (value < 0 || value > 2) return C_KZG_BADARGS;   // (2: diagnostic -- build the graph anew on every call)
         g_commit_graph.store((int)value);  // read at call time

@@ -14,6 +14,7 @@
 #include "blob_groups_plan.hpp"
 #include "cell_groups_plan.hpp"
 #include "combiner.hpp"
+#include "locate_plan.hpp"
 #include "recover_rows_plan.hpp"
 #include "slice_starts.hpp"
 
@@ -2843,5 +2844,264 @@ extern "C" C_KZG_RET ckzg_hip_g1_lincomb(g1_t *out, const g1_t *p, const fr_t *c
         if (ret != C_KZG_OK) return ret;
         *as_g1(out) = r;
         return C_KZG_OK;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Per-item verdicts at batch cost: the batch check's two sums kept as prefix sums, a failing batch bisected on the host
+// (ckzg_hip_g1_prefix_sums, ckzg_hip_verify_kzg_proof_batch_locate, ckzg_hip_verify_blob_kzg_proof_batch_locate;
+// locate.hip, locate_plan.hpp)
+// ------------------------------------------------------------------------------------------
+
+extern "C" C_KZG_RET ckzg_hip_g1_prefix_sums(g1_t *out, const g1_t *p, uint64_t len, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (len == 0) return C_KZG_OK;
+        if (!out || !p) return C_KZG_BADARGS;
+        Lease lease(s);
+        dev::DeviceCtx *ctx = lease.ctx;
+        if (!ctx) return C_KZG_ERROR;
+        std::vector<G1XYZZ> pts(len);
+        for (uint64_t i = 0; i < len; i++) pts[i] = xyzz_from_jac(*as_g1(&p[i]));
+        const size_t nscr = dev::g1_prefix_scan_scratch_points(len, 1);
+        Arena &ar = ctx->api_arena;
+        OKM(ar.begin((len + nscr) * sizeof(G1XYZZ)));
+        ArenaTrim trim(ar);
+        ABuf<G1XYZZ> d_pts(ar, len), d_scr(ar, nscr);
+        OKM(d_pts.p && d_scr.p);
+        StreamDrain drain{ctx->stream};
+        OKB(hipMemcpyAsync(d_pts.p, pts.data(), len * sizeof(G1XYZZ), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        RC(dev::g1_prefix_scan_enqueue(ctx, d_pts.p, d_scr.p, len, 1));
+        OKB(d_pts.down(pts.data(), len));
+        for (uint64_t i = 0; i < len; i++) *as_g1(&out[i]) = jac_from_xyzz(pts[i]);
+        return C_KZG_OK;
+    });
+}
+
+namespace {
+
+// what both forms of a chunk share from the left-hand points onwards (sized for the largest chunk of the call, m items)
+struct LocateBufs {
+    size_t nscan = 0;
+    ABuf<Fp> d_tab, d_prefix;
+    ABuf<uint8_t> d_in48, d_st, d_bad, d_res;
+    ABuf<G1Affine> d_pts, d_lhs, d_negp, d_pref;
+    ABuf<G1XYZZ> d_xyzz, d_ab, d_scan;
+    bool tab_up = false;   // the line tables of the per-lane check are uploaded by the first chunk that hands over
+    static constexpr size_t TAB = 4 * (size_t)MILLER_STEPS * 2;   // Fp: lam[68], c[68] of [1]_2, then of [s]_2, Fp2 each
+    static size_t bytes(size_t m) {
+        return TAB * sizeof(Fp) + 2 * m * sizeof(Fp) + m * (2 * 48 + 4 + 2) + 6 * m * sizeof(G1Affine) +
+               (3 * m + dev::g1_prefix_scan_scratch_points(m, 2)) * sizeof(G1XYZZ) + 13 * 256;
+    }
+    bool take(Arena &ar, size_t m) {
+        nscan = dev::g1_prefix_scan_scratch_points(m, 2);
+        d_tab = ABuf<Fp>(ar, TAB), d_prefix = ABuf<Fp>(ar, 2 * m);
+        d_in48 = ABuf<uint8_t>(ar, 2 * m * 48), d_st = ABuf<uint8_t>(ar, 4 * m), d_bad = ABuf<uint8_t>(ar, m), d_res = ABuf<uint8_t>(ar, m);
+        d_pts = ABuf<G1Affine>(ar, 2 * m), d_lhs = ABuf<G1Affine>(ar, m), d_negp = ABuf<G1Affine>(ar, m), d_pref = ABuf<G1Affine>(ar, 2 * m);
+        d_xyzz = ABuf<G1XYZZ>(ar, m), d_ab = ABuf<G1XYZZ>(ar, 2 * m), d_scan = ABuf<G1XYZZ>(ar, nscan);
+        return d_tab.p && d_prefix.p && d_in48.p && d_st.p && d_bad.p && d_res.p && d_pts.p && d_lhs.p && d_negp.p && d_pref.p &&
+               d_xyzz.p && d_ab.p && d_scan.p;
+    }
+};
+
+// validate_kzg_g1 (bytes.c:81-95) of the k commitments and k proofs of a chunk: bytes -> d_in48, points -> d_pts,
+// decompression flags in d_st[0, 2k), subgroup flags in [2k, 4k).  Enqueue-only, on the compute stream.
+C_KZG_RET locate_points_in(dev::DeviceCtx *ctx, LocateBufs &b, const Bytes48 *cb, const Bytes48 *pb, size_t k) {
+    OKB(hipMemcpyAsync(b.d_in48.p, cb, k * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(b.d_in48.p + k * 48, pb, k * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    RC(dev::decompress_g1_batch_device(ctx, b.d_pts.p, b.d_st.p, b.d_in48.p, 2 * k));
+    RC(dev::subgroup_g1_batch_device(ctx, b.d_st.p + 2 * k, b.d_pts.p, 2 * k));
+    return C_KZG_OK;
+}
+
+// A chunk of k items from its left-hand points onwards: d_xyzz = P1_i (infinity for an invalid item), d_negp = -proof_i
+// and d_bad are enqueued on the compute stream (k_point_lhs / k_point_lhs_fr), r is the chunk's challenge.  Scales both
+// by r^i, scans, brings the 2k prefix points home and bisects on the host pool; what the bisection leaves open when it
+// reaches locate_max_checks goes through the per-lane check once (P1 and -proof are still on the device).
+// stats: [0] += host range checks, [1] += items settled by the per-lane check, [2] += 1.
+C_KZG_RET locate_chunk_from_lhs(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t *stats, LocateBufs &b, const Fr &r, size_t k,
+                                const PreparedG2 *pg) {
+    RC(dev::batch_to_affine_device(ctx, b.d_lhs.p, b.d_xyzz.p, b.d_prefix.p, k));
+    RC(dev::locate_scale_enqueue(ctx, b.d_ab.p, b.d_lhs.p, b.d_negp.p, r, k));
+    RC(dev::g1_prefix_scan_enqueue(ctx, b.d_ab.p, b.d_scan.p, k, 2));
+    RC(dev::batch_to_affine_device(ctx, b.d_pref.p, b.d_ab.p, b.d_prefix.p, 2 * k));
+    std::vector<G1Affine> pref(2 * k);   // PA[1 .. k], then PB[1 .. k]; PA[0] = PB[0] = infinity
+    std::vector<uint8_t> bad(k);
+    OKB(hipMemcpyAsync(bad.data(), b.d_bad.p, k, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(b.d_pref.down(pref.data(), 2 * k));
+    // e(PA[hi] - PA[lo], [1]_2) * e(-(PB[hi] - PB[lo]), [s]_2) == 1
+    auto diff = [&](const G1Affine *p, size_t lo, size_t hi) {
+        const G1Jac top = jac_from_affine(p[hi - 1]);
+        return lo ? jac_madd(top, affine_neg(p[lo - 1])) : top;
+    };
+    auto range_ok = [&](size_t lo, size_t hi) {
+        return pairing_product_is_one(jac_to_affine_fast(diff(pref.data(), lo, hi)), pg->gen,
+                                      jac_to_affine_fast(jac_neg(diff(pref.data() + k, lo, hi))), pg->s1);
+    };
+    const int64_t opt = g_locate_max_checks.load(std::memory_order_relaxed);
+    const LocateOutcome res = locate_bisect(ok, bad.data(), k, (uint64_t)opt, range_ok,
+                                            [](size_t n, const std::function<void(size_t)> &fn) { parallel_for(n, fn); });
+    stats[0] += res.checks;
+    stats[2] += 1;
+    if (!res.open.empty()) {
+        if (!b.tab_up) {
+            std::vector<Fp> tab(LocateBufs::TAB);
+            const host::G2Prepared *q[2] = {&pg->gen, &pg->s1};
+            for (int j = 0; j < 2; j++) {
+                memcpy(&tab[(size_t)(2 * j) * MILLER_STEPS * 2], q[j]->lam, sizeof q[j]->lam);
+                memcpy(&tab[(size_t)(2 * j + 1) * MILLER_STEPS * 2], q[j]->c, sizeof q[j]->c);
+            }
+            OKB(b.d_tab.up(tab.data(), LocateBufs::TAB));
+            b.tab_up = true;
+        }
+        RC(dev::pairing_check_enqueue(ctx, b.d_res.p, b.d_lhs.p, b.d_negp.p, b.d_bad.p, b.d_tab.p, k));
+        std::vector<uint8_t> lane(k);
+        OKB(b.d_res.down(lane.data(), k));
+        for (const LocateRange &o : res.open) {
+            for (size_t i = o.a; i < o.b; i++) {
+                if (bad[i]) continue;
+                ok[i] = lane[i] == 1;
+                stats[1] += 1;
+            }
+        }
+    }
+    C_KZG_RET ret = C_KZG_OK;
+    for (size_t i = 0; i < k; i++) {
+        if (status) status[i] = bad[i] ? (uint8_t)C_KZG_BADARGS : (uint8_t)C_KZG_OK;
+        if (bad[i]) ret = C_KZG_BADARGS;
+    }
+    return ret;
+}
+
+C_KZG_RET locate_point_proofs_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t *stats, const Bytes48 *cb,
+                                 const Bytes32 *zs, const Bytes32 *ys, const Bytes48 *pb, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++) ok[i] = false;
+    if (n == 0) return C_KZG_OK;
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    const uint64_t CH = CKZG_HIP_LOCATE_CHUNK_ITEMS;
+    const uint64_t m = n < CH ? n : CH;
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(LocateBufs::bytes(m) + 2 * m * 32 + 256));
+    ArenaTrim trim(ar);
+    LocateBufs b;
+    OKM(b.take(ar, m));
+    ABuf<uint8_t> d_zy(ar, 2 * m * 32);
+    OKM(d_zy.p);
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the arena's reuse
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t off = 0; off < n; off += CH) {
+        const uint64_t k = n - off < CH ? n - off : CH;
+        RC(locate_points_in(ctx, b, cb + off, pb + off, k));
+        OKB(hipMemcpyAsync(d_zy.p, zs + off, k * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        OKB(hipMemcpyAsync(d_zy.p + k * 32, ys + off, k * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        RC(dev::point_lhs_enqueue(ctx, b.d_xyzz.p, b.d_negp.p, b.d_bad.p, b.d_pts.p, b.d_st.p, b.d_st.p + 2 * k, d_zy.p,
+                                  d_zy.p + k * 32, k));
+        // the chunk's challenge, hashed underneath the kernels above (locate_plan.hpp)
+        uint8_t digest[32];
+        locate_point_digest<Sha256>(digest, cb[off].bytes, zs[off].bytes, ys[off].bytes, pb[off].bytes, k);
+        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg));
+        if (ret != C_KZG_OK && ret != C_KZG_BADARGS) return ret;
+    }
+    return ret;
+}
+
+C_KZG_RET locate_blob_proofs_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t *stats, const Blob *blobs,
+                                const Bytes48 *cb, const Bytes48 *pb, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++) ok[i] = false;
+    if (n == 0) return C_KZG_OK;
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    const uint64_t CH = CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS;
+    const uint64_t m = n < CH ? n : CH;
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(LocateBufs::bytes(m) + m * ((size_t)BYTES_PER_BLOB + 2 * sizeof(Fr) + 4) + 4 * 256));
+    ArenaTrim trim(ar);
+    LocateBufs b;
+    OKM(b.take(ar, m));
+    ABuf<uint8_t> d_blobs(ar, m * (size_t)BYTES_PER_BLOB);
+    ABuf<Fr> d_z(ar, m), d_y(ar, m);
+    ABuf<uint32_t> d_ubad(ar, m);
+    OKM(d_blobs.p && d_z.p && d_y.p && d_ubad.p);
+    std::vector<Fr> z(m), y(m);
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the arena's reuse
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t off = 0; off < n; off += CH) {
+        const uint64_t k = n - off < CH ? n - off : CH;
+        const bool gpu_sha = challenges_on_gpu(k);   // (option "gpu_sha_min", as in the grouped verification)
+        {
+            // the challenges z_i on the host pool (one SHA-256 over 131,152 bytes per blob), underneath the copies
+            BackgroundFor hashes;
+            hashes.what = "blob locate challenge hash jobs";
+            hashes.n = gpu_sha ? 0 : k;
+            hashes.fn = [&](size_t i) { z[i] = challenge_from_bytes(blobs[off + i].bytes, cb[off + i].bytes); };
+            hashes.start();
+            RC(locate_points_in(ctx, b, cb + off, pb + off, k));
+            OKB(hipMemcpyAsync(d_blobs.p, blobs + off, k * (size_t)BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            OKB(hipMemsetAsync(d_ubad.p, 0, k * 4, ctx->stream) == hipSuccess);
+            if (gpu_sha) {
+                RC(dev::sha256_challenges_device(ctx, d_z.p, d_blobs.p, b.d_in48.p, k));
+            } else {
+                hashes.finish();
+                OKB(hipMemcpyAsync(d_z.p, z.data(), k * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            }
+        }
+        RC(dev::eval_blob_bytes_batch_device(ctx, d_y.p, d_ubad.p, d_blobs.p, d_z.p, k));
+        RC(dev::point_lhs_fr_enqueue(ctx, b.d_xyzz.p, b.d_negp.p, b.d_bad.p, b.d_pts.p, b.d_st.p, b.d_st.p + 2 * k, d_z.p, d_y.p,
+                                     d_ubad.p, k));
+        // the 64 bytes per item the transcript needs
+        if (gpu_sha) OKB(hipMemcpyAsync(z.data(), d_z.p, k * sizeof(Fr), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+        OKB(d_y.down(y.data(), k));
+        uint8_t digest[32];
+        host_batch_digest(digest, k, cb + off, pb + off, z.data(), y.data());
+        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg));
+        if (ret != C_KZG_OK && ret != C_KZG_BADARGS) return ret;
+    }
+    return ret;
+}
+
+// the shards' stats summed into the caller's three entries
+template <class Body>
+C_KZG_RET locate_entry(uint64_t *stats, uint64_t n, uint64_t min_shard, const KZGSettings *s, Body &&body) {
+    std::atomic<uint64_t> sum[3] = {{0}, {0}, {0}};
+    const C_KZG_RET ret = for_each_device_shard(s, n, min_shard, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+        uint64_t st[3] = {0, 0, 0};
+        const C_KZG_RET r = body(ctx, st, lo, hi);
+        for (int j = 0; j < 3; j++) sum[j].fetch_add(st[j], std::memory_order_relaxed);
+        return r;
+    });
+    if (stats)
+        for (int j = 0; j < 3; j++) stats[j] = sum[j].load(std::memory_order_relaxed);
+    return ret;
+}
+
+}  // namespace
+
+extern "C" C_KZG_RET ckzg_hip_verify_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats,
+                                                           const Bytes48 *commitments_bytes, const Bytes32 *zs_bytes,
+                                                           const Bytes32 *ys_bytes, const Bytes48 *proofs_bytes, uint64_t n,
+                                                           const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        if (!ok || !commitments_bytes || !zs_bytes || !ys_bytes || !proofs_bytes) return C_KZG_BADARGS;
+        return locate_entry(stats, n, 64, s, [&](dev::DeviceCtx *ctx, uint64_t *st, uint64_t lo, uint64_t hi) {
+            return locate_point_proofs_on(ctx, ok + lo, status ? status + lo : nullptr, st, commitments_bytes + lo, zs_bytes + lo,
+                                          ys_bytes + lo, proofs_bytes + lo, hi - lo);
+        });
+    });
+}
+
+extern "C" C_KZG_RET ckzg_hip_verify_blob_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats, const Blob *blobs,
+                                                                const Bytes48 *commitments_bytes, const Bytes48 *proofs_bytes,
+                                                                uint64_t n, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        if (!ok || !blobs || !commitments_bytes || !proofs_bytes) return C_KZG_BADARGS;
+        return locate_entry(stats, n, 1, s, [&](dev::DeviceCtx *ctx, uint64_t *st, uint64_t lo, uint64_t hi) {
+            return locate_blob_proofs_on(ctx, ok + lo, status ? status + lo : nullptr, st, blobs + lo, commitments_bytes + lo,
+                                         proofs_bytes + lo, hi - lo);
+        });
     });
 }

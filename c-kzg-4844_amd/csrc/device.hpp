@@ -574,10 +574,22 @@ int fr_mul_cell_factor_enqueue(DeviceCtx *ctx, Fr *d_a, const Fr *d_f, const uin
 int point_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8_t *d_bad, const G1Affine *d_pts,
                       const uint8_t *d_st_dec, const uint8_t *d_st_sub, const uint8_t *d_z32, const uint8_t *d_y32,
                       size_t n);
+// the same from z, y as the device holds them (Fr, Montgomery) and the blobs' flags d_unit_bad[n] (non-zero: invalid)
+int point_lhs_fr_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8_t *d_bad, const G1Affine *d_pts,
+                         const uint8_t *d_st_dec, const uint8_t *d_st_sub, const Fr *d_z, const Fr *d_y,
+                         const uint32_t *d_unit_bad, size_t n);
 // d_res[i] = 1 / 0 / 2 (valid / not / invalid item) for e(d_lhs[i], [1]_2) * e(d_neg_proof[i], [s]_2) == 1; d_tab: the
 // prepared lines lam[68], c[68] of [1]_2, then of [s]_2, as Fp2 = 2 x Fp (host_pairing.hpp: G2Prepared)
 int pairing_check_enqueue(DeviceCtx *ctx, uint8_t *d_res, const G1Affine *d_lhs, const G1Affine *d_neg_proof,
                           const uint8_t *d_bad, const Fp *d_tab, size_t n);
+// locate.hip: the terms and the running sums of a batch check (ckzg_api2.hip: locate_chunk_from_lhs).  Enqueue-only, on
+// ctx->stream.  d_ab[i] = [r^i] d_p1[i], d_ab[n + i] = [r^i] proof_i from d_neg_proof[i] = -proof_i (affine; XYZZ out).
+int locate_scale_enqueue(DeviceCtx *ctx, G1XYZZ *d_ab, const G1Affine *d_p1, const G1Affine *d_neg_proof, const Fr &r,
+                         size_t n);
+// d_data[s][i] <- d_data[s][0] + ... + d_data[s][i] for nseg arrays of n points each, in place, with the complete
+// addition; d_scratch: g1_prefix_scan_scratch_points(n, nseg) points
+size_t g1_prefix_scan_scratch_points(size_t n, size_t nseg);
+int g1_prefix_scan_enqueue(DeviceCtx *ctx, G1XYZZ *d_data, G1XYZZ *d_scratch, size_t n, size_t nseg);
 // generic helpers
 int batch_to_affine_device(DeviceCtx *ctx, G1Affine *d_out, const G1XYZZ *d_in, Fp *d_prefix, size_t n);
 

@@ -818,3 +818,98 @@ extern "C" void hs_g2_line_table(uint32_t *out, const G2Jac *q) {
     memcpy(out, p.lam, sizeof p.lam);
     memcpy(out + sizeof p.lam / 4, p.c, sizeof p.c);
 }
+
+// ---- ckzg_hip_verify_kzg_proof_batch_locate / ckzg_hip_verify_blob_kzg_proof_batch_locate: the host half
+// (locate_plan.hpp), checked without a GPU (tests/test_locate_cpu.py). ----
+#include "locate_plan.hpp"
+// The bisection over the predicate "no bad item in the range" (an invalid item is inert, as on the device, whatever its
+// bad byte says).  max_checks < 0: no hand-over.  Out: ok[n], open_out[n] = 1 for the items of the ranges left open at
+// hand-over, stats[0] = checks, stats[1] = open ranges.
+extern "C" void hs_locate_bisect(uint8_t *ok, uint64_t *stats, uint8_t *open_out, const uint8_t *bad, const uint8_t *invalid,
+                                 uint64_t n, int64_t max_checks) {
+    std::vector<uint8_t> okb(n ? n : 1);
+    auto range_ok = [&](size_t a, size_t b) {
+        for (size_t i = a; i < b; i++)
+            if (bad[i] && !invalid[i]) return false;
+        return true;
+    };
+    auto serial = [](size_t m, auto &&fn) {
+        for (size_t i = 0; i < m; i++) fn(i);
+    };
+    const LocateOutcome res = locate_bisect(reinterpret_cast<bool *>(okb.data()), invalid, (size_t)n,
+                                            max_checks < 0 ? UINT64_MAX : (uint64_t)max_checks, range_ok, serial);
+    for (uint64_t i = 0; i < n; i++) {
+        ok[i] = okb[i];
+        open_out[i] = 0;
+    }
+    for (const LocateRange &r : res.open)
+        for (size_t i = r.a; i < r.b; i++) open_out[i] = 1;
+    stats[0] = res.checks;
+    stats[1] = res.open.size();
+}
+
+// The whole second half of the point form in host arithmetic: validation, P1_i = C_i - [y_i]G + [z_i]proof_i, the
+// challenge r (locate_point_digest), A_i = [r^i]P1_i and B_i = [r^i]proof_i, their prefix sums, and the bisection over
+// the real predicate e(PA[b] - PA[a], [1]_2) * e(-(PB[b] - PB[a]), [tau]_2) == 1.  tau_g2: [tau]_2 (g2_values_monomial[1]).
+// Out: ok[n], status[n] (1 = invalid item), stats[0] = checks, r32 = the digest r was reduced from.
+extern "C" void hs_locate_points_host(uint8_t *ok, uint8_t *status, uint64_t *stats, uint8_t *r32, const uint8_t *c48,
+                                      const uint8_t *z32, const uint8_t *y32, const uint8_t *p48, uint64_t n,
+                                      const G2Jac *tau_g2, int64_t max_checks) {
+    G2Prepared q1, q2;
+    g2_prepare(q1, g2_to_affine(g2_generator()));
+    g2_prepare(q2, g2_to_affine(*tau_g2));
+    auto fr_canonical = [](uint32_t raw[8], const uint8_t *b) {
+        uint32_t m[8];
+        for (int i = 0; i < 8; i++) {
+            const uint8_t *p = b + 4 * (7 - i);
+            raw[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+        }
+        mod_limbs<FrParams>(m);
+        return !limbs_geq<8>(raw, m);
+    };
+    locate_point_digest<Sha256>(r32, c48, z32, y32, p48, n);
+    uint32_t rraw[8];
+    for (int i = 0; i < 8; i++) {
+        const uint8_t *p = r32 + 4 * (7 - i);
+        rraw[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+    }
+    const Fr r = from_raw<FrParams>(rraw);   // (reduces)
+    std::vector<uint8_t> invalid(n ? n : 1), okb(n ? n : 1);
+    std::vector<G1Jac> pa(n + 1), pb(n + 1);   // PA[0] = PB[0] = infinity
+    pa[0] = pb[0] = G1Jac::inf();
+    Fr rp = Fr::one();
+    for (uint64_t i = 0; i < n; i++, rp = mul(rp, r)) {
+        G1Affine c, pr;
+        uint32_t z[8], y[8], k[8];
+        bool bad = g1_uncompress(c, c48 + 48 * i) != 0 || g1_uncompress(pr, p48 + 48 * i) != 0;
+        bad = bad || !g1_in_subgroup_host(c) || !g1_in_subgroup_host(pr);
+        bad = !fr_canonical(z, z32 + 32 * i) || bad;
+        bad = !fr_canonical(y, y32 + 32 * i) || bad;
+        invalid[i] = bad ? 1 : 0;
+        G1Jac a = G1Jac::inf(), b = G1Jac::inf();
+        if (!bad) {
+            const G1Jac proof = jac_from_affine(pr);
+            const G1Jac p1 = jac_add(jac_add(jac_from_affine(c), jac_neg(g1_mul_glv_host(g1_generator(), y))), g1_mul_glv_host(proof, z));
+            to_raw<FrParams>(k, rp);
+            a = g1_mul_glv_host(p1, k);
+            b = g1_mul_glv_host(proof, k);
+        }
+        pa[i + 1] = jac_add(pa[i], a);
+        pb[i + 1] = jac_add(pb[i], b);
+    }
+    auto range_ok = [&](size_t lo, size_t hi) {
+        const G1Jac da = jac_add(pa[hi], jac_neg(pa[lo])), db = jac_add(pb[hi], jac_neg(pb[lo]));
+        return pairing_product_is_one(jac_to_affine(da), q1, jac_to_affine(jac_neg(db)), q2);
+    };
+    auto serial = [](size_t m, auto &&fn) {
+        for (size_t i = 0; i < m; i++) fn(i);
+    };
+    const LocateOutcome res = locate_bisect(reinterpret_cast<bool *>(okb.data()), invalid.data(), (size_t)n,
+                                            max_checks < 0 ? UINT64_MAX : (uint64_t)max_checks, range_ok, serial);
+    for (uint64_t i = 0; i < n; i++) {
+        ok[i] = okb[i];
+        status[i] = invalid[i];
+    }
+    stats[0] = res.checks;
+    stats[1] = res.open.size();
+}

@@ -8,6 +8,7 @@
 //     proofs and commitments, src/eip4844/eip4844.c:731-746, src/eip7594/eip7594.c:530,807,926)
 //   * element-wise Fr helpers used by recover_cells (src/eip7594/recovery.c:281,322-328)
 #include "device.hpp"
+#include "rpow2.hpp"
 #include "dev_inline.hpp"
 #include "g1_28.hpp"
 #include "g1_quad.hpp"
@@ -466,30 +467,7 @@ int eval_blob_bytes_batch_device(DeviceCtx *ctx, Fr *d_y, uint32_t *d_bad, const
 // sum r^i C_i) as digit-ready vectors over the 2n points of a call-time table (commitments [0, n), proofs [n, 2n);
 // the caller zeroed sc): one lane per blob raises the batch challenge to its own index -- <= 2 log2(n) products --
 // so that nothing but r itself (32 bytes, a kernel argument) crosses PCIe between the transcript and the sums.
-// r^(2^k), k < 24, made on the host (23 squarings) and passed by value: a lane's power of r is then the product of
-// the entries its index selects -- <= 13 products for n = 8192, ~6 on average, and no squarings of its own.
-struct RPow2 {
-    Fr p[24];
-};
-__device__ __forceinline__ Fr rpow_at(const RPow2 &t, uint32_t i) {
-    Fr pw = Fr::one();
-    bool first = true;
-#pragma unroll 1
-    for (int k = 0; k < 24 && (i >> k); k++) {
-        if ((i >> k) & 1u) {
-            pw = first ? t.p[k] : mul(pw, t.p[k]);
-            first = false;
-        }
-    }
-    return pw;
-}
-static RPow2 rpow2_of(const Fr &r) {
-    RPow2 t;
-    t.p[0] = r;
-    for (int k = 1; k < 24; k++) t.p[k] = mul(t.p[k - 1], t.p[k - 1]);
-    return t;
-}
-
+// r^(2^k), k < 24, made on the host and passed by value: rpow2.hpp.
 __global__ void k_rlc_scalars(uint32_t *sc, const Fr *z, RPow2 rp2, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

@@ -105,6 +105,11 @@ extern "C" {
  *                   names what it waited for.  A DEVICE wait that expires marks the device as not answering: its kernels
  *                   may still be running, so later calls on it fail at once with C_KZG_ERROR instead of queueing behind
  *                   them, and free_trusted_setup leaves the device state in place.  Takes effect immediately.
+ *   "locate_max_checks"  host range checks a chunk of the *_locate calls may spend bisecting a failing batch before what
+ *                   is still open goes once through the per-lane GPU check (see ckzg_hip_verify_kzg_proof_batch_locate).
+ *                   0: hand over as soon as the root check fails.  Default 1024: the range checks a 256-thread
+ *                   host pool completes (20.7 per ms) in the 74.8 ms the per-lane pass takes on a full chunk, rounded
+ *                   down to a power of two (profiles/locate_bench.json).  Takes effect immediately.
  * A width that does not fit the free HBM is narrowed at load time (ckzg_hip_table_wbits reports the result).
  * Returns C_KZG_BADARGS for an unknown key or out-of-range value. */
 C_KZG_RET ckzg_hip_set_option(const char *key, int64_t value);
@@ -188,6 +193,51 @@ C_KZG_RET ckzg_hip_compute_kzg_proof_batch_device(void *d_proofs, void *d_ys, vo
 C_KZG_RET ckzg_hip_verify_kzg_proof_batch(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
                                           const Bytes32 *zs_bytes, const Bytes32 *ys_bytes,
                                           const Bytes48 *proofs_bytes, uint64_t n, const KZGSettings *s);
+
+/* Per-item verdicts at batch cost.  For every i, (status[i], ok[i]) is (return value, *ok) of
+ * verify_kzg_proof(&commitments[i], &zs[i], &ys[i], &proofs[i], s), as for ckzg_hip_verify_kzg_proof_batch -- but the
+ * normal case, a batch in which everything verifies, costs ONE two-pairing check instead of one per item.  The two sums
+ * of the random-linear-combination check (eip4844.c:697-758) are linear in per-item terms A_i = [r^i](C_i - [y_i]G +
+ * [z_i]proof_i) and B_i = [r^i]proof_i; the device keeps their running (prefix) sums, so the host can check any
+ * contiguous range [a, b) of the batch with two point subtractions and one two-pairing check, and a failing batch is
+ * bisected there without further GPU work: b false items among n cost about 2 b log2(n) more checks, run on the host
+ * pool.  A range of one item is the deterministic check itself, so ok[i] = false is always exact; ok[i] = true is as
+ * sound as every other batch path of the library (error 2^-255 per check).  An invalid item (point not in G1, z or y
+ * not canonical) contributes infinity to every range, never makes one fail and is settled from its flag alone.
+ * Returns C_KZG_BADARGS if any item is invalid (its ok[i] = false, status[i] = 1; the other items' verdicts are still
+ * written), C_KZG_OK otherwise; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  status and stats may be NULL;
+ * n == 0 is C_KZG_OK and writes nothing.  Host pointers; several devices take contiguous runs of items.
+ * On a device the items go in chunks of at most CKZG_HIP_LOCATE_CHUNK_ITEMS; every chunk has its own challenge (the
+ * batch transcript over the chunk's items as given) and its own bisection: a per-item verdict does not depend on r.
+ * stats (three entries, summed over chunks and devices): [0] range checks (two-pairing checks) run on the host,
+ * [1] items whose verdict came from the per-lane GPU check, [2] chunks.
+ * Hand-over: before a level of the bisection starts, if the checks done plus two per range still open would exceed the
+ * option "locate_max_checks", the bisection of that chunk stops and the chunk goes once through the per-lane check of
+ * ckzg_hip_verify_kzg_proof_batch (its inputs are still on the device); the items of the open ranges take their verdict
+ * from it.  That bounds the worst case (everything false) near the cost of that call.  0 = hand over as soon as a
+ * chunk's root check fails (the root check itself is always run).  ckzg_hip_set_option takes effect immediately.
+ * Measured (profiles/locate_bench.json; medians of 20, a 256-thread host): everything good, 14.1 / 14.6 / 14.8 / 24.4 ms
+ * for 64 / 512 / 4,096 / 65,536 items against 64.9 / 65.2 / 65.3 / 86.4 ms for ckzg_hip_verify_kzg_proof_batch; one false
+ * item 20.0 / 25.6 / 29.8 / 43.2 ms, eight 24.8 / 30.9 / 38.5 / 53.9 ms.  NOT faster: with every item false, 113.7 ms at
+ * 4,096 and 143.5 ms at 65,536 (the bisection up to the hand-over, then the per-lane pass) against 65.3 / 86.4 ms; and
+ * at 64 items a loop of verify_kzg_proof on the host's threads took 6.2 ms (27.4 ms at 512, 279 ms at 4,096). */
+#define CKZG_HIP_LOCATE_CHUNK_ITEMS 65536
+C_KZG_RET ckzg_hip_verify_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats,
+                                                 const Bytes48 *commitments_bytes, const Bytes32 *zs_bytes,
+                                                 const Bytes32 *ys_bytes, const Bytes48 *proofs_bytes, uint64_t n,
+                                                 const KZGSettings *s);
+
+/* The same for blobs: for every i, (status[i], ok[i]) is (return value, *ok) of verify_blob_kzg_proof(&blobs[i],
+ * &commitments[i], &proofs[i], s).  The blobs' challenges z_i and evaluations y_i are made as in
+ * ckzg_hip_verify_blob_kzg_proof_batch_groups and stay on the device; from there on it is the point form.  Chunks of
+ * at most CKZG_HIP_BLOB_GROUPS_CHUNK_BLOBS blobs.  Return values, NULL handling, stats and the hand-over as above.
+ * Measured (same record): everything good, 14.3 / 14.4 / 16.2 ms for 8 / 64 / 512 blobs; NOT faster than
+ * ckzg_hip_verify_blob_kzg_proof_batch_groups with groups of one at 8 and 64 blobs (2.5 / 4.3 ms: the two ladder kernels
+ * of this call cost ~12 ms whatever the size), ahead of its median at 512 (20.2 ms, minimum 16.7); with every blob
+ * false 19.3 / 26.5 / 56.3 ms. */
+C_KZG_RET ckzg_hip_verify_blob_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats, const Blob *blobs,
+                                                      const Bytes48 *commitments_bytes, const Bytes48 *proofs_bytes,
+                                                      uint64_t n, const KZGSettings *s);
 
 /* verify_cell_kzg_proof_batch (src/eip7594/eip7594.c:825-974) over num_groups independent batches in one call, one
  * verdict per group -- the shape of a PeerDAS node, which verifies every column sidecar of a block on its own to know
@@ -326,6 +376,12 @@ C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGP
  * half-term, 4 = ladders with four lanes per half-term (g1_quad.hpp). */
 C_KZG_RET ckzg_hip_g1_lincomb(g1_t *out, const g1_t *p, const fr_t *coeffs, uint64_t len, int algo,
                               const KZGSettings *s);
+
+/* out[i] = p[0] + ... + p[i] (inclusive), reference in-memory form (g1_t Jacobian) in and out; len == 0 writes nothing.
+ * Complete: identity inputs, p[i] == running sum (doubling) and p[i] == -running sum are handled.  No subgroup
+ * requirement (additions only); points must be on the curve.  The G1 prefix scan of the *_locate calls on its own:
+ * tiles of 256 points scanned through LDS, the tiles' totals scanned the same way, about ten additions per point. */
+C_KZG_RET ckzg_hip_g1_prefix_sums(g1_t *out, const g1_t *p, uint64_t len, const KZGSettings *s);
 
 /* Timing hook for bench.py: elapsed milliseconds of the named kernel family inside the last
  * batch call, measured with hipEvents on the stream the kernels were launched on (for a call that was
