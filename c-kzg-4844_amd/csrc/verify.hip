@@ -488,8 +488,8 @@ __global__ void k_rlc_scalars(uint32_t *sc, const Fr *z, RPow2 rp2, uint32_t n) 
 
 int rlc_scalars_enqueue(hipStream_t stream, uint32_t *d_sc, const Fr *d_z, const Fr &r, size_t n) {
     if (!n) return 0;
+    if (n >= ((size_t)1 << 24)) return 2;   // (rpow2.hpp: 24 squarings) refused before anything is enqueued
     HIP_TRY(hipMemsetAsync(d_sc, 0, 6 * n * 8 * sizeof(uint32_t), stream));
-    if (n >= ((size_t)1 << 24)) return 2;
     hipLaunchKernelGGL(k_rlc_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_sc, d_z, rpow2_of(r), (uint32_t)n);
     HIP_TRY(hipGetLastError());
     return 0;

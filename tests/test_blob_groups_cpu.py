@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import rlc_expect as rx
 from conftest import ROOT, SHIM_SO
 from kzg_ctypes import HIP_SO, Kzg, KzgError, KZGSettings, TRUSTED_SETUP
 from test_abi_exports import declared_symbols
@@ -154,6 +155,10 @@ def test_host_replay_of_the_segmented_arithmetic_matches_the_oracle(h, oracle):
         assert total > 0 and total % 64 == 0 and info[0] == total and info[1] == (1 if quad_max else 0)
         scal = [sum(sc[8 * t + i] << (32 * i) for i in range(8)) for t in range(total)]
         assert all(src[t] == 0xffffffff and scal[t] == 0 for t in range(part_off[2 * G] * per, total))
+        # every scalar is the integer the layout of blob_groups_plan.hpp puts there: a verdict cannot tell r^i from
+        # another weight that lands consistently on item i's commitment, proof and y
+        rx.check_terms(src[:total], scal, part_off[:],
+                       rx.blob_group_terms([len(g) for g in groups], [t[3] for t in flat], [t[4] for t in flat], rs, per))
         got = []
         for g in range(G):
             sums = []
@@ -169,3 +174,27 @@ def test_host_replay_of_the_segmented_arithmetic_matches_the_oracle(h, oracle):
             else:
                 got.append(h.hs_pairings_verify(sums[0], g2_gen, sums[1], g2_s) == 1)
         assert got == want, (quad_max, got)
+
+
+@pytest.mark.parametrize("quad_max", [8192, 0])
+def test_host_replay_weights_are_the_integers(h, quad_max):
+    """the group sizes and challenges of tests/test_gpu_rlc_stages.py (a group's r = 0, another's = 1), term by term"""
+    import random
+    sizes = rx.GROUP_SIZES
+    G, N = len(sizes), sum(sizes)
+    rnd = random.Random(99 + quad_max)
+    z = [rnd.randrange(R) for _ in range(N)]
+    y = [rnd.randrange(R) for _ in range(N)]
+    z[0], z[70], y[1], y[71] = 0, R - 1, 0, R - 1
+    rs = rx.group_challenges(77 + quad_max)
+    start = [sum(sizes[:g]) for g in range(G + 1)]
+    cap = 4096
+    sc = (C.c_uint32 * (cap * 8))()
+    src = (C.c_uint32 * cap)()
+    part_off = (C.c_uint32 * (2 * G + 1))()
+    info = (C.c_uint32 * 2)()
+    total = h.hs_blob_groups_replay(sc, src, part_off, info, C.c_size_t(cap), (C.c_uint64 * (G + 1))(*start), C.c_size_t(G),
+                                    rx.le32(z), rx.le32(y), rx.le32(rs), C.c_size_t(quad_max))
+    want = rx.blob_group_terms(sizes, z, y, rs, 8 if quad_max else 32)
+    assert total == len(want[0]) and info[0] == total
+    rx.check_terms(src[:total], rx.from_le32(sc, total), part_off[:], want)

@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import rlc_expect as rx
 from conftest import ROOT, SHIM_SO
 from kzg_ctypes import HIP_SO, Kzg, KzgError, KZGSettings, TRUSTED_SETUP
 from test_abi_exports import declared_symbols
@@ -170,6 +171,10 @@ def test_host_replay_of_the_segmented_arithmetic_matches_the_oracle(h, oracle):
         # pairs: (0: c0, c1) (2: c1, c0) (3: c0, c1) (4: c0); rows: 2 + 3 + 2 + 1
         assert info[2] == 7 and info[3] == 8
         scal = [sum(sc[8 * t + i] << (32 * i) for i in range(8)) for t in range(total)]
+        # every weight is the integer the layout of cell_groups_plan.hpp puts there (the interpolation coefficients
+        # are no weights: the verdicts below cover them)
+        rx.check_terms(src[:total], scal, part_off[:],
+                       rx.cell_group_terms([len(g) for g in groups], cell_commit, len(uniq), [t[1] for t in flat], rs, roots, per))
         got = []
         for g in range(G):
             sums = []
@@ -186,3 +191,30 @@ def test_host_replay_of_the_segmented_arithmetic_matches_the_oracle(h, oracle):
                     len({t[0] for t in groups[g]}) + len(groups[g]) + 64
                 got.append(h.hs_pairings_verify(sums[0], g2_gen, sums[1], g2_s64) == 1)
         assert got == want, (quad_max, got)
+
+
+@pytest.mark.parametrize("quad_max", [8192, 0])
+def test_host_replay_weights_are_the_integers(h, quad_max):
+    """the group sizes and challenges of tests/test_gpu_rlc_stages.py (a group's r = 0, another's = 1), term by term"""
+    import random
+    sizes = rx.GROUP_SIZES
+    G, N = len(sizes), sum(sizes)
+    rnd = random.Random(199 + quad_max)
+    num_commits = 5
+    cell_commit = [rnd.randrange(num_commits) for _ in range(N)]
+    cols = [(29 * i + 3) % 128 for i in range(N)]
+    rs = rx.group_challenges(177 + quad_max)
+    roots = rx.roots_of_unity()
+    start = [sum(sizes[:g]) for g in range(G + 1)]
+    cells_raw = rx.le32(rnd.randrange(R) for _ in range(64 * N))
+    cap = 4096
+    sc = (C.c_uint32 * (cap * 8))()
+    src = (C.c_uint32 * cap)()
+    part_off = (C.c_uint32 * (2 * G + 1))()
+    info = (C.c_uint32 * 4)()
+    total = h.hs_cell_groups_replay(sc, src, part_off, info, C.c_size_t(cap), (C.c_uint64 * (G + 1))(*start), C.c_size_t(G),
+                                    (C.c_uint32 * N)(*cell_commit), C.c_size_t(num_commits), (C.c_uint64 * N)(*cols), cells_raw,
+                                    rx.le32(rs), rx.le32(roots), C.c_size_t(quad_max))
+    want = rx.cell_group_terms(sizes, cell_commit, num_commits, cols, rs, roots, 8 if quad_max else 32)
+    assert total == len(want[0]) and info[0] == total
+    rx.check_terms(src[:total], rx.from_le32(sc, total), part_off[:], want)
