@@ -797,6 +797,19 @@ class OutPipe {
     bool started = false, closing = false, failed = false;
 };
 
+// Finishes an OutPipe, then waits for the streams it is given (the second if any), when it goes out of scope: declared
+// right after the pipe, it keeps every exit path, an early error return included, from leaving work behind that reads
+// the arena, the staging buffers or the frame
+struct PipeDrain {
+    OutPipe &pipe;
+    hipStream_t first, second = nullptr;
+    ~PipeDrain() {
+        (void)pipe.finish();
+        (void)dev::sync_stream(first);
+        if (second) (void)dev::sync_stream(second);
+    }
+};
+
 struct DeviceBuffer {
     void *p = nullptr;
     bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }

@@ -697,15 +697,7 @@ static C_KZG_RET cells_and_proofs_batch_on(dev::DeviceCtx *ctx, Cell *cells, KZG
     std::vector<uint8_t> st(n);
     std::vector<size_t> mark;
     OutPipe pipe(ctx);
-    struct StreamDrain {  // nothing may still read the arena or the staging buffers when this function leaves
-        dev::DeviceCtx *c;
-        OutPipe &p;
-        ~StreamDrain() {
-            (void)p.finish();
-            (void)dev::sync_stream(c->copy_stream);
-            (void)dev::sync_stream(c->stream);
-        }
-    } drain{ctx, pipe};
+    PipeDrain drain{pipe, ctx->copy_stream, ctx->stream};  // nothing may still read the arena or the staging buffers when this function leaves
     bool pending[2] = {false, false};
     const bool src_pinned = host_pointer_is_pinned(blobs);
     uint64_t sub_index = 0, chunk = 0;

@@ -1464,121 +1464,92 @@ static void vanishing_poly_from_roots(std::vector<Fr> &poly, const std::vector<F
     poly[n] = Fr::one();
 }
 
-// recover_cells (recovery.c:200-365) on the GPU for `count` extended blobs that miss the SAME
-// cells.  d_e holds count x 8192 values in cell (bit-reversed) order with zeros at the missing
-// cells and is overwritten with the recovered values, same order.  Everything that depends only
-// on the missing set (Z over the domain, 1/Z over the coset) is computed once.
-static C_KZG_RET recover_cells_gpu(dev::DeviceCtx *ctx, Fr *d_e, size_t count, const uint64_t *cell_indices,
-                                   size_t num_cells, const KZGSettings *s) {
-    const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
-    std::vector<Fr> roots;
-    const Fr *rou = as_fr(s->roots_of_unity);
-    bool have[CELLS_PER_EXT_BLOB] = {false};
-    for (size_t k = 0; k < num_cells; k++) have[cell_indices[k]] = true;
-    for (size_t i = 0; i < CELLS_PER_EXT_BLOB; i++)
-        if (!have[i]) roots.push_back(rou[reverse_bits_limited(CELLS_PER_EXT_BLOB, i) * (n / CELLS_PER_EXT_BLOB)]);
-    if (roots.empty() || roots.size() >= CELLS_PER_EXT_BLOB) return C_KZG_BADARGS;  // recovery.c:103-106
-    std::vector<Fr> shortp, zc(n, Fr::zero()), ones(n, Fr::one());
-    vanishing_poly_from_roots(shortp, roots);
-    for (size_t i = 0; i < shortp.size(); i++) zc[i * FIELD_ELEMENTS_PER_CELL] = shortp[i];
-    // (the caller's arena scope is open: these three vectors come out of it too)
-    ABuf<Fr> d_zc(ctx->api_arena, n), d_zev(ctx->api_arena, n), d_zinv(ctx->api_arena, n);
-    OKM(d_zc.p && d_zev.p && d_zinv.p);
-    OKB(d_zc.up(zc.data(), n));
-    OKB(d_zinv.up(ones.data(), n));
-    OKB(hipMemcpyAsync(d_zev.p, d_zc.p, n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
-    // Z over the domain, in bit-reversed order = the order of d_e
-    RC(dev::fr_ntt_batch(ctx, d_zev.p, 1, 13, true, false, false));
-    // 1 / Z over the coset (the divisor of recovery.c:322-328, inverted once for the whole batch)
-    RC(dev::fr_mul_inplace_device(ctx, d_zc.p, ctx->d_shift, n, n));
-    RC(dev::fr_ntt_batch(ctx, d_zc.p, 1, 13, true, false, false));
-    RC(dev::fr_div_inplace_device(ctx, d_zinv.p, d_zc.p, n));
-    const size_t tot = count * n;
-    RC(dev::fr_mul_inplace_device(ctx, d_e, d_zev.p, tot, n));           // (E * Z)(w^i)
-    RC(dev::fr_ntt_batch(ctx, d_e, count, 13, false, true, true));       // -> coefficients
-    RC(dev::fr_mul_inplace_device(ctx, d_e, ctx->d_shift, tot, n));      // coset_fft: scale by 7^i ...
-    RC(dev::fr_ntt_batch(ctx, d_e, count, 13, true, false, false));      // ... and transform
-    RC(dev::fr_mul_inplace_device(ctx, d_e, d_zinv.p, tot, n));          // recovery.c:322-328
-    RC(dev::fr_ntt_batch(ctx, d_e, count, 13, false, true, true));       // coset_ifft ...
-    RC(dev::fr_mul_inplace_device(ctx, d_e, ctx->d_unshift, tot, n));    // ... unscale by 7^-i
-    RC(dev::fr_ntt_batch(ctx, d_e, count, 13, true, false, false));      // evaluations, cell order
-    OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-    return C_KZG_OK;
-}
+// ---- The chunk pipeline of both recovery calls ----
+// recover_cells (recovery.c:200-365) and FK20 on the GPU for the rows of a call on one device, in chunks of at most
+// RECOVER_CHUNK_ROWS device rows.  recover_chunks owns what the calls share: the arena request and the common buffers,
+// the OutPipe and its drain, the chunk loop with its alternating output buffers, the conversion from and to bytes, the
+// transform sequence, the one wait per chunk, flags and status, the give-back, the proof tail and the timing epilogue.
+// A *source* supplies what differs between the call whose rows all hold the same cells (RecoverSameCells) and the call
+// by rows (RecoverByRows): its chunks, its way of bringing the cells into the zeroed image, its way of making and
+// applying Z, and which caller rows its device rows are.
+//     chunks(), rows(c), all_full(c)       the chunks; all_full: every row holds 128 cells, nothing to recover
+//     max_rows(), in_bytes()               over the chunks: device rows, bytes of cells copied in
+//     extra_bytes(), take(arena)           the source's own device buffers, taken after the common ones
+//     prepare(ctx)                         once before the loop
+//     cells_in(ctx, c, d_img, d_in)        chunk c's cells -> their places in d_img (k x 8192 x 32 bytes, zeroed)
+//     mul_z(ctx, c, d_e), mul_zinv(...)    d_e *= Z over the domain, d_e *= 1 / Z over the coset
+//     for_each_run(c, f)                   f(device row, caller row, rows) for every run of rows that goes back in one copy
+//     caller_row(c, i)                     the caller row of device row i (status)
+// Caller rows index recovered_cells, recovered_proofs and status as they are passed.  A row flagged in status[] holds
+// unspecified output; the return value is `result` (what the caller found before) or C_KZG_BADARGS if a row is flagged.
+constexpr size_t RECOVER_CHUNK_ROWS = 512;  // 512 rows: 128 MiB of byte image + 128 MiB of Fr + 64 MiB of coefficients
 
-static C_KZG_RET recover_batch_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs,
-                                  uint8_t *status, const uint64_t *cell_indices, const Cell *cells,
-                                  uint64_t num_cells, uint64_t num_blobs, const KZGSettings *s) {
-    if (num_blobs == 0) return C_KZG_OK;
+template <class Source>
+static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs, uint8_t *status,
+                                C_KZG_RET result, Source &&src) {
+    if (src.chunks() == 0) return result;
     const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
-    const size_t CH = 512;  // 512 rows: 128 MiB of byte image + 128 MiB of Fr + 64 MiB of coefficients
-    const size_t m = num_blobs < CH ? (size_t)num_blobs : CH;
+    const size_t m = src.max_rows();
     // Batches drain their outputs (256 KB of cells + 6 KB of proofs per row) through an OutPipe: the cells
     // of a chunk cross PCIe while its proofs are computed, the proofs while the next chunk starts.  Output
     // buffers alternate between chunks.  A call with a few rows copies directly (no helper thread).
-    const bool piped = num_blobs > 8;
+    const bool piped = m > 8;
     const int nbuf = piped ? 2 : 1;
-    std::vector<uint32_t> idx32(num_cells);
-    for (size_t i = 0; i < num_cells; i++) idx32[i] = (uint32_t)cell_indices[i];
     std::vector<uint32_t> bad(m);
-    C_KZG_RET result = C_KZG_OK;
     Arena &ar = ctx->api_arena;
-    const size_t nchunks = (size_t)((num_blobs + CH - 1) / CH);  // recover_cells_gpu takes 3 vectors per chunk
-    OKM(ar.begin(m * (nbuf * n * 32 + num_cells * BYTES_PER_CELL + n * sizeof(Fr) + 4) + num_cells * 4 +
-                 nchunks * 3 * (n * sizeof(Fr) + 256) +
+    // image(s) + Fr + flags per row; input; the source's own; proofs
+    OKM(ar.begin(m * (nbuf * n * 32 + n * sizeof(Fr) + 4) + src.in_bytes() + src.extra_bytes() +
                  (recovered_proofs ? m * (nbuf * CELLS_PER_EXT_BLOB * 48 + FIELD_ELEMENTS_PER_BLOB * sizeof(Fr)) : 0) + 4096));
     ArenaTrim trim(ar);
-    ABuf<uint8_t> d_img0(ar, m * n * 32), d_img1(ar, piped ? m * n * 32 : 1), d_in(ar, m * num_cells * BYTES_PER_CELL);
+    ABuf<uint8_t> d_img0(ar, m * n * 32), d_img1(ar, piped ? m * n * 32 : 1), d_in(ar, src.in_bytes());
     ABuf<uint8_t> d_pr0(ar, recovered_proofs ? m * CELLS_PER_EXT_BLOB * 48 : 1);
     ABuf<uint8_t> d_pr1(ar, recovered_proofs && piped ? m * CELLS_PER_EXT_BLOB * 48 : 1);
     ABuf<Fr> d_e(ar, m * n), d_poly(ar, recovered_proofs ? m * FIELD_ELEMENTS_PER_BLOB : 1);
-    ABuf<uint32_t> d_bad(ar, m), d_idx(ar, num_cells);
-    OKM(d_img0.p && d_img1.p && d_in.p && d_pr0.p && d_pr1.p && d_e.p && d_poly.p && d_bad.p && d_idx.p);
+    ABuf<uint32_t> d_bad(ar, m);
+    OKM(d_img0.p && d_img1.p && d_in.p && d_pr0.p && d_pr1.p && d_e.p && d_poly.p && d_bad.p && src.take(ar));
     uint8_t *img_buf[2] = {d_img0.p, piped ? d_img1.p : d_img0.p}, *pr_buf[2] = {d_pr0.p, piped ? d_pr1.p : d_pr0.p};
-    OKB(d_idx.up(idx32.data(), num_cells));
+    // the pipe's page-locked staging, taken here so that running out of it is C_KZG_MALLOC like every other allocation
+    if (piped) OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, OutPipe::PIECE));
     OutPipe pipe(ctx);
-    struct Drain {  // nothing may still read the arena when this function leaves, on any path
-        dev::DeviceCtx *c;
-        OutPipe &p;
-        ~Drain() {
-            (void)p.finish();
-            (void)dev::sync_stream(c->stream);
-        }
-    } drain{ctx, pipe};
+    PipeDrain drain{pipe, ctx->stream};  // nothing may still read the arena or the source when this function leaves
     std::vector<size_t> mark;
-    size_t chunk = 0;
+    // the outputs of a chunk go back run by run: device rows are packed, caller rows keep the gaps of invalid rows
+    auto give_back = [&](size_t c, const uint8_t *d_src, void *h_dst, size_t per_row) -> bool {
+        return src.for_each_run(c, [&](size_t dev_row, size_t caller_row, size_t rows) -> bool {
+            const uint8_t *from = d_src + dev_row * per_row;
+            uint8_t *to = static_cast<uint8_t *>(h_dst) + caller_row * per_row;
+            if (piped) return pipe.push(from, to, rows * per_row);
+            return hipMemcpy(to, from, rows * per_row, hipMemcpyDeviceToHost) == hipSuccess;   // (the stream has been waited for)
+        });
+    };
     OKB(hipEventRecord(ctx->ev[1], ctx->stream) == hipSuccess);
-    for (size_t off = 0; off < num_blobs; off += CH, chunk++) {
-        const size_t k = num_blobs - off < CH ? (size_t)(num_blobs - off) : CH;
-        const size_t in_bytes = k * num_cells * BYTES_PER_CELL;
-        uint8_t *d_img = img_buf[chunk & 1], *d_proofs = pr_buf[chunk & 1];
-        if (piped && chunk >= 2) pipe.wait_for(mark[chunk - 2]);
-        OKB(hipMemcpyAsync(d_in.p, cells + off * num_cells, in_bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    RC(src.prepare(ctx));
+    for (size_t c = 0; c < src.chunks(); c++) {
+        const size_t k = src.rows(c), tot = k * n;
+        uint8_t *d_img = img_buf[c & 1], *d_proofs = pr_buf[c & 1];
+        if (piped && c >= 2) pipe.wait_for(mark[c - 2]);   // this chunk's output buffers have been drained
         OKB(hipMemsetAsync(d_img, 0, k * n * 32, ctx->stream) == hipSuccess);
         OKB(hipMemsetAsync(d_bad.p, 0, k * 4, ctx->stream) == hipSuccess);
-        RC(dev::scatter_cells_device(ctx, d_img, d_in.p, d_idx.p, (uint32_t)num_cells, k));
-        RC(dev::bytes_to_fr_batch(ctx, d_e.p, d_bad.p, d_img, k * n, (uint32_t)n));
-        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-        OKB(d_bad.down(bad.data(), k));
-        bool any_bad = false;
+        RC(src.cells_in(ctx, c, d_img, d_in.p));
+        RC(dev::bytes_to_fr_batch(ctx, d_e.p, d_bad.p, d_img, tot, (uint32_t)n));
+        if (!src.all_full(c)) {
+            RC(src.mul_z(ctx, c, d_e.p));                                        // (E * Z)(w^i)
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));         // -> coefficients
+            RC(dev::fr_mul_inplace_device(ctx, d_e.p, ctx->d_shift, tot, n));    // coset_fft: scale by 7^i ...
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));        // ... and transform
+            RC(src.mul_zinv(ctx, c, d_e.p));                                     // recovery.c:322-328
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));         // coset_ifft ...
+            RC(dev::fr_mul_inplace_device(ctx, d_e.p, ctx->d_unshift, tot, n));  // ... unscale by 7^-i
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));        // evaluations, cell order
+            if (recovered_cells) RC(dev::fr_to_bytes_batch(ctx, d_img, d_e.p, tot));
+        }
+        OKB(d_bad.down(bad.data(), k));   // the chunk's one wait for the stream: the flags, and d_img is final
         for (size_t i = 0; i < k; i++) {
-            if (status) status[off + i] = bad[i] ? (uint8_t)C_KZG_BADARGS : 0;
-            any_bad |= bad[i] != 0;
+            if (!bad[i]) continue;   // a field element >= r: the row's output is unspecified
+            if (status) status[src.caller_row(c, i)] = (uint8_t)C_KZG_BADARGS;
+            result = C_KZG_BADARGS;
         }
-        if (any_bad) result = C_KZG_BADARGS;  // rows flagged in status[] hold unspecified output
-        if (num_cells != CELLS_PER_EXT_BLOB) {
-            C_KZG_RET ret = recover_cells_gpu(ctx, d_e.p, k, cell_indices, num_cells, s);
-            if (ret != C_KZG_OK) return ret;
-            if (recovered_cells) RC(dev::fr_to_bytes_batch(ctx, d_img, d_e.p, k * n));
-        }
-        if (recovered_cells) {
-            if (piped) {
-                OKB(pipe.push(d_img, recovered_cells + off * CELLS_PER_EXT_BLOB, k * n * 32));
-            } else {
-                OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-                OKB(hipMemcpy(recovered_cells + off * CELLS_PER_EXT_BLOB, d_img, k * n * 32, hipMemcpyDeviceToHost) == hipSuccess);
-            }
-        }
+        if (recovered_cells) OKB(give_back(c, d_img, recovered_cells, n * 32));
         if (recovered_proofs) {
             // cell order is bit-reversed evaluation order: DIT inverse gives the coefficients
             // (poly_lagrange_to_monomial over 8192 points, eip7594.c:270); FK20 reads the low 4096
@@ -1586,13 +1557,8 @@ static C_KZG_RET recover_batch_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZ
             OKB(hipMemcpy2DAsync(d_poly.p, FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), d_e.p, n * sizeof(Fr),
                                  FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), k, hipMemcpyDeviceToDevice,
                                  ctx->stream) == hipSuccess);
-            RC(dev::fk20_proofs_device(ctx, d_proofs, d_poly.p, k));
-            if (piped) {
-                OKB(pipe.push(d_proofs, recovered_proofs + off * CELLS_PER_EXT_BLOB, k * CELLS_PER_EXT_BLOB * 48));
-            } else {
-                OKB(hipMemcpy(recovered_proofs + off * CELLS_PER_EXT_BLOB, d_proofs, k * CELLS_PER_EXT_BLOB * 48,
-                              hipMemcpyDeviceToHost) == hipSuccess);
-            }
+            RC(dev::fk20_proofs_device(ctx, d_proofs, d_poly.p, k));   // (ends in a wait for the stream)
+            OKB(give_back(c, d_proofs, recovered_proofs, CELLS_PER_EXT_BLOB * 48));
         }
         mark.push_back(pipe.pushed_count());
     }
@@ -1606,6 +1572,77 @@ static C_KZG_RET recover_batch_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZ
         (void)hipGetLastError();
     }
     return result;
+}
+
+// The source of the call whose rows all hold the SAME num_cells cells: one index list, one copy in and one run back
+// per chunk.  Everything that depends only on the missing set -- Z over the domain and 1 / Z over the coset, two
+// full-length vectors from the host's vanishing polynomial -- is made once per call, in front of the loop.
+struct RecoverSameCells {
+    static constexpr size_t CH = RECOVER_CHUNK_ROWS, n = FIELD_ELEMENTS_PER_EXT_BLOB;
+    const uint64_t *cell_indices;
+    const Cell *cells;
+    size_t num_cells, num_rows;
+    const KZGSettings *s;
+    ABuf<uint32_t> d_idx;
+    ABuf<Fr> d_zc, d_zev, d_zinv;   // d_zc: the coefficients of Z, a temporary of prepare()
+
+    size_t chunks() const { return (num_rows + CH - 1) / CH; }
+    size_t rows(size_t c) const { return num_rows - c * CH < CH ? num_rows - c * CH : CH; }
+    bool all_full(size_t) const { return num_cells == CELLS_PER_EXT_BLOB; }
+    size_t max_rows() const { return num_rows < CH ? num_rows : CH; }
+    size_t in_bytes() const { return max_rows() * num_cells * BYTES_PER_CELL; }
+    size_t extra_bytes() const { return num_cells * 4 + 3 * (n * sizeof(Fr) + 256); }
+    bool take(Arena &ar) {
+        d_idx = ABuf<uint32_t>(ar, num_cells);
+        d_zc = ABuf<Fr>(ar, n), d_zev = ABuf<Fr>(ar, n), d_zinv = ABuf<Fr>(ar, n);
+        return d_idx.p && d_zc.p && d_zev.p && d_zinv.p;
+    }
+    C_KZG_RET prepare(dev::DeviceCtx *ctx) {
+        std::vector<uint32_t> idx32(num_cells);
+        for (size_t i = 0; i < num_cells; i++) idx32[i] = (uint32_t)cell_indices[i];
+        OKB(d_idx.up(idx32.data(), num_cells));
+        if (num_cells == CELLS_PER_EXT_BLOB) return C_KZG_OK;
+        std::vector<Fr> roots;
+        const Fr *rou = as_fr(s->roots_of_unity);
+        bool have[CELLS_PER_EXT_BLOB] = {false};
+        for (size_t k = 0; k < num_cells; k++) have[cell_indices[k]] = true;
+        for (size_t i = 0; i < CELLS_PER_EXT_BLOB; i++)
+            if (!have[i]) roots.push_back(rou[reverse_bits_limited(CELLS_PER_EXT_BLOB, i) * (n / CELLS_PER_EXT_BLOB)]);
+        if (roots.empty() || roots.size() >= CELLS_PER_EXT_BLOB) return C_KZG_BADARGS;  // recovery.c:103-106
+        std::vector<Fr> shortp, zc(n, Fr::zero()), ones(n, Fr::one());
+        vanishing_poly_from_roots(shortp, roots);
+        for (size_t i = 0; i < shortp.size(); i++) zc[i * FIELD_ELEMENTS_PER_CELL] = shortp[i];
+        OKB(d_zc.up(zc.data(), n));
+        OKB(d_zinv.up(ones.data(), n));
+        OKB(hipMemcpyAsync(d_zev.p, d_zc.p, n * sizeof(Fr), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
+        // Z over the domain, in bit-reversed order = the order of the rows
+        RC(dev::fr_ntt_batch(ctx, d_zev.p, 1, 13, true, false, false));
+        // 1 / Z over the coset (the divisor of recovery.c:322-328, inverted once for the whole call)
+        RC(dev::fr_mul_inplace_device(ctx, d_zc.p, ctx->d_shift, n, n));
+        RC(dev::fr_ntt_batch(ctx, d_zc.p, 1, 13, true, false, false));
+        RC(dev::fr_div_inplace_device(ctx, d_zinv.p, d_zc.p, n));
+        return C_KZG_OK;
+    }
+    C_KZG_RET cells_in(dev::DeviceCtx *ctx, size_t c, uint8_t *d_img, uint8_t *d_in) {
+        const size_t k = rows(c);
+        OKB(hipMemcpyAsync(d_in, cells + c * CH * num_cells, k * num_cells * BYTES_PER_CELL, hipMemcpyHostToDevice,
+                           ctx->stream) == hipSuccess);
+        RC(dev::scatter_cells_device(ctx, d_img, d_in, d_idx.p, (uint32_t)num_cells, k));
+        return C_KZG_OK;
+    }
+    int mul_z(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_inplace_device(ctx, d_e, d_zev.p, rows(c) * n, n); }
+    int mul_zinv(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_inplace_device(ctx, d_e, d_zinv.p, rows(c) * n, n); }
+    template <class F>
+    bool for_each_run(size_t c, F &&f) const { return f((size_t)0, c * CH, rows(c)); }
+    size_t caller_row(size_t c, size_t i) const { return c * CH + i; }
+};
+
+static C_KZG_RET recover_batch_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs,
+                                  uint8_t *status, const uint64_t *cell_indices, const Cell *cells,
+                                  uint64_t num_cells, uint64_t num_blobs, const KZGSettings *s) {
+    if (status) memset(status, 0, (size_t)num_blobs);
+    return recover_chunks(ctx, recovered_cells, recovered_proofs, status, C_KZG_OK,
+                          RecoverSameCells{cell_indices, cells, (size_t)num_cells, (size_t)num_blobs, s});
 }
 
 extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_batch(Cell *recovered_cells, KZGProof *recovered_proofs,
@@ -1632,131 +1669,73 @@ extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_batch(Cell *recovered
     });
 }
 
-// recover_batch_on for rows that hold different cells: caller rows [lo, hi) of the call on one device.  The plan
-// (recover_rows_plan.hpp) names the valid rows, their distinct sets and every cell's place; per chunk the GPU makes the
-// per-cell values of Z and 1 / Z for each distinct set (recover_set_factors.hpp) and all rows of the chunk, whatever
-// they hold, go through the five transforms of recover_cells (recovery.c:200-365) and one FK20 batch together.  No
-// field arithmetic on the host.  A chunk whose rows all hold 128 cells skips the transforms like the uniform call.
-static C_KZG_RET recover_rows_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs, uint8_t *status,
-                                 const uint64_t *cell_indices, const Cell *cells, const uint64_t *row_start, uint64_t lo,
-                                 uint64_t hi) {
-    const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
-    const size_t CH = 512;   // as recover_batch_on
-    RecoverRowsPlan plan;
-    build_recover_rows_plan(plan, cell_indices, row_start + lo, hi - lo, CH);
-    C_KZG_RET result = plan.any_invalid ? C_KZG_BADARGS : C_KZG_OK;
-    if (status) {
-        for (uint64_t r = lo; r < hi; r++) status[r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
+// The source of the call by rows: caller rows [lo, hi) of the call on one device.  The plan (recover_rows_plan.hpp)
+// names the valid rows, their distinct sets and every cell's place; per chunk the GPU makes the per-cell values of Z
+// and 1 / Z for each distinct set (recover_set_factors.hpp) and all rows of the chunk, whatever they hold, go through
+// the transforms and one FK20 batch together.  No field arithmetic on the host.
+struct RecoverByRows {
+    const RecoverRowsPlan &plan;
+    const Cell *cells;
+    uint64_t lo;
+    ABuf<Fr> d_zdom, d_zinv;      // 128 factors per set
+    ABuf<uint32_t> d_meta;        // row_set [k] | cell_dst [cells] | set_mask [4 sets]
+    std::vector<uint32_t> meta;
+
+    size_t chunks() const { return plan.chunks.size(); }
+    size_t rows(size_t c) const { return plan.chunks[c].rows(); }
+    bool all_full(size_t c) const { return plan.chunks[c].all_full; }
+    size_t max_rows() const { return plan.max_rows; }
+    size_t in_bytes() const { return plan.max_cells * BYTES_PER_CELL; }
+    // set ids per row; target per cell; mask + 2 x 128 factors per set
+    size_t extra_bytes() const {
+        return plan.max_rows * 4 + plan.max_cells * 4 + plan.max_sets * (16 + 2 * CELLS_PER_EXT_BLOB * sizeof(Fr));
     }
-    if (plan.chunks.empty()) return result;
-    const size_t m = plan.max_rows, mc = plan.max_cells, ms = plan.max_sets;
-    const bool piped = m > 8;
-    const int nbuf = piped ? 2 : 1;
-    std::vector<uint32_t> bad(m), meta;
-    Arena &ar = ctx->api_arena;
-    // image(s) + Fr + flags + set ids per row; input + target per cell; mask + 2 x 128 factors per set; proofs
-    OKM(ar.begin(m * (nbuf * n * 32 + n * sizeof(Fr) + 4 + 4) + mc * (BYTES_PER_CELL + 4) +
-                 ms * (16 + 2 * CELLS_PER_EXT_BLOB * sizeof(Fr)) +
-                 (recovered_proofs ? m * (nbuf * CELLS_PER_EXT_BLOB * 48 + FIELD_ELEMENTS_PER_BLOB * sizeof(Fr)) : 0) + 4096));
-    ArenaTrim trim(ar);
-    ABuf<uint8_t> d_img0(ar, m * n * 32), d_img1(ar, piped ? m * n * 32 : 1), d_in(ar, mc * BYTES_PER_CELL);
-    ABuf<uint8_t> d_pr0(ar, recovered_proofs ? m * CELLS_PER_EXT_BLOB * 48 : 1);
-    ABuf<uint8_t> d_pr1(ar, recovered_proofs && piped ? m * CELLS_PER_EXT_BLOB * 48 : 1);
-    ABuf<Fr> d_e(ar, m * n), d_poly(ar, recovered_proofs ? m * FIELD_ELEMENTS_PER_BLOB : 1);
-    ABuf<Fr> d_zdom(ar, ms * CELLS_PER_EXT_BLOB), d_zinv(ar, ms * CELLS_PER_EXT_BLOB);
-    ABuf<uint32_t> d_bad(ar, m), d_meta(ar, m + mc + 4 * ms);   // meta: row_set [k] | cell_dst [cells] | set_mask [4 sets]
-    OKM(d_img0.p && d_img1.p && d_in.p && d_pr0.p && d_pr1.p && d_e.p && d_poly.p && d_zdom.p && d_zinv.p && d_bad.p &&
-        d_meta.p);
-    uint8_t *img_buf[2] = {d_img0.p, piped ? d_img1.p : d_img0.p}, *pr_buf[2] = {d_pr0.p, piped ? d_pr1.p : d_pr0.p};
-    // the pipe's page-locked staging, taken here so that running out of it is C_KZG_MALLOC like every other allocation
-    if (piped) OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, OutPipe::PIECE));
-    OutPipe pipe(ctx);
-    struct Drain {  // nothing may still read the arena or the plan when this function leaves, on any path
-        dev::DeviceCtx *c;
-        OutPipe &p;
-        ~Drain() {
-            (void)p.finish();
-            (void)dev::sync_stream(c->stream);
-        }
-    } drain{ctx, pipe};
-    std::vector<size_t> mark;
-    // the outputs of a chunk go back run by run: device rows are packed, caller rows keep the gaps of invalid rows
-    auto give_back = [&](const RecoverRowsChunk &ch, const uint8_t *d_src, uint8_t *h_dst, size_t per_row) -> bool {
-        for (const RecoverRowsRun &run : ch.runs) {
-            const uint8_t *src = d_src + run.dev_row * per_row;
-            uint8_t *dst = h_dst + (size_t)(lo + run.caller_row) * per_row;
-            if (piped) {
-                if (!pipe.push(src, dst, run.rows * per_row)) return false;
-            } else if (hipMemcpy(dst, src, run.rows * per_row, hipMemcpyDeviceToHost) != hipSuccess) {
-                return false;
-            }
-        }
-        return true;
-    };
-    OKB(hipEventRecord(ctx->ev[1], ctx->stream) == hipSuccess);
-    for (size_t chunk = 0; chunk < plan.chunks.size(); chunk++) {
-        const RecoverRowsChunk &ch = plan.chunks[chunk];
-        const size_t k = ch.rows(), nc = ch.cells(), ns = ch.sets();
-        uint8_t *d_img = img_buf[chunk & 1], *d_proofs = pr_buf[chunk & 1];
-        const uint32_t *d_row_set = d_meta.p, *d_cell_dst = d_meta.p + k, *d_set_mask = d_meta.p + k + nc;
-        if (piped && chunk >= 2) pipe.wait_for(mark[chunk - 2]);
+    bool take(Arena &ar) {
+        d_zdom = ABuf<Fr>(ar, plan.max_sets * CELLS_PER_EXT_BLOB), d_zinv = ABuf<Fr>(ar, plan.max_sets * CELLS_PER_EXT_BLOB);
+        d_meta = ABuf<uint32_t>(ar, plan.max_rows + plan.max_cells + 4 * plan.max_sets);
+        return d_zdom.p && d_zinv.p && d_meta.p;
+    }
+    C_KZG_RET prepare(dev::DeviceCtx *) { return C_KZG_OK; }
+    C_KZG_RET cells_in(dev::DeviceCtx *ctx, size_t c, uint8_t *d_img, uint8_t *d_in) {
+        const RecoverRowsChunk &ch = plan.chunks[c];
+        const uint32_t *d_cell_dst = d_meta.p + ch.rows(), *d_set_mask = d_cell_dst + ch.cells();
         meta.clear();
         meta.insert(meta.end(), ch.row_set.begin(), ch.row_set.end());
         meta.insert(meta.end(), ch.cell_dst.begin(), ch.cell_dst.end());
         meta.insert(meta.end(), ch.set_mask.begin(), ch.set_mask.end());
-        // (the stream was drained at the end of the chunk before: nothing reads d_meta or `meta` any more)
+        // (the stream was waited for in the chunk before, after its last use of d_meta: nothing reads it or `meta` any more)
         OKB(hipMemcpyAsync(d_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
         for (const RecoverRowsRun &run : ch.runs) {
-            OKB(hipMemcpyAsync(d_in.p + (size_t)run.dev_cell * BYTES_PER_CELL, cells + run.src_cell,
+            OKB(hipMemcpyAsync(d_in + (size_t)run.dev_cell * BYTES_PER_CELL, cells + run.src_cell,
                                (size_t)run.cells * BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
         }
-        OKB(hipMemsetAsync(d_img, 0, k * n * 32, ctx->stream) == hipSuccess);
-        OKB(hipMemsetAsync(d_bad.p, 0, k * 4, ctx->stream) == hipSuccess);
-        if (!ch.all_full) RC(dev::recover_set_factors_enqueue(ctx, d_zdom.p, d_zinv.p, d_set_mask, ns));
-        RC(dev::scatter_cells_rows_enqueue(ctx, d_img, d_in.p, d_cell_dst, nc));
-        RC(dev::bytes_to_fr_batch(ctx, d_e.p, d_bad.p, d_img, k * n, (uint32_t)n));
-        if (!ch.all_full) {
-            RC(dev::fr_mul_cell_factor_enqueue(ctx, d_e.p, d_zdom.p, d_row_set, k));   // (E * Z)(w^i)
-            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));               // -> coefficients
-            RC(dev::fr_mul_inplace_device(ctx, d_e.p, ctx->d_shift, k * n, n));        // coset_fft: scale by 7^i ...
-            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));              // ... and transform
-            RC(dev::fr_mul_cell_factor_enqueue(ctx, d_e.p, d_zinv.p, d_row_set, k));   // recovery.c:322-328
-            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));               // coset_ifft ...
-            RC(dev::fr_mul_inplace_device(ctx, d_e.p, ctx->d_unshift, k * n, n));      // ... unscale by 7^-i
-            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));              // evaluations, cell order
-            if (recovered_cells) RC(dev::fr_to_bytes_batch(ctx, d_img, d_e.p, k * n));
-        }
-        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-        OKB(d_bad.down(bad.data(), k));
-        for (size_t i = 0; i < k; i++) {
-            if (!bad[i]) continue;   // a field element >= r: the row's output is unspecified
-            if (status) status[lo + ch.row_caller[i]] = (uint8_t)C_KZG_BADARGS;
-            result = C_KZG_BADARGS;
-        }
-        if (recovered_cells) OKB(give_back(ch, d_img, reinterpret_cast<uint8_t *>(recovered_cells), n * 32));
-        if (recovered_proofs) {
-            // cell order is bit-reversed evaluation order: DIT inverse gives the coefficients
-            // (poly_lagrange_to_monomial over 8192 points, eip7594.c:270); FK20 reads the low 4096
-            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));
-            OKB(hipMemcpy2DAsync(d_poly.p, FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), d_e.p, n * sizeof(Fr),
-                                 FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), k, hipMemcpyDeviceToDevice,
-                                 ctx->stream) == hipSuccess);
-            RC(dev::fk20_proofs_device(ctx, d_proofs, d_poly.p, k));
-            if (!piped) OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-            OKB(give_back(ch, d_proofs, reinterpret_cast<uint8_t *>(recovered_proofs), CELLS_PER_EXT_BLOB * 48));
-        }
-        mark.push_back(pipe.pushed_count());
+        if (!ch.all_full) RC(dev::recover_set_factors_enqueue(ctx, d_zdom.p, d_zinv.p, d_set_mask, ch.sets()));
+        RC(dev::scatter_cells_rows_enqueue(ctx, d_img, d_in, d_cell_dst, ch.cells()));
+        return C_KZG_OK;
     }
-    OKB(hipEventRecord(ctx->ev[4], ctx->stream) == hipSuccess);
-    if (pipe.finish() != C_KZG_OK) return C_KZG_ERROR;
-    OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-    {   // ckzg_hip_last_kernel_ms: as recover_batch_on
-        float ms_dev;
-        if (hipEventElapsedTime(&ms_dev, ctx->ev[1], ctx->ev[4]) == hipSuccess) ctx->last_ms[3] = ms_dev;
-        if (recovered_proofs) dev::fk20_collect_times(ctx);
-        (void)hipGetLastError();
+    int mul_z(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_cell_factor_enqueue(ctx, d_e, d_zdom.p, d_meta.p, rows(c)); }
+    int mul_zinv(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_cell_factor_enqueue(ctx, d_e, d_zinv.p, d_meta.p, rows(c)); }
+    template <class F>
+    bool for_each_run(size_t c, F &&f) const {
+        for (const RecoverRowsRun &run : plan.chunks[c].runs) {
+            if (!f((size_t)run.dev_row, (size_t)(lo + run.caller_row), (size_t)run.rows)) return false;
+        }
+        return true;
     }
-    return result;
+    size_t caller_row(size_t c, size_t i) const { return (size_t)(lo + plan.chunks[c].row_caller[i]); }
+};
+
+// Structurally invalid rows get C_KZG_BADARGS here and no device row: they are neither copied, computed nor written
+static C_KZG_RET recover_rows_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs, uint8_t *status,
+                                 const uint64_t *cell_indices, const Cell *cells, const uint64_t *row_start, uint64_t lo,
+                                 uint64_t hi) {
+    RecoverRowsPlan plan;
+    build_recover_rows_plan(plan, cell_indices, row_start + lo, hi - lo, RECOVER_CHUNK_ROWS);
+    if (status) {
+        for (uint64_t r = lo; r < hi; r++) status[r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
+    }
+    return recover_chunks(ctx, recovered_cells, recovered_proofs, status, plan.any_invalid ? C_KZG_BADARGS : C_KZG_OK,
+                          RecoverByRows{plan, cells, lo});
 }
 
 extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs,

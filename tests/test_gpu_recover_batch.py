@@ -85,3 +85,31 @@ def test_batch_recover_argument_checks(hip):
     idx = (C.c_uint64 * 64)(*range(64))
     assert f(None, None, None, idx, b"", C.c_uint64(64), C.c_uint64(1), hip.sp) == 1   # no output requested
     assert f(rc, None, None, idx, b"", C.c_uint64(64), C.c_uint64(0), hip.sp) == 0     # empty batch
+
+
+def test_status_and_outputs_across_the_chunk_edge(hip):
+    """514 rows from two blobs, all holding the even columns: chunks of 512 + 2.  Rows 3 and 513 carry a field element
+    >= r; 513 is the second device row of the second chunk, so its flag and the rows around the edge only land where
+    they belong if device rows are mapped to caller rows with the chunk's offset."""
+    nb, cs, ps = 514, 128 * 2048, 128 * 48
+    blobs, full = _rows(hip, 65, 2)
+    keep = list(range(0, 128, 2))
+    cut = [b"".join(full[b][0][i] for i in keep) for b in range(2)]
+    blob_of = [(r + r // 3) % 2 for r in range(nb)]
+    assert blob_of[511] != blob_of[512]
+    data = bytearray(b"".join(cut[b] for b in blob_of))
+    r_mod = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
+    for r, cell, elem in ((3, 5, 1), (513, 63, 63)):
+        at = (r * len(keep) + cell) * 2048 + elem * 32
+        data[at:at + 32] = r_mod.to_bytes(32, "big")
+    f = hip.lib.ckzg_hip_recover_cells_and_kzg_proofs_batch
+    f.restype = C.c_int
+    rc, rp = C.create_string_buffer(nb * cs), C.create_string_buffer(nb * ps)
+    st = (C.c_uint8 * nb)(*([0xa5] * nb))
+    ret = f(rc, rp, st, (C.c_uint64 * len(keep))(*keep), bytes(data), C.c_uint64(len(keep)), C.c_uint64(nb), hip.sp)
+    assert ret == 1  # C_KZG_BADARGS
+    assert [r for r in range(nb) if st[r] != 0] == [3, 513] and st[3] == 1 and st[513] == 1
+    craw, praw = rc.raw, rp.raw
+    for r in (0, 2, 4, 511, 512):
+        assert craw[r * cs:(r + 1) * cs] == b"".join(full[blob_of[r]][0]), "cells of row %d" % r
+        assert praw[r * ps:(r + 1) * ps] == b"".join(full[blob_of[r]][1]), "proofs of row %d" % r

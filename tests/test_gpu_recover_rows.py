@@ -266,3 +266,46 @@ def test_concurrent_callers(hip, full):
         rc, rp, st = results[t]
         assert st == [0] * len(calls[t][0])
         _expect_rows(full, calls[t][1], rc, rp)
+
+
+def test_device_rows_shifted_against_caller_rows_across_the_chunk_edge(hip, full):
+    """515 rows over three sets.  Row 1 holds 63 cells: it is invalid and gets no device row, so the first chunk of 512
+    device rows ends at caller row 512 and from row 2 on device row and caller row differ.  Rows 512 (the last device
+    row of the first chunk) and 513 (the first of the second) carry a field element >= r."""
+    sets = _sets()
+    names = ["random_70", "even", "last_64"]
+    nr = 515
+    blob_of = [(3 * r + r // 7) % 4 for r in range(nr)]
+    keeps = [sets[names[(r + r // 5) % 3]] for r in range(nr)]
+    rows = [(keep, [full[blob_of[r]][0][c] for c in keep]) for r, keep in enumerate(keeps)]
+    rows[1] = (list(range(63)), [full[blob_of[1]][0][c] for c in range(63)])
+    for r, at, elem in ((512, 0, 0), (513, 40, 17)):
+        cell = bytearray(rows[r][1][at])
+        cell[elem * 32:(elem + 1) * 32] = R.to_bytes(32, "big")
+        rows[r][1][at] = bytes(cell)
+    assert len({tuple(rows[r][0]) for r in (0, 2, 511, 514)}) == 3
+    ret, craw, praw, st = _raw_call(hip, rows)
+    assert ret == 1
+    assert [r for r in range(nr) if st[r] != 0] == [1, 512, 513] and st[1] == st[512] == st[513] == 1
+    assert craw[CELLS:2 * CELLS] == b"\xa5" * CELLS and praw[PROOFS:2 * PROOFS] == b"\xa5" * PROOFS
+    for r in (0, 2, 511, 514):
+        assert craw[r * CELLS:(r + 1) * CELLS] == b"".join(full[blob_of[r]][0]), "cells of row %d" % r
+        assert praw[r * PROOFS:(r + 1) * PROOFS] == b"".join(full[blob_of[r]][1]), "proofs of row %d" % r
+
+
+@pytest.mark.parametrize("name", ["random_70", "all_128"])
+@pytest.mark.parametrize("nr", [8, 9])
+def test_piped_boundary_every_output_form_both_calls(hip, full, nr, name):
+    """8 rows are the last call that copies its outputs back directly, 9 the first that drains them through the pipe;
+    all_128 at 9 rows is the piped path that skips the transforms and returns the scattered image.  The batch call
+    and the rows call, each as cells + proofs, cells only and proofs only, give the full rows."""
+    keep = _sets()[name]
+    blobs = [(r + r // 4) % 4 for r in range(nr)]
+    per_row = [[full[b][0][c] for c in keep] for b in blobs]
+    want_c, want_p = [full[b][0] for b in blobs], [full[b][1] for b in blobs]
+    for want_cells, want_proofs in ((True, True), (True, False), (False, True)):
+        bc, bp = hip.recover_cells_and_kzg_proofs_batch(keep, per_row, want_cells, want_proofs)
+        rc, rp, st = hip.recover_cells_and_kzg_proofs_rows([(keep, cells) for cells in per_row], want_cells, want_proofs)
+        assert st == [0] * nr
+        assert bc == rc == (want_c if want_cells else None)
+        assert bp == rp == (want_p if want_proofs else None)

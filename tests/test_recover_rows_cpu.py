@@ -207,7 +207,7 @@ def test_factors_are_the_two_products(h, name):
 
 
 def test_factors_are_the_vanishing_polynomial_of_the_existing_route(h):
-    """Z as recover_cells_gpu builds it: the recurrence of vanishing_poly_from_roots over the roots
+    """Z as RecoverSameCells::prepare builds it: the recurrence of vanishing_poly_from_roots over the roots
     w^(64 brp7(j)) of the missing cells j, its coefficients spread 64 apart, evaluated at w^brp13(p) (the domain in
     the order in which the data is held) and at 7 w^brp13(p) (the coset)."""
     cols = _sets()["random_70"]
