@@ -876,6 +876,10 @@ static uint32_t pick_pairs_per_block_fixed(size_t nvec, uint32_t pairs_per_vec) 
     }
     return pick_pairs_per_block(nvec, pairs_per_vec);
 }
+// the choice of either picker, for code outside this file that has to know the launch shape (the G1 stage tests)
+uint32_t msm_pairs_per_block(size_t nvec, uint32_t pairs_per_vec, bool fixed) {
+    return fixed ? pick_pairs_per_block_fixed(nvec, pairs_per_vec) : pick_pairs_per_block(nvec, pairs_per_vec);
+}
 // bytes of partial sums of nvec vectors cut into bpv blocks each, plus one reduced sum per vector: raw 57-word records
 // when k_msm_fold_finalize folds them (bpv > 8), reduced XYZZ points otherwise
 static size_t partials_bytes(size_t nvec, uint32_t bpv) {
