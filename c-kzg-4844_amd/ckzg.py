@@ -190,6 +190,25 @@ class Kzg:
             raise KzgError("ckzg_hip_verify_blob_kzg_proof_batch_locate -> C_KZG_RET %d" % ret)
         return [bool(v) for v in ok[:n]], [int(v) for v in st[:n]], [int(v) for v in stats]
 
+    def verify_cell_kzg_proof_batch_locate(self, commitments, cell_indices, cells, proofs):
+        """ckzg_hip_verify_cell_kzg_proof_batch_locate: one verify_cell_kzg_proof_batch verdict per cell at the cost of
+        one batch check when everything verifies.  Returns (ok, status, stats) as verify_kzg_proof_batch_locate does."""
+        n = len(cells)
+        _check(len(commitments) == n and len(cell_indices) == n and len(proofs) == n, "list lengths")
+        for c in cells:
+            _check(len(c) == BYTES_PER_CELL, "cell")
+        for c in list(commitments) + list(proofs):
+            _check(len(c) == 48, "commitment/proof")
+        ok = (C.c_bool * max(n, 1))()
+        st = (C.c_uint8 * max(n, 1))()
+        stats = (C.c_uint64 * 3)()
+        ret = self._fn("ckzg_hip_verify_cell_kzg_proof_batch_locate")(
+            ok, st, stats, b"".join(commitments), (C.c_uint64 * max(n, 1))(*cell_indices), b"".join(cells), b"".join(proofs),
+            C.c_uint64(n), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_verify_cell_kzg_proof_batch_locate -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:n]], [int(v) for v in st[:n]], [int(v) for v in stats]
+
     def g1_prefix_sums(self, points):
         """ckzg_hip_g1_prefix_sums: out[i] = points[0] + ... + points[i], each a g1_t (144 bytes, Jacobian) in and out."""
         n = len(points)

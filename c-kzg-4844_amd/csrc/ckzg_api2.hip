@@ -2867,7 +2867,7 @@ struct LocateBufs {
     ABuf<G1Affine> d_pts, d_lhs, d_negp, d_pref;
     ABuf<G1XYZZ> d_xyzz, d_ab, d_scan;
     bool tab_up = false;   // the line tables of the per-lane check are uploaded by the first chunk that hands over
-    static constexpr size_t TAB = 4 * (size_t)MILLER_STEPS * 2;   // Fp: lam[68], c[68] of [1]_2, then of [s]_2, Fp2 each
+    static constexpr size_t TAB = 4 * (size_t)MILLER_STEPS * 2;   // Fp: lam[68], c[68] of [1]_2, then of the second point, Fp2 each
     static size_t bytes(size_t m) {
         return TAB * sizeof(Fp) + 2 * m * sizeof(Fp) + m * (2 * 48 + 4 + 2) + 6 * m * sizeof(G1Affine) +
                (3 * m + dev::g1_prefix_scan_scratch_points(m, 2)) * sizeof(G1XYZZ) + 13 * 256;
@@ -2898,8 +2898,9 @@ C_KZG_RET locate_points_in(dev::DeviceCtx *ctx, LocateBufs &b, const Bytes48 *cb
 // by r^i, scans, brings the 2k prefix points home and bisects on the host pool; what the bisection leaves open when it
 // reaches locate_max_checks goes through the per-lane check once (P1 and -proof are still on the device).
 // stats: [0] += host range checks, [1] += items settled by the per-lane check, [2] += 1.
+// q2: the second G2 point of the check, [s]_2 for the point and blob forms, [s^64]_2 for the cell form.
 C_KZG_RET locate_chunk_from_lhs(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t *stats, LocateBufs &b, const Fr &r, size_t k,
-                                const PreparedG2 *pg) {
+                                const PreparedG2 *pg, const host::G2Prepared &q2) {
     RC(dev::batch_to_affine_device(ctx, b.d_lhs.p, b.d_xyzz.p, b.d_prefix.p, k));
     RC(dev::locate_scale_enqueue(ctx, b.d_ab.p, b.d_lhs.p, b.d_negp.p, r, k));
     RC(dev::g1_prefix_scan_enqueue(ctx, b.d_ab.p, b.d_scan.p, k, 2));
@@ -2908,14 +2909,14 @@ C_KZG_RET locate_chunk_from_lhs(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, 
     std::vector<uint8_t> bad(k);
     OKB(hipMemcpyAsync(bad.data(), b.d_bad.p, k, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
     OKB(b.d_pref.down(pref.data(), 2 * k));
-    // e(PA[hi] - PA[lo], [1]_2) * e(-(PB[hi] - PB[lo]), [s]_2) == 1
+    // e(PA[hi] - PA[lo], [1]_2) * e(-(PB[hi] - PB[lo]), q2) == 1
     auto diff = [&](const G1Affine *p, size_t lo, size_t hi) {
         const G1Jac top = jac_from_affine(p[hi - 1]);
         return lo ? jac_madd(top, affine_neg(p[lo - 1])) : top;
     };
     auto range_ok = [&](size_t lo, size_t hi) {
         return pairing_product_is_one(jac_to_affine_fast(diff(pref.data(), lo, hi)), pg->gen,
-                                      jac_to_affine_fast(jac_neg(diff(pref.data() + k, lo, hi))), pg->s1);
+                                      jac_to_affine_fast(jac_neg(diff(pref.data() + k, lo, hi))), q2);
     };
     const int64_t opt = g_locate_max_checks.load(std::memory_order_relaxed);
     const LocateOutcome res = locate_bisect(ok, bad.data(), k, (uint64_t)opt, range_ok,
@@ -2925,7 +2926,7 @@ C_KZG_RET locate_chunk_from_lhs(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, 
     if (!res.open.empty()) {
         if (!b.tab_up) {
             std::vector<Fp> tab(LocateBufs::TAB);
-            const host::G2Prepared *q[2] = {&pg->gen, &pg->s1};
+            const host::G2Prepared *q[2] = {&pg->gen, &q2};
             for (int j = 0; j < 2; j++) {
                 memcpy(&tab[(size_t)(2 * j) * MILLER_STEPS * 2], q[j]->lam, sizeof q[j]->lam);
                 memcpy(&tab[(size_t)(2 * j + 1) * MILLER_STEPS * 2], q[j]->c, sizeof q[j]->c);
@@ -2979,7 +2980,7 @@ C_KZG_RET locate_point_proofs_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status,
         // the chunk's challenge, hashed underneath the kernels above (locate_plan.hpp)
         uint8_t digest[32];
         locate_point_digest<Sha256>(digest, cb[off].bytes, zs[off].bytes, ys[off].bytes, pb[off].bytes, k);
-        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg));
+        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg, pg->s1));
         if (ret != C_KZG_OK && ret != C_KZG_BADARGS) return ret;
     }
     return ret;
@@ -3033,7 +3034,102 @@ C_KZG_RET locate_blob_proofs_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, 
         OKB(d_y.down(y.data(), k));
         uint8_t digest[32];
         host_batch_digest(digest, k, cb + off, pb + off, z.data(), y.data());
-        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg));
+        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg, pg->s1));
+        if (ret != C_KZG_OK && ret != C_KZG_BADARGS) return ret;
+    }
+    return ret;
+}
+
+// The cell form: per item P1_i = C_i - [I_i(s)]_1 + [h_i^64] proof_i against [s^64]_2 (eip7594.c:825-974 on a batch of
+// one).  [I_i(s)]_1 is a 64-term fixed-base sum over g1_values_monomial[0..63] per cell (msm_small_vectors_device, every
+// vector on the same 64-point table); the table is this slot's own, built by its first call and kept until the slot goes.
+// Window width (tools/bench_cell_locate.py; profiles/cell_locate_bench_first.json, the run that chose it, all-good batches of 8,192 / 16,384 cells):
+// 8 bits 16.64 / 21.53 ms, 10 bits 16.25 / 20.68, 12 bits 15.87 / 20.05, for 12.6 / 41 / 138 MB per slot (8 slots per
+// device by default, up to 64): 10 bits takes more than half of what the widest table gains at under a third of its memory.
+// The fused interpolation kernel against the three-pass form (same record, two runs each): 16.83, 16.76 against 16.75,
+// 16.74 ms at 8,192 and 21.66, 21.60 against 21.54, 21.54 at 16,384: the three-pass form is 0.02-0.13 ms ahead in every
+// pair, under 1 % of the call and at most twice the spread of two runs of one form (0.07 ms).  The fused kernel ships (one
+// launch, no second buffer); the three-pass form stays reachable in the A/B build, and the fused kernel's launch shape (one
+// 64-lane workgroup per cell) is what to look at next.
+C_KZG_RET locate_cells_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t *stats, const Bytes48 *cb,
+                          const uint64_t *cell_indices, const Cell *cells, const Bytes48 *pb, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++) ok[i] = false;
+    if (n == 0) return C_KZG_OK;
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    static const int table_wbits = (int)dev::ab_knob("CKZG_HIP_CELL_LOCATE_WBITS", 10);
+    static const bool fused = dev::ab_knob("CKZG_HIP_CELL_INTERP_FUSED", 1) != 0;
+    const size_t l = FIELD_ELEMENTS_PER_CELL;
+    if (!ctx->cell_interp.d_table) {
+        // (a failed build leaves d_table null and nothing allocated: the next call builds it)
+        RC(dev::build_fixed_base_table(ctx, &ctx->cell_interp, ctx->d_mono, (int)l, table_wbits));
+    }
+    const dev::FixedBaseTable &t = ctx->cell_interp;
+    const uint64_t CH = CKZG_HIP_CELL_LOCATE_CHUNK_CELLS;
+    const uint64_t m = n < CH ? n : CH, mpad = (m + 63) / 64 * 64;
+    const size_t digits_per_cell = (size_t)t.nwin * l;
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(LocateBufs::bytes(m) + m * (size_t)BYTES_PER_CELL + mpad * l * sizeof(Fr) + 3 * m * 4 + m * digits_per_cell * 2 +
+                 m * sizeof(G1XYZZ) + 8 * 256));
+    ArenaTrim trim(ar);
+    LocateBufs b;
+    OKM(b.take(ar, m));
+    ABuf<uint8_t> d_cells(ar, m * (size_t)BYTES_PER_CELL);   // (the three-pass form reuses it for its canonical coefficients)
+    ABuf<Fr> d_cellfr(ar, mpad * l);
+    ABuf<uint32_t> d_meta(ar, 2 * m), d_cbad(ar, m);         // column [k] | commitment [k]
+    ABuf<int16_t> d_digits(ar, m * digits_per_cell);
+    ABuf<G1XYZZ> d_interp(ar, m);
+    OKM(d_cells.p && d_cellfr.p && d_meta.p && d_cbad.p && d_digits.p && d_interp.p);
+    std::vector<uint32_t> meta(2 * m);
+    std::vector<uint8_t> leaves(32 * m);
+    std::vector<Bytes48> uniq;
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the arena's reuse
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t off = 0; off < n; off += CH) {
+        const uint64_t k = n - off < CH ? n - off : CH;
+        // the chunk's distinct commitments: decompressed and subgroup-tested once each
+        uniq.clear();
+        {
+            std::unordered_map<std::string_view, uint32_t> ids;
+            ids.reserve(256);
+            for (uint64_t i = 0; i < k; i++) {
+                auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(cb[off + i].bytes), 48), (uint32_t)uniq.size());
+                if (it.second) uniq.push_back(cb[off + i]);
+                meta[k + i] = it.first->second;
+                meta[i] = cell_indices[off + i] < CELLS_PER_EXT_BLOB ? (uint32_t)cell_indices[off + i] : (uint32_t)CELLS_PER_EXT_BLOB;
+            }
+        }
+        const size_t nc = uniq.size();
+        uint8_t digest[32];
+        {
+            // the leaves of the chunk's challenge on the host pool (locate_plan.hpp), underneath the copies and kernels
+            BackgroundFor hashes;
+            hashes.what = "cell locate leaf hash jobs";
+            hashes.n = k;
+            hashes.fn = [&](size_t i) {
+                locate_cell_leaf<Sha256>(&leaves[32 * i], cb[off + i].bytes, cell_indices[off + i], cells[off + i].bytes, pb[off + i].bytes);
+            };
+            hashes.start();
+            // (all copies from pageable memory first: such a copy returns only when it is done)
+            OKB(hipMemcpyAsync(b.d_in48.p, pb + off, k * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            OKB(hipMemcpyAsync(b.d_in48.p + k * 48, uniq.data(), nc * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            OKB(hipMemcpyAsync(d_meta.p, meta.data(), 2 * k * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            OKB(hipMemcpyAsync(d_cells.p, cells + off, k * (size_t)BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            // proofs [0, k), distinct commitments [k, k + nc): flags in d_st[0, k + nc) and d_st[2k, 2k + k + nc)
+            RC(dev::decompress_g1_batch_device(ctx, b.d_pts.p, b.d_st.p, b.d_in48.p, k + nc));
+            RC(dev::subgroup_g1_batch_device(ctx, b.d_st.p + 2 * k, b.d_pts.p, k + nc));
+            OKB(hipMemsetAsync(d_cbad.p, 0, k * 4, ctx->stream) == hipSuccess);
+            RC(dev::bytes_to_fr_batch(ctx, d_cellfr.p, d_cbad.p, d_cells.p, k * l, (uint32_t)l));
+            RC(dev::cell_interp_digits_enqueue(ctx, d_digits.p, d_cellfr.p, d_meta.p, k, t.wbits, t.twin, fused,
+                                               reinterpret_cast<uint32_t *>(d_cells.p)));
+            RC(dev::msm_small_vectors_device(ctx, t, d_interp.p, d_digits.p, k, (uint32_t)l, 1));
+            RC(dev::cell_lhs_enqueue(ctx, b.d_xyzz.p, b.d_negp.p, b.d_bad.p, b.d_pts.p, b.d_st.p, b.d_st.p + 2 * k, d_interp.p,
+                                     d_meta.p, d_meta.p + k, d_cbad.p, k));
+            hashes.finish();
+            locate_cell_root<Sha256>(digest, leaves.data(), k);
+        }
+        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg,
+                                               pg->s64));
         if (ret != C_KZG_OK && ret != C_KZG_BADARGS) return ret;
     }
     return ret;
@@ -3081,6 +3177,21 @@ extern "C" C_KZG_RET ckzg_hip_verify_blob_kzg_proof_batch_locate(bool *ok, uint8
         return locate_entry(stats, n, 1, s, [&](dev::DeviceCtx *ctx, uint64_t *st, uint64_t lo, uint64_t hi) {
             return locate_blob_proofs_on(ctx, ok + lo, status ? status + lo : nullptr, st, blobs + lo, commitments_bytes + lo,
                                          proofs_bytes + lo, hi - lo);
+        });
+    });
+}
+
+extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats,
+                                                                const Bytes48 *commitments_bytes, const uint64_t *cell_indices,
+                                                                const Cell *cells, const Bytes48 *proofs_bytes, uint64_t num_cells,
+                                                                const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_cells == 0) return C_KZG_OK;
+        if (!ok || !commitments_bytes || !cell_indices || !cells || !proofs_bytes) return C_KZG_BADARGS;
+        return locate_entry(stats, num_cells, 64, s, [&](dev::DeviceCtx *ctx, uint64_t *st, uint64_t lo, uint64_t hi) {
+            return locate_cells_on(ctx, ok + lo, status ? status + lo : nullptr, st, commitments_bytes + lo, cell_indices + lo,
+                                   cells + lo, proofs_bytes + lo, hi - lo);
         });
     });
 }

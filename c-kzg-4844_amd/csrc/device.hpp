@@ -337,6 +337,8 @@ struct DeviceCtx {
     size_t h_out_bytes = 0;
     FixedBaseTable commit;        // over g1_values_lagrange_brp (4096 points)
     FixedBaseTable mono;          // over g1_values_monomial (4096 points): low-latency cell proofs
+    FixedBaseTable cell_interp;   // over g1_values_monomial[0..63], this slot's own: built by the first
+                                  // ckzg_hip_verify_cell_kzg_proof_batch_locate on the slot, kept until the slot goes
     int direct_max = 10;          // batches up to this many blobs use the direct proof path (set at load)
     uint64_t tables_version = 0;  // which publication of the pool's tables the copies above are (api_common.hpp: PublishedTables)
     G1Affine *d_lagr = nullptr;   // g1_values_lagrange_brp, affine, 4096 (bases of the commitment table; kept for widening)
@@ -445,6 +447,7 @@ int msm_small_vectors_device(DeviceCtx *ctx, const FixedBaseTable &t, G1XYZZ *d_
 // ntt.hip
 int fr_ntt_batch(DeviceCtx *ctx, Fr *d_data, size_t count, int logn, bool dif, bool inverse,
                  bool scale_by_inv_n);
+Fr fr_inv_pow2(int logn);   // (2^logn)^-1, Montgomery form (host)
 int bytes_to_fr_batch(DeviceCtx *ctx, Fr *d_out, uint32_t *d_bad, const uint8_t *d_in, size_t total,
                       uint32_t elems_per_unit);
 int fr_to_bytes_batch(DeviceCtx *ctx, uint8_t *d_out, const Fr *d_in, size_t total);
@@ -586,6 +589,18 @@ int pairing_check_enqueue(DeviceCtx *ctx, uint8_t *d_res, const G1Affine *d_lhs,
 // ctx->stream.  d_ab[i] = [r^i] d_p1[i], d_ab[n + i] = [r^i] proof_i from d_neg_proof[i] = -proof_i (affine; XYZZ out).
 int locate_scale_enqueue(DeviceCtx *ctx, G1XYZZ *d_ab, const G1Affine *d_p1, const G1Affine *d_neg_proof, const Fr &r,
                          size_t n);
+// The cell form (ckzg_api2.hip: locate_cells_on).  d_digits[n][2 twin][64] <- the signed digits (table geometry wbits,
+// twin) of minus the interpolation coefficients of cell i over the coset of column d_col[i], from d_cell_fr[n][64]
+// (Montgomery).  fused: one kernel, one wave per cell.  Otherwise fr_ntt_batch in place -- d_cell_fr then has room up to
+// the next multiple of 64 cells and is overwritten -- a scale pass into d_raw_tmp[n][64][8] and a recoding pass.
+int cell_interp_digits_enqueue(DeviceCtx *ctx, int16_t *d_digits, Fr *d_cell_fr, const uint32_t *d_col, size_t n, int wbits,
+                               int twin, bool fused, uint32_t *d_raw_tmp);
+// d_pts: proofs [0, n), the chunk's distinct commitments [n, n + nc), decompressed, with their n + nc flags; d_commit[n]:
+// which commitment an item names; d_cell_bad[n]: bytes_to_fr_batch's flags; d_minus_interp[n] = -[I_i(s)]_1.  Writes
+// P1_i = C_i - [I_i(s)]_1 + [h_i^64] proof_i (XYZZ; infinity for an invalid item), -proof_i (affine) and d_bad[n].
+int cell_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8_t *d_bad, const G1Affine *d_pts,
+                     const uint8_t *d_st_dec, const uint8_t *d_st_sub, const G1XYZZ *d_minus_interp, const uint32_t *d_col,
+                     const uint32_t *d_commit, const uint32_t *d_cell_bad, size_t n);
 // d_data[s][i] <- d_data[s][0] + ... + d_data[s][i] for nseg arrays of n points each, in place, with the complete
 // addition; d_scratch: g1_prefix_scan_scratch_points(n, nseg) points
 size_t g1_prefix_scan_scratch_points(size_t n, size_t nseg);

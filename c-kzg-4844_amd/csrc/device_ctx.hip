@@ -191,6 +191,7 @@ static void destroy_slot(dev::DeviceCtx *ctx) {
         if (ctx->d_shift) (void)hipFree(ctx->d_shift);
         if (ctx->d_unshift) (void)hipFree(ctx->d_unshift);
     }
+    if (ctx->cell_interp.d_table) (void)hipFree(ctx->cell_interp.d_table);   // (every slot's own, built on first use)
     if (ctx->scratch.ptr) (void)hipFree(ctx->scratch.ptr);
     ctx->api_arena.release();
     ctx->lc_arena.release();

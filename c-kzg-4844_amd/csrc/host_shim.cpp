@@ -913,3 +913,128 @@ extern "C" void hs_locate_points_host(uint8_t *ok, uint8_t *status, uint64_t *st
     stats[0] = res.checks;
     stats[1] = res.open.size();
 }
+
+// ---- ckzg_hip_verify_cell_kzg_proof_batch_locate: the chunk's two-level digest, and the whole second half in host
+// arithmetic (tests/test_cell_locate_cpu.py). ----
+#include <map>
+#include <string>
+extern "C" void hs_locate_cell_digest(uint8_t *digest32, const uint8_t *c48, const uint64_t *cell_indices, const uint8_t *cells,
+                                      const uint8_t *p48, uint64_t n) {
+    locate_cell_digest<Sha256>(digest32, c48, cell_indices, cells, p48, n);
+}
+
+// Per item: validation (index < 128, 64 canonical field elements, both points in G1), the interpolation polynomial of
+// the cell over its coset by the definition of the inverse transform (64 x 64 products, no butterflies: a route of its
+// own), P1_i = C_i - sum_k I_i[k] mono64[k] + [h_i^64] proof_i, then as hs_locate_points_host: r from
+// locate_cell_digest, A_i = [r^i] P1_i, B_i = [r^i] proof_i, prefix sums and the bisection over
+// e(PA[b] - PA[a], [1]_2) * e(-(PB[b] - PB[a]), [s^64]_2) == 1.  mono48: g1_values_monomial[0..63] as the setup file has
+// them (64 x 48 bytes), s64_g2: [s^64]_2.  Out: ok[n], status[n] (1 = invalid item), stats[0] = checks, stats[1] = ranges
+// left open, r32 = the digest r was reduced from.  Returns 0, or 1 if a setup point does not decompress.
+extern "C" int hs_locate_cells_host(uint8_t *ok, uint8_t *status, uint64_t *stats, uint8_t *r32, const uint8_t *c48,
+                                    const uint64_t *cell_indices, const uint8_t *cells, const uint8_t *p48, uint64_t n,
+                                    const uint8_t *mono48, const G2Jac *s64_g2, int64_t max_checks) {
+    G2Prepared q1, q2;
+    g2_prepare(q1, g2_to_affine(g2_generator()));
+    g2_prepare(q2, g2_to_affine(*s64_g2));
+    G1Jac mono[64];
+    for (int k = 0; k < 64; k++) {
+        G1Affine a;
+        if (g1_uncompress(a, mono48 + 48 * k) != 0) return 1;
+        mono[k] = jac_from_affine(a);
+    }
+    // w = 7^((r - 1) / 8192), the 8192-th root of unity the setup uses; roots[i] = w^i
+    std::vector<Fr> roots(8192);
+    {
+        uint32_t e[8], seven[8] = {7, 0, 0, 0, 0, 0, 0, 0};
+        mod_limbs<FrParams>(e);
+        e[0] -= 1;   // (r is odd)
+        for (int i = 0; i < 8; i++) e[i] = (e[i] >> 13) | (i < 7 ? e[i + 1] << 19 : 0u);
+        Fr w = Fr::one(), base = from_raw<FrParams>(seven);
+        for (int i = 0; i < 256; i++, base = mul(base, base))
+            if ((e[i >> 5] >> (i & 31)) & 1u) w = mul(w, base);
+        roots[0] = Fr::one();
+        for (int i = 1; i < 8192; i++) roots[i] = mul(roots[i - 1], w);
+    }
+    uint32_t sixty_four[8] = {64, 0, 0, 0, 0, 0, 0, 0};
+    const Fr inv64 = fr_inv_safegcd(from_raw<FrParams>(sixty_four));
+    auto brp = [](uint32_t v, int bits) {
+        uint32_t o = 0;
+        for (int b = 0; b < bits; b++) o |= ((v >> b) & 1u) << (bits - 1 - b);
+        return o;
+    };
+    locate_cell_digest<Sha256>(r32, c48, cell_indices, cells, p48, n);
+    uint32_t rraw[8];
+    for (int i = 0; i < 8; i++) {
+        const uint8_t *p = r32 + 4 * (7 - i);
+        rraw[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+    }
+    const Fr r = from_raw<FrParams>(rraw);   // (reduces)
+    std::vector<uint8_t> invalid(n ? n : 1), okb(n ? n : 1);
+    std::vector<G1Jac> pa(n + 1), pb(n + 1);   // PA[0] = PB[0] = infinity
+    pa[0] = pb[0] = G1Jac::inf();
+    std::map<std::string, G1Jac> interp_of;   // [I(s)]_1 per distinct (column, cell): the vectors repeat their cells
+    Fr rp = Fr::one();
+    for (uint64_t i = 0; i < n; i++, rp = mul(rp, r)) {
+        G1Affine c, pr;
+        bool bad = g1_uncompress(c, c48 + 48 * i) != 0 || g1_uncompress(pr, p48 + 48 * i) != 0;
+        bad = bad || !g1_in_subgroup_host(c) || !g1_in_subgroup_host(pr);
+        bad = bad || cell_indices[i] >= 128;
+        Fr ev[64];
+        for (int j = 0; j < 64 && !bad; j++) {
+            uint32_t raw[8], m[8];
+            for (int w = 0; w < 8; w++) {
+                const uint8_t *p = cells + 2048 * i + 32 * j + 4 * (7 - w);
+                raw[w] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+            }
+            mod_limbs<FrParams>(m);
+            bad = limbs_geq<8>(raw, m);
+            ev[j] = from_raw<FrParams>(raw);
+        }
+        invalid[i] = bad ? 1 : 0;
+        G1Jac a = G1Jac::inf(), b = G1Jac::inf();
+        if (!bad) {
+            const uint32_t rb = brp((uint32_t)cell_indices[i], 7);
+            std::string key(reinterpret_cast<const char *>(cells + 2048 * i), 2048);
+            key.push_back((char)cell_indices[i]);
+            auto it = interp_of.find(key);
+            if (it == interp_of.end()) {
+                G1Jac sum = G1Jac::inf();
+                for (uint32_t k = 0; k < 64; k++) {
+                    // coefficient k of the polynomial through ev[brp6(j)] at h w64^j: (1/64) sum_j ev[brp6(j)] w64^(-jk), times h^-k
+                    Fr ck = Fr::zero();
+                    for (uint32_t j = 0; j < 64; j++) ck = add(ck, mul(ev[brp(j, 6)], roots[(8192u - 128u * ((j * k) & 63u)) & 8191u]));
+                    ck = mul(mul(ck, inv64), roots[((8192u - rb) * k) & 8191u]);
+                    uint32_t kraw[8];
+                    to_raw<FrParams>(kraw, ck);
+                    sum = jac_add(sum, g1_mul_glv_host(mono[k], kraw));
+                }
+                it = interp_of.emplace(key, sum).first;
+            }
+            uint32_t h64[8], k[8];
+            to_raw<FrParams>(h64, roots[64u * rb]);
+            const G1Jac proof = jac_from_affine(pr);
+            const G1Jac p1 = jac_add(jac_add(jac_from_affine(c), jac_neg(it->second)), g1_mul_glv_host(proof, h64));
+            to_raw<FrParams>(k, rp);
+            a = g1_mul_glv_host(p1, k);
+            b = g1_mul_glv_host(proof, k);
+        }
+        pa[i + 1] = jac_add(pa[i], a);
+        pb[i + 1] = jac_add(pb[i], b);
+    }
+    auto range_ok = [&](size_t lo, size_t hi) {
+        const G1Jac da = jac_add(pa[hi], jac_neg(pa[lo])), db = jac_add(pb[hi], jac_neg(pb[lo]));
+        return pairing_product_is_one(jac_to_affine(da), q1, jac_to_affine(jac_neg(db)), q2);
+    };
+    auto serial = [](size_t m, auto &&fn) {
+        for (size_t i = 0; i < m; i++) fn(i);
+    };
+    const LocateOutcome res = locate_bisect(reinterpret_cast<bool *>(okb.data()), invalid.data(), (size_t)n,
+                                            max_checks < 0 ? UINT64_MAX : (uint64_t)max_checks, range_ok, serial);
+    for (uint64_t i = 0; i < n; i++) {
+        ok[i] = okb[i];
+        status[i] = invalid[i];
+    }
+    stats[0] = res.checks;
+    stats[1] = res.open.size();
+    return 0;
+}

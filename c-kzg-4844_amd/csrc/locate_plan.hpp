@@ -1,7 +1,8 @@
 // locate_plan.hpp -- which items of a chunk are false, found by bisection over a predicate range_ok(a, b) on contiguous
-// ranges (ckzg_hip_verify_kzg_proof_batch_locate / ckzg_hip_verify_blob_kzg_proof_batch_locate).
-// Pure host code, shared by the product (ckzg_api2.hip: the predicate is one two-pairing check over differences of
-// prefix sums) and the host test shim (host_shim.cpp: hs_locate_bisect, hs_locate_points_host).
+// ranges (ckzg_hip_verify_kzg_proof_batch_locate / ckzg_hip_verify_blob_kzg_proof_batch_locate /
+// ckzg_hip_verify_cell_kzg_proof_batch_locate; DESIGN.md sections 3f, 3g), and the chunk challenges of the point and cell
+// forms.  Pure host code, shared by the product (ckzg_api2.hip: the predicate is one two-pairing check over differences
+// of prefix sums) and the host test shim (host_shim.cpp: hs_locate_bisect, hs_locate_points_host, hs_locate_cells_host).
 //
 // The rules are fixed, so that the number of checks is a property and not an observation:
 //   * invalid items are inert (they contribute infinity to every range) and are settled from their flag: ok = false;
@@ -101,6 +102,46 @@ void locate_point_digest(uint8_t digest[32], const uint8_t *c48, const uint8_t *
         h.update(p48 + 48 * i, 48);
     }
     h.finish(digest);
+}
+
+// The challenge of a chunk of the cell form (ckzg_hip_verify_cell_kzg_proof_batch_locate): two levels, so that the
+// 2,152 bytes of every item are hashed on their own -- on as many threads as there are -- and only 32 bytes per item
+// go through the one stream that binds them together.  Over the chunk's items as given, invalid ones included:
+//   leaf_i = SHA-256("CKZGHIPCELLLEAF_" | C_i (48) | u64be cell_index_i | cell_i (2048) | proof_i (48))
+//   root   = SHA-256("CKZGHIPCELLROOT_" | u64be 4096 | u64be k | leaf_0 | ... | leaf_{k-1})
+// (Not the reference's transcript, eip7594.c:390-482, which is one stream over every cell: a per-item verdict does not
+// depend on r.)
+template <class Sha>
+void locate_cell_leaf(uint8_t leaf[32], const uint8_t *c48, uint64_t cell_index, const uint8_t *cell2048, const uint8_t *p48) {
+    Sha h;
+    uint8_t head[24] = {'C', 'K', 'Z', 'G', 'H', 'I', 'P', 'C', 'E', 'L', 'L', 'L', 'E', 'A', 'F', '_'};
+    h.update(head, 16);
+    h.update(c48, 48);
+    for (int i = 0; i < 8; i++) head[i] = (uint8_t)(cell_index >> (8 * (7 - i)));
+    h.update(head, 8);
+    h.update(cell2048, 2048);
+    h.update(p48, 48);
+    h.finish(leaf);
+}
+template <class Sha>
+void locate_cell_root(uint8_t digest[32], const uint8_t *leaves, uint64_t k) {
+    Sha h;
+    uint8_t head[32] = {'C', 'K', 'Z', 'G', 'H', 'I', 'P', 'C', 'E', 'L', 'L', 'R', 'O', 'O', 'T', '_'};
+    for (int i = 0; i < 8; i++) {
+        head[16 + i] = (uint8_t)((uint64_t)4096 >> (8 * (7 - i)));
+        head[24 + i] = (uint8_t)(k >> (8 * (7 - i)));
+    }
+    h.update(head, 32);
+    h.update(leaves, 32 * k);
+    h.finish(digest);
+}
+// both levels on one thread (the host test shim; the product hashes the leaves on its pool)
+template <class Sha>
+void locate_cell_digest(uint8_t digest[32], const uint8_t *c48, const uint64_t *cell_indices, const uint8_t *cells, const uint8_t *p48,
+                        uint64_t k) {
+    std::vector<uint8_t> leaves(32 * (k ? k : 1));
+    for (uint64_t i = 0; i < k; i++) locate_cell_leaf<Sha>(&leaves[32 * i], c48 + 48 * i, cell_indices[i], cells + 2048 * i, p48 + 48 * i);
+    locate_cell_root<Sha>(digest, leaves.data(), k);
 }
 
 }  // namespace ckzg

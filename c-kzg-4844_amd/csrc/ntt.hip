@@ -133,7 +133,7 @@ __global__ void k_ntt8192_outer(Fr *data, const Fr *roots, size_t total_butterfl
     store_fr(a + i + 4096, y);
 }
 
-static Fr inv_pow2(int logn) {
+Fr fr_inv_pow2(int logn) {
     // (2^logn)^-1 in Montgomery form: halve `one` logn times  (x/2 = (x + (x odd ? r : 0)) >> 1)
     Fr v = Fr::one();
     uint32_t m[8];
@@ -162,7 +162,7 @@ int fr_ntt_batch(DeviceCtx *ctx, Fr *d_data, size_t count, int logn, bool dif, b
     Fr scale = Fr::one();
     int do_scale = 0;
     if (scale_by_inv_n) {
-        scale = inv_pow2(logn);
+        scale = fr_inv_pow2(logn);
         do_scale = 1;
     }
     if (logn <= 12) {

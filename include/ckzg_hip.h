@@ -263,6 +263,45 @@ C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status,
                                                       const Bytes48 *proofs_bytes, const uint64_t *group_start,
                                                       uint64_t num_groups, const KZGSettings *s);
 
+/* Per-cell verdicts at batch cost: the third *_locate call.  For every i, (status[i], ok[i]) is exactly (return value,
+ * *ok) of verify_cell_kzg_proof_batch(&ok, &commitments[i], &cell_indices[i], &cells[i], &proofs[i], 1, s) -- the unit
+ * PeerDAS moves around, for a node that holds a few thousand cells and must know which of them are false -- and a
+ * call in which every cell verifies costs ONE two-pairing check.  Per item the check of eip7594.c:825-974 has the
+ * left-hand point P1_i = C_i - [I_i(s)]_1 + [h_i^64] proof_i, I_i the interpolation polynomial of cell i over its
+ * coset and h_i the coset factor of column cell_indices[i]; with A_i = [r^i] P1_i and B_i = [r^i] proof_i a range
+ * [a, b) is true iff e(sum A, [1]_2) * e(-sum B, [s^64]_2) == 1, and from the prefix sums on it is the point form above:
+ * bisection on the host pool, ok[i] = false always exact, the hand-over under the option "locate_max_checks", stats.
+ * The cells are NOT aggregated by column first (prefix sums cannot be taken over an aggregate): every cell has its own
+ * 64-point inverse transform (one wave) and its own 64-term fixed-base sum over g1_values_monomial[0..63], whose
+ * table (41 MB per device slot, 10-bit windows) is built by the first call on a slot and kept until
+ * free_trusted_setup; load time and every other entry point are as they were.
+ * An item is invalid when its index is >= 128, when its cell holds a non-canonical field element, or when its
+ * commitment or proof is not a valid G1 point: status[i] = 1, ok[i] = false, inert in every range, settled from its
+ * flag alone; the other items are still decided.  Returns C_KZG_BADARGS if any item is invalid, C_KZG_OK otherwise
+ * (also for num_cells == 0, which writes nothing); C_KZG_MALLOC / C_KZG_ERROR if the call itself failed (a table that
+ * could not be allocated leaves nothing behind, and the next call builds it).  status and stats may be NULL; NULL ok or
+ * inputs with num_cells > 0 give C_KZG_BADARGS.  Host pointers; several devices take contiguous runs of items; on a
+ * device the items go in chunks of at most CKZG_HIP_CELL_LOCATE_CHUNK_CELLS, each with its own challenge and bisection.
+ * The challenge is NOT the reference's transcript (one SHA-256 stream over every cell, 8.4 of the 9.9 ms of an
+ * 8,192-cell batch on one core): a per-item verdict does not depend on r, so the chunk's items, as given, are hashed in
+ * two levels -- leaf_i = SHA-256("CKZGHIPCELLLEAF_" | C_i | u64be cell_index_i | cell_i | proof_i) on the host pool
+ * underneath the copies and kernels, root = SHA-256("CKZGHIPCELLROOT_" | u64be 4096 | u64be k | leaf_0 | ... |
+ * leaf_{k-1}), r = root reduced mod r.
+ * Measured (profiles/cell_locate_bench.json; medians of 20, a 256-thread host; the existing calls on a build of the
+ * parent commit in the same process): everything good, 11.8 / 12.3 / 16.1 / 20.8 ms for 128 / 1,024 / 8,192 / 16,384
+ * cells, against 9.1 (minimum 8.2) / 57.9 (40.6) / 470 (407) / 884 (830) ms for
+ * ckzg_hip_verify_cell_kzg_proof_batch_groups with groups of one; one verify_cell_kzg_proof_batch over the same cells,
+ * ONE verdict for all of them, takes 2.6 / 2.9 / 9.8 / 18.7 ms.  One false cell 19.1 / 24.1 / 30.9 / 35.6 ms (11 / 17 /
+ * 21 / 21 host range checks), eight 23.6 / 29.0 / 40.1 / 45.6 ms.  NOT faster: at 128 cells in every case (the two ladder
+ * kernels of a *_locate call cost ~12 ms whatever the size: groups of one win, 9.1 ms); and with every cell false at
+ * 1,024 cells, 111.5 ms against 57.9 (the bisection up to the hand-over, then the per-lane pass; 114.9 / 122.5 ms at
+ * 8,192 / 16,384, where groups of one take 470 / 884). */
+#define CKZG_HIP_CELL_LOCATE_CHUNK_CELLS 16384
+C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats,
+                                                      const Bytes48 *commitments_bytes, const uint64_t *cell_indices,
+                                                      const Cell *cells, const Bytes48 *proofs_bytes, uint64_t num_cells,
+                                                      const KZGSettings *s);
+
 /* verify_blob_kzg_proof_batch (src/eip4844/eip4844.c:775-844) over num_groups independent batches in one call, one
  * verdict per group -- a transaction pool validating blob transactions of 1-9 blobs each, a syncing node validating
  * the blob sidecars of a range of blocks: callers that must know WHICH batch is bad.  Host pointers.  The three input

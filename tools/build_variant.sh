@@ -10,7 +10,7 @@ set -e
 name=$1; shift
 cd "$(dirname "$0")/../c-kzg-4844_amd"
 mkdir -p build_$name
-for f in csrc/ckzg_api.hip csrc/device_ctx.hip csrc/msm.hip csrc/ntt.hip csrc/fk20.hip csrc/verify.hip csrc/pippenger.hip csrc/ckzg_api2.hip; do
+for f in csrc/ckzg_api.hip csrc/device_ctx.hip csrc/msm.hip csrc/ntt.hip csrc/fk20.hip csrc/verify.hip csrc/pippenger.hip csrc/ckzg_api2.hip csrc/pairing.hip csrc/locate.hip; do
   o=build_$name/$(basename $f .hip).o
   # ONLY=<file stem> restricts the extra flags to that translation unit (e.g. ONLY=msm)
   # (a space-separated list is accepted: ONLY="msm fk20")
