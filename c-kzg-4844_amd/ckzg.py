@@ -219,6 +219,37 @@ class Kzg:
         raw = out.raw
         return [raw[144 * i:144 * i + 144] for i in range(n)]
 
+    def g1_fft(self, points, n, inverse=False):
+        """ckzg_hip_g1_fft: len(points) / n transforms of length n (a power of two up to 8192) over g1_t values (144
+        bytes, Jacobian), natural order in and out; inverse: the twiddles w^-1 and no factor 1/n."""
+        for p in points:
+            _check(len(p) == 144, "g1_t")
+        _check(n >= 0 and (n == 0 or len(points) % n == 0), "points is not a whole number of transforms")
+        count = len(points) // n if n else 0
+        out = C.create_string_buffer(144 * max(len(points), 1))
+        self._call("ckzg_hip_g1_fft", out, b"".join(points), C.c_uint64(n), C.c_uint64(count), C.c_int(1 if inverse else 0),
+                   self.sp)
+        raw = out.raw
+        return [raw[144 * i:144 * i + 144] for i in range(n * count)]
+
+    def compute_domain_kzg_proofs_batch(self, blobs):
+        """ckzg_hip_compute_domain_kzg_proofs_batch: for every blob its 4096 openings at the points of the evaluation
+        domain; proofs[i][j] is the proof of compute_kzg_proof(blobs[i], brp_roots_of_unity[j]), which opens field
+        element j.  Returns (proofs, status): status[i] = 1 (C_KZG_BADARGS) for a blob with a non-canonical element,
+        whose proofs are then unspecified."""
+        n = len(blobs)
+        for b in blobs:
+            _check(len(b) == BYTES_PER_BLOB, "blob")
+        per = 4096 * 48
+        proofs = C.create_string_buffer(per * max(n, 1))
+        st = (C.c_uint8 * max(n, 1))()
+        ret = self._fn("ckzg_hip_compute_domain_kzg_proofs_batch")(proofs, st, b"".join(blobs), C.c_uint64(n), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_compute_domain_kzg_proofs_batch -> C_KZG_RET %d" % ret)
+        raw = proofs.raw
+        return ([[raw[per * i + 48 * j:per * i + 48 * j + 48] for j in range(4096)] for i in range(n)],
+                [int(v) for v in st[:n]])
+
     def verify_blob_kzg_proof(self, blob, commitment, proof):
         _check(len(blob) == BYTES_PER_BLOB, "blob")
         _check(len(commitment) == 48 and len(proof) == 48, "commitment/proof")

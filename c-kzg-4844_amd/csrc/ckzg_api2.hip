@@ -14,6 +14,7 @@
 #include "blob_groups_plan.hpp"
 #include "cell_groups_plan.hpp"
 #include "combiner.hpp"
+#include "g1_fft_plan.hpp"
 #include "locate_plan.hpp"
 #include "recover_rows_plan.hpp"
 #include "slice_starts.hpp"
@@ -3193,5 +3194,164 @@ extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_locate(bool *ok, uint8
             return locate_cells_on(ctx, ok + lo, status ? status + lo : nullptr, st, commitments_bytes + lo, cell_indices + lo,
                                    cells + lo, proofs_bytes + lo, hi - lo);
         });
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// The G1 transform at the boundary, and the openings of a blob at every point of the evaluation domain
+// (ckzg_hip_g1_fft, ckzg_hip_compute_domain_kzg_proofs_batch[_device]; g1_fft.hip, g1_fft_plan.hpp)
+// ------------------------------------------------------------------------------------------
+
+extern "C" C_KZG_RET ckzg_hip_g1_fft(g1_t *out, const g1_t *in, uint64_t n, uint64_t count, int inverse, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        // the arguments first: none of these checks needs the device
+        const int logn = n ? g1_fft_log2(n) : 0;
+        if (logn < 0) return C_KZG_BADARGS;
+        if (n && count && (!out || !in || count > (((uint64_t)1 << 31) >> logn))) return C_KZG_BADARGS;
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0 || count == 0) return C_KZG_OK;
+        const size_t len = (size_t)(n * count);
+        // on the curve (y^2 = x^3 + 4 on the affine form), then the subgroup test on the device: the ladders use the
+        // endomorphism, which is [lambda] only on the prime-order subgroup
+        std::vector<G1Affine> aff(len);
+        std::atomic<bool> off_curve{false};
+        parallel_for((len + 255) / 256, [&](size_t c) {
+            const Fp four = dbl(dbl(Fp::one()));
+            for (size_t i = c * 256; i < len && i < (c + 1) * 256; i++) {
+                aff[i] = jac_to_affine_fast(*as_g1(&in[i]));
+                if (!aff[i].is_inf() && sqr(aff[i].y) != add(mul(sqr(aff[i].x), aff[i].x), four)) off_curve.store(true, std::memory_order_relaxed);
+            }
+        });
+        if (off_curve.load()) return C_KZG_BADARGS;
+        Lease lease(s);
+        dev::DeviceCtx *ctx = lease.ctx;
+        if (!ctx) return C_KZG_ERROR;
+        const size_t ntmp = dev::g1_fft_tmp_points(logn, count);
+        Arena &ar = ctx->api_arena;
+        OKM(ar.begin(len * (sizeof(G1Affine) + 1 + sizeof(G1XYZZ)) + ntmp * sizeof(G1XYZZ) + 4 * 256));
+        ArenaTrim trim(ar);
+        ABuf<G1Affine> d_aff(ar, len);
+        ABuf<uint8_t> d_st(ar, len);
+        ABuf<G1XYZZ> d_pts(ar, len), d_tmp(ar, ntmp);
+        OKM(d_aff.p && d_st.p && d_pts.p && d_tmp.p);
+        StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the arena's reuse or the frame
+        OKB(hipMemcpyAsync(d_aff.p, aff.data(), len * sizeof(G1Affine), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        RC(dev::subgroup_g1_batch_device(ctx, d_st.p, d_aff.p, len));
+        std::vector<uint8_t> st(len);
+        OKB(d_st.down(st.data(), len));
+        for (uint8_t b : st) {
+            if (b) return C_KZG_BADARGS;
+        }
+        std::vector<G1XYZZ> pts(len);
+        for (size_t i = 0; i < len; i++) pts[i] = xyzz_from_affine(aff[i]);
+        OKB(hipMemcpyAsync(d_pts.p, pts.data(), len * sizeof(G1XYZZ), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        // natural order in, bit-reversed out: the permutation is done on the way home
+        RC(dev::g1_fft_enqueue(ctx, d_pts.p, d_tmp.p, logn, count, n, /*dif=*/true, inverse ? 1 : 0));
+        OKB(d_pts.down(pts.data(), len));
+        parallel_for((len + 255) / 256, [&](size_t c) {
+            for (size_t i = c * 256; i < len && i < (c + 1) * 256; i++) {
+                const size_t f = i >> logn, p = i & (n - 1);
+                *as_g1(&out[(f << logn) + reverse_bits_limited(n, p)]) = jac_from_xyzz(pts[i]);
+            }
+        });
+        return C_KZG_OK;
+    });
+}
+
+namespace {
+
+// what a chunk of up to m blobs needs next to the blobs and the proofs themselves
+struct DomainBufs {
+    ABuf<uint32_t> bad;
+    ABuf<uint8_t> scratch;
+    static size_t bytes(uint64_t m) { return m * sizeof(uint32_t) + dev::domain_proofs_scratch_bytes(m) + 2 * 256; }
+    DomainBufs(Arena &ar, uint64_t m) : bad(ar, m), scratch(ar, dev::domain_proofs_scratch_bytes(m)) {}
+    bool ok() const { return bad.p && scratch.p; }
+};
+
+// one chunk of k <= CKZG_HIP_DOMAIN_CHUNK_BLOBS blobs in HBM: enqueue-only, on the slot's compute stream; d_status may be null
+C_KZG_RET domain_proofs_chunk(dev::DeviceCtx *ctx, const DomainBufs &b, uint8_t *d_proofs48, uint8_t *d_status, const uint8_t *d_blobs,
+                              uint64_t k) {
+    OKB(hipMemsetAsync(b.bad.p, 0, k * sizeof(uint32_t), ctx->stream) == hipSuccess);
+    RC(dev::domain_proofs_enqueue(ctx, d_proofs48, b.bad.p, d_blobs, k, b.scratch.p));
+    if (d_status) RC(dev::flags_to_status_enqueue(ctx, d_status, b.bad.p, k));
+    return C_KZG_OK;
+}
+
+// One device's share of a host-pointer call: per chunk, blobs to HBM, the chunk, proofs | statuses back in one copy
+C_KZG_RET domain_proofs_on(dev::DeviceCtx *ctx, KZGProof *proofs, uint8_t *status, const Blob *blobs, uint64_t n) {
+    if (n == 0) return C_KZG_OK;
+    const uint64_t CH = CKZG_HIP_DOMAIN_CHUNK_BLOBS, per = (uint64_t)FIELD_ELEMENTS_PER_BLOB * 48;
+    const uint64_t m = domain_chunk_size(n, CH, 0);
+    RC(dev::domain_xhat_ensure(ctx));
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(m * (BYTES_PER_BLOB + per + 1) + DomainBufs::bytes(m) + 2 * 256));
+    ArenaTrim trim(ar);
+    ABuf<uint8_t> d_blobs(ar, m * BYTES_PER_BLOB), d_res(ar, m * (per + 1));
+    DomainBufs b(ar, m);
+    OKM(d_blobs.p && d_res.p && b.ok());
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the caller's buffers or the arena's reuse
+    std::vector<uint8_t> st(m);
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
+        const uint64_t k = domain_chunk_size(n, CH, c);
+        OKB(hipMemcpyAsync(d_blobs.p, blobs + off, k * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        RC(domain_proofs_chunk(ctx, b, d_res.p, d_res.p + k * per, d_blobs.p, k));
+        OKB(hipMemcpyAsync(proofs + off * FIELD_ELEMENTS_PER_BLOB, d_res.p, k * per, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+        OKB(hipMemcpyAsync(st.data(), d_res.p + k * per, k, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+        for (uint64_t i = 0; i < k; i++) {
+            if (status) status[off + i] = st[i];
+            if (st[i]) ret = C_KZG_BADARGS;
+        }
+        off += k;
+    }
+    return ret;
+}
+
+}  // namespace
+
+extern "C" C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch(KZGProof *proofs, uint8_t *status, const Blob *blobs, uint64_t n,
+                                                             const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (n && (!proofs || !blobs)) return C_KZG_BADARGS;
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        return for_each_device_shard(s, n, 1, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return domain_proofs_on(ctx, proofs + lo * FIELD_ELEMENTS_PER_BLOB, status ? status + lo : nullptr, blobs + lo, hi - lo);
+        });
+    });
+}
+
+extern "C" C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch_device(void *d_proofs, void *d_status, const void *d_blobs,
+                                                                    uint64_t n, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (n && (!d_proofs || !d_blobs)) return C_KZG_BADARGS;
+        SettingsCtx *sc = settings_of(s);
+        if (!sc) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        const void *ptrs[3] = {d_proofs, d_status, d_blobs};
+        const int pool = pool_of_pointers(sc, ptrs, 3);
+        if (pool < 0) return C_KZG_BADARGS;
+        Lease lease(s, pool);
+        dev::DeviceCtx *ctx = lease.ctx;
+        if (!ctx) return C_KZG_ERROR;
+        const uint64_t CH = CKZG_HIP_DOMAIN_CHUNK_BLOBS, per = (uint64_t)FIELD_ELEMENTS_PER_BLOB * 48;
+        const uint64_t m = domain_chunk_size(n, CH, 0);
+        RC(dev::domain_xhat_ensure(ctx));
+        Arena &ar = ctx->api_arena;
+        OKM(ar.begin(DomainBufs::bytes(m)));
+        ArenaTrim trim(ar);
+        DomainBufs b(ar, m);
+        OKM(b.ok());
+        StreamDrain drain{ctx->stream};
+        uint8_t *out = static_cast<uint8_t *>(d_proofs), *st = static_cast<uint8_t *>(d_status);
+        const uint8_t *bl = static_cast<const uint8_t *>(d_blobs);
+        for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
+            const uint64_t k = domain_chunk_size(n, CH, c);
+            RC(domain_proofs_chunk(ctx, b, out + off * per, st ? st + off : nullptr, bl + off * BYTES_PER_BLOB, k));
+            off += k;
+        }
+        return C_KZG_OK;
     });
 }

@@ -369,6 +369,10 @@ struct DeviceCtx {
     Fr *d_brp_roots = nullptr;    // 8192
     uint32_t *d_brp_roots29 = nullptr;   // the first 4096 of them as fr29.hpp's nine 29-bit limbs, then 1/brp_roots[2m], m < 2048
     uint32_t *d_roots_raw = nullptr;  // GLV halves {k1, k2} of w^(64 i), i <= 128 (twiddles of the G1 FFT)
+    // the general G1 transform and the openings at every domain point (g1_fft.hip), this slot's own: built by the
+    // first call on the slot that needs them, kept until the slot goes
+    uint32_t *d_g1_fft_roots = nullptr;   // GLV halves {k1[4], k2[4]} of w^i, i < 8192 (256 KB)
+    G1Affine *d_domain_xhat = nullptr;    // the G1 transform of the reversed monomial setup, DIF order, affine, 8192 (768 KB)
     // FK20
     FixedBaseTable fk20;          // over x_ext_fft columns: point index = col*64 + row
     G1Affine *d_xext = nullptr;   // [128][64] affine
@@ -605,6 +609,21 @@ int cell_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8
 // addition; d_scratch: g1_prefix_scan_scratch_points(n, nseg) points
 size_t g1_prefix_scan_scratch_points(size_t n, size_t nseg);
 int g1_prefix_scan_enqueue(DeviceCtx *ctx, G1XYZZ *d_data, G1XYZZ *d_scratch, size_t n, size_t nseg);
+// g1_fft.hip: `count` G1 transforms of length 2^logn (logn <= 13), in place, transform f at d_data + f * stride.
+// dif: natural order in, bit-reversed out (stages logn .. 1); otherwise bit-reversed in, natural out.  inverse: the
+// twiddles w^-1, no factor 1/n.  Every point must be the identity or in the prime-order subgroup (GLV ladders).
+// d_tmp: g1_fft_tmp_points(logn, count) points.  Enqueue-only, on ctx->stream; builds the slot's twiddle records on
+// first use (3 = out of memory).  Which ladder form a stage takes: g1_fft_plan.hpp with g1_fft_quad_max().
+uint64_t g1_fft_quad_max();
+size_t g1_fft_tmp_points(int logn, size_t count);
+int g1_fft_enqueue(DeviceCtx *ctx, G1XYZZ *d_data, G1XYZZ *d_tmp, int logn, size_t count, size_t stride, bool dif, int inverse);
+// The openings of k blobs at every point of the evaluation domain: d_proofs48[k][4096][48], proof j of a blob opens its
+// field element j.  domain_xhat_ensure builds the slot's transformed setup on first use (waits for it; a failure keeps
+// nothing); domain_proofs_enqueue is enqueue-only on ctx->stream, d_bad[k] zeroed by the caller on that stream.
+size_t domain_xhat_bytes();
+int domain_xhat_ensure(DeviceCtx *ctx);
+size_t domain_proofs_scratch_bytes(size_t k);
+int domain_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint32_t *d_bad, const uint8_t *d_blobs, size_t k, uint8_t *scratch);
 // generic helpers
 int batch_to_affine_device(DeviceCtx *ctx, G1Affine *d_out, const G1XYZZ *d_in, Fp *d_prefix, size_t n);
 

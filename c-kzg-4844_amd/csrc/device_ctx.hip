@@ -192,6 +192,8 @@ static void destroy_slot(dev::DeviceCtx *ctx) {
         if (ctx->d_unshift) (void)hipFree(ctx->d_unshift);
     }
     if (ctx->cell_interp.d_table) (void)hipFree(ctx->cell_interp.d_table);   // (every slot's own, built on first use)
+    if (ctx->d_g1_fft_roots) (void)hipFree(ctx->d_g1_fft_roots);             // (likewise: g1_fft.hip)
+    if (ctx->d_domain_xhat) (void)hipFree(ctx->d_domain_xhat);
     if (ctx->scratch.ptr) (void)hipFree(ctx->scratch.ptr);
     ctx->api_arena.release();
     ctx->lc_arena.release();

@@ -1,0 +1,64 @@
+// g1_fft_plan.hpp -- the host decisions of the general G1 transform (g1_fft.hip; ckzg_hip_g1_fft) and of the
+// openings at every domain point (ckzg_hip_compute_domain_kzg_proofs_batch): the index maps of a stage, which ladder
+// form runs at which size, how a batch is cut into chunks.  Pure functions of their arguments, so that the CPU tests
+// reach them through libhost_shim.so and the kernels use the same maps (HD).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "field.hpp"
+
+namespace ckzg {
+
+constexpr int G1_FFT_MAX_LOG = 13;   // the longest transform: the 8192 roots of unity of the setup
+
+// log2(n) for a transform length the library serves (a power of two up to 8192), -1 otherwise
+inline int g1_fft_log2(uint64_t n) {
+    if (n == 0 || (n & (n - 1)) != 0 || n > ((uint64_t)1 << G1_FFT_MAX_LOG)) return -1;
+    int l = 0;
+    while (((uint64_t)1 << l) < n) l++;
+    return l;
+}
+
+// Stage s of a length-2^logn transform (butterfly span 2^s) has n/2 butterflies; those with j = 0 have twiddle 1 and
+// need no ladder.  The others are numbered densely, m = 0 .. g1_fft_ladders(logn, s) - 1, group-major:
+//   group = m / (half - 1), j = 1 + m % (half - 1), slot of the multiplied point i1 = group * 2^s + half + j,
+//   twiddle w_8192^(j * 8192 / 2^s)  (the same exponent whatever n is: w_n^(j n / 2^s)).
+HD uint32_t g1_fft_ladders(int logn, int s) { return s < 2 ? 0u : (1u << (logn - 1)) - (1u << (logn - s)); }
+HD void g1_fft_ladder_index(uint32_t m, int s, uint32_t &i1, uint32_t &root) {
+    const uint32_t half = 1u << (s - 1), per = half - 1u;
+    const uint32_t group = m / per, j = 1u + (m - group * per);
+    i1 = (group << s) + half + j;
+    root = j << (G1_FFT_MAX_LOG - s);
+}
+
+// Which ladder form a launch takes.  A half-ladder (one 128-bit GLV half of one product) runs on one lane or on the four
+// lanes of a quad (g1_quad.hpp: a 2.3-3x shorter dependent chain for four times the lanes).  The quad form is taken
+// while it still leaves the chip under-filled: up to quad_max products per launch, 2 x 4 x 8192 lanes = 1024 waves = one
+// wave per SIMD of the 256 compute units at the default.
+constexpr uint64_t G1_FFT_QUAD_MAX_DEFAULT = 8192;
+enum G1FftForm { G1_FFT_FORM_QUAD = 0, G1_FFT_FORM_LANE = 1 };
+inline int g1_fft_form(uint64_t products, uint64_t quad_max) { return products <= quad_max ? G1_FFT_FORM_QUAD : G1_FFT_FORM_LANE; }
+// the form of the stage with the most ladders of `count` transforms of length 2^logn (the last stage of a pass: every
+// stage of a call takes its own decision, this is the one the tests aim at)
+inline int g1_fft_form_at(int logn, uint64_t count, uint64_t quad_max) {
+    return g1_fft_form(count * g1_fft_ladders(logn, logn), quad_max);
+}
+
+// The chunks of a batch of n blobs on one device: chunk c covers [c * chunk, min(n, (c + 1) * chunk)).
+inline uint64_t domain_chunk_count(uint64_t n, uint64_t chunk) { return chunk ? (n + chunk - 1) / chunk : 0; }
+inline uint64_t domain_chunk_size(uint64_t n, uint64_t chunk, uint64_t c) {
+    const uint64_t lo = c * chunk;
+    if (lo >= n) return 0;
+    return n - lo < chunk ? n - lo : chunk;
+}
+
+// The circulant vector of the single-point FK20 (N = 4096 coefficients c, length 2N): v[0] = c[N-1], v[1 .. N+1] = 0,
+// v[N+2+j] = c[1+j] for j = 0 .. N-3.  Returns the coefficient index that slot t reads, or -1 for a zero slot.
+HD int domain_circulant_source(uint32_t t, uint32_t N) {
+    if (t == 0) return (int)N - 1;
+    if (t >= N + 2u) return (int)(t - (N + 1u));
+    return -1;
+}
+
+}  // namespace ckzg

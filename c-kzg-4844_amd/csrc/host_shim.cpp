@@ -1038,3 +1038,17 @@ extern "C" int hs_locate_cells_host(uint8_t *ok, uint8_t *status, uint64_t *stat
     stats[1] = res.open.size();
     return 0;
 }
+
+// ---- g1_fft_plan.hpp: the index maps, the form picker and the chunk split of the general G1 transform and of the
+// ---- openings at every domain point (tests/test_domain_openings_cpu.py) ----
+#include "g1_fft_plan.hpp"
+
+extern "C" int hs_g1_fft_log2(uint64_t n) { return g1_fft_log2(n); }
+extern "C" uint32_t hs_g1_fft_ladders(int logn, int s) { return g1_fft_ladders(logn, s); }
+extern "C" void hs_g1_fft_ladder_index(uint32_t m, int s, uint32_t *i1, uint32_t *root) { g1_fft_ladder_index(m, s, *i1, *root); }
+extern "C" int hs_g1_fft_form(uint64_t products, uint64_t quad_max) { return g1_fft_form(products, quad_max); }
+extern "C" int hs_g1_fft_form_at(int logn, uint64_t count, uint64_t quad_max) { return g1_fft_form_at(logn, count, quad_max); }
+extern "C" uint64_t hs_g1_fft_quad_max_default() { return G1_FFT_QUAD_MAX_DEFAULT; }
+extern "C" uint64_t hs_domain_chunk_count(uint64_t n, uint64_t chunk) { return domain_chunk_count(n, chunk); }
+extern "C" uint64_t hs_domain_chunk_size(uint64_t n, uint64_t chunk, uint64_t c) { return domain_chunk_size(n, chunk, c); }
+extern "C" int hs_domain_circulant_source(uint32_t t, uint32_t n) { return domain_circulant_source(t, n); }

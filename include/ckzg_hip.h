@@ -422,6 +422,44 @@ C_KZG_RET ckzg_hip_g1_lincomb(g1_t *out, const g1_t *p, const fr_t *coeffs, uint
  * tiles of 256 points scanned through LDS, the tiles' totals scanned the same way, about ten additions per point. */
 C_KZG_RET ckzg_hip_g1_prefix_sums(g1_t *out, const g1_t *p, uint64_t len, const KZGSettings *s);
 
+/* g1_fft / g1_ifft_unscaled (src/eip7594/fft.c:199-240) on the GPU at any power of two up to 8192: `count`
+ * independent transforms of length n, contiguous, reference in-memory form (g1_t Jacobian) in and out, natural order
+ * in and out.  inverse == 0: out[k] = sum_m [w_n^(k m)] in[m] with w_n = roots_of_unity[8192 / n]; inverse != 0: the
+ * same sum with w_n^-1 and NO factor 1/n.  n == 0 or count == 0 writes nothing and returns C_KZG_OK; n == 1 copies the
+ * input.  C_KZG_BADARGS (nothing written) for an n that is not a power of two or is above 8192, for NULL pointers with
+ * work to do, and for an input point that is not on the curve or not in the prime-order subgroup: the twiddle products
+ * are GLV ladders, valid only there -- the reference function accepts any curve point (the same deviation as
+ * ckzg_hip_g1_lincomb).  The identity is a valid input anywhere.  Complete: the identity, u == v and u == -v in a
+ * butterfly are handled.  Host pointers.  One add/subtract launch and one ladder launch (plus the sum of the two GLV
+ * halves) per stage, in place in HBM; the ladders have fixed addition positions, so lanes with different twiddles stay
+ * in step, and run on four lanes per half-product while the launch would otherwise leave the chip under-filled
+ * (csrc/g1_fft_plan.hpp).  The twiddle records of the 8192 roots (256 KB) are built by the first call on a stream slot
+ * and kept until free_trusted_setup. */
+C_KZG_RET ckzg_hip_g1_fft(g1_t *out, const g1_t *in, uint64_t n, uint64_t count, int inverse, const KZGSettings *s);
+
+/* The openings of n blobs at EVERY point of the evaluation domain: proofs is [n][4096], and proofs[4096 i + j] is byte
+ * for byte the *proof_out of compute_kzg_proof(&proof, &y, &blobs[i], z_j, s) with z_j = brp_roots_of_unity[j] as 32
+ * big-endian bytes -- the proof for field element j of blob i; the y of that call is the element itself, so there is no
+ * ys output.  One blob's 4096 openings are one Toeplitz product and one G1 transform (FK20 in its single-point form:
+ * 8192 one-term products, an inverse transform of length 8192 and a forward transform of length 4096), not 4096
+ * fixed-base sums.  A blob with a non-canonical field element gets status[i] = 1, its 4096 outputs are unspecified, the
+ * other blobs are still computed and the call returns C_KZG_BADARGS.  status may be NULL; n == 0 returns C_KZG_OK;
+ * NULL proofs or blobs with n > 0 give C_KZG_BADARGS; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  With
+ * several devices contiguous runs of blobs go to each; on a device the blobs go in chunks of at most
+ * CKZG_HIP_DOMAIN_CHUNK_BLOBS (about 6.3 MB of HBM per blob of a chunk).  The transformed setup (8192 affine points,
+ * 768 KB) is built by the first call on a stream slot and kept until free_trusted_setup; if it cannot be allocated the
+ * call returns C_KZG_MALLOC, keeps nothing, and the next call builds it. */
+#define CKZG_HIP_DOMAIN_CHUNK_BLOBS 16
+C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch(KZGProof *proofs, uint8_t *status, const Blob *blobs, uint64_t n,
+                                                   const KZGSettings *s);
+
+/* Same with blobs (n Blob), proofs (n x 4096 x 48 bytes) and status (n bytes; may be NULL) resident in HBM.  As for the
+ * other *_device calls, invalid blobs are reported through d_status ONLY (d_status[i] = 1 = C_KZG_BADARGS): the return
+ * value is C_KZG_OK unless the call itself failed.  A host pointer, or buffers on different GPUs, give C_KZG_BADARGS
+ * and nothing is launched. */
+C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch_device(void *d_proofs, void *d_status, const void *d_blobs,
+                                                          uint64_t n, const KZGSettings *s);
+
 /* Timing hook for bench.py: elapsed milliseconds of the named kernel family inside the last
  * batch call, measured with hipEvents on the stream the kernels were launched on (for a call that was
  * processed in several chunks: the last chunk).
