@@ -250,6 +250,33 @@ class Kzg:
         return ([[raw[per * i + 48 * j:per * i + 48 * j + 48] for j in range(4096)] for i in range(n)],
                 [int(v) for v in st[:n]])
 
+    def compute_coset_kzg_proofs_batch(self, blobs, log2_coset, want_evals=False):
+        """ckzg_hip_compute_coset_kzg_proofs_batch: for every blob its m = 8192 >> log2_coset multiproofs on the cosets
+        of 2^log2_coset points of the 8192-point extended domain; proofs[i][c] opens the points brp_roots_of_unity[c l ..
+        c l + l - 1].  Returns (proofs, status), or (proofs, evals, status) with want_evals: evals[i] holds the 8192
+        extended evaluations of blob i in that order (the bytes of its 128 cells, back to back).  status[i] = 1
+        (C_KZG_BADARGS) for a blob with a non-canonical element, whose outputs are then unspecified."""
+        n = len(blobs)
+        for b in blobs:
+            _check(len(b) == BYTES_PER_BLOB, "blob")
+        _check(0 <= log2_coset <= 6, "log2_coset")
+        m = 8192 >> log2_coset
+        per, per_ev = m * 48, 8192 * 32
+        proofs = C.create_string_buffer(per * max(n, 1))
+        evals = C.create_string_buffer(per_ev * max(n, 1)) if want_evals else None
+        st = (C.c_uint8 * max(n, 1))()
+        ret = self._fn("ckzg_hip_compute_coset_kzg_proofs_batch")(proofs, evals, st, b"".join(blobs), C.c_uint64(n),
+                                                                  C.c_uint32(log2_coset), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_compute_coset_kzg_proofs_batch -> C_KZG_RET %d" % ret)
+        raw = proofs.raw
+        out = [[raw[per * i + 48 * j:per * i + 48 * j + 48] for j in range(m)] for i in range(n)]
+        status = [int(v) for v in st[:n]]
+        if not want_evals:
+            return out, status
+        ev = evals.raw
+        return out, [ev[per_ev * i:per_ev * (i + 1)] for i in range(n)], status
+
     def verify_blob_kzg_proof(self, blob, commitment, proof):
         _check(len(blob) == BYTES_PER_BLOB, "blob")
         _check(len(commitment) == 48 and len(proof) == 48, "commitment/proof")

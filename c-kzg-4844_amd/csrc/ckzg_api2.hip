@@ -3355,3 +3355,119 @@ extern "C" C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch_device(void *d_pro
         return C_KZG_OK;
     });
 }
+
+// ------------------------------------------------------------------------------------------
+// The openings of a blob on every coset of the extended domain, coset sizes 1 to 64
+// (ckzg_hip_compute_coset_kzg_proofs_batch[_device]; g1_fft.hip, g1_fft_plan.hpp)
+// ------------------------------------------------------------------------------------------
+
+namespace {
+
+static_assert(CKZG_HIP_COSET_MAX_LOG2 == COSET_MAX_LOG, "the header and g1_fft_plan.hpp name the same largest coset");
+
+// what a chunk of up to m blobs needs next to the blobs and the outputs themselves
+struct CosetBufs {
+    ABuf<uint32_t> bad;
+    ABuf<uint8_t> scratch;
+    static size_t bytes(uint64_t m) { return m * sizeof(uint32_t) + dev::coset_proofs_scratch_bytes(m) + 2 * 256; }
+    CosetBufs(Arena &ar, uint64_t m) : bad(ar, m), scratch(ar, dev::coset_proofs_scratch_bytes(m)) {}
+    bool ok() const { return bad.p && scratch.p; }
+};
+
+// one chunk of k <= CKZG_HIP_COSET_CHUNK_BLOBS blobs in HBM: enqueue-only, on the slot's compute stream; d_evals and
+// d_status may be null
+C_KZG_RET coset_proofs_chunk(dev::DeviceCtx *ctx, const CosetBufs &b, uint8_t *d_proofs48, uint8_t *d_evals, uint8_t *d_status,
+                             const uint8_t *d_blobs, uint64_t k, int e) {
+    OKB(hipMemsetAsync(b.bad.p, 0, k * sizeof(uint32_t), ctx->stream) == hipSuccess);
+    RC(dev::coset_proofs_enqueue(ctx, d_proofs48, d_evals, b.bad.p, d_blobs, k, e, b.scratch.p));
+    if (d_status) RC(dev::flags_to_status_enqueue(ctx, d_status, b.bad.p, k));
+    return C_KZG_OK;
+}
+
+// One device's share of a host-pointer call: per chunk, blobs to HBM, the chunk, proofs | evaluations | statuses back
+C_KZG_RET coset_proofs_on(dev::DeviceCtx *ctx, KZGProof *proofs, Bytes32 *evals, uint8_t *status, const Blob *blobs, uint64_t n, int e) {
+    if (n == 0) return C_KZG_OK;
+    const uint64_t CH = CKZG_HIP_COSET_CHUNK_BLOBS, np = coset_proofs_per_blob(e), per = np * 48;
+    const uint64_t per_ev = evals ? (uint64_t)FIELD_ELEMENTS_PER_EXT_BLOB * 32 : 0;
+    const uint64_t m = domain_chunk_size(n, CH, 0);
+    RC(dev::coset_xhat_ensure(ctx, e));
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(m * (BYTES_PER_BLOB + per + per_ev + 1) + CosetBufs::bytes(m) + 2 * 256));
+    ArenaTrim trim(ar);
+    ABuf<uint8_t> d_blobs(ar, m * BYTES_PER_BLOB), d_res(ar, m * (per + per_ev + 1));
+    CosetBufs b(ar, m);
+    OKM(d_blobs.p && d_res.p && b.ok());
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the caller's buffers or the arena's reuse
+    std::vector<uint8_t> st(m);
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
+        const uint64_t k = domain_chunk_size(n, CH, c);
+        uint8_t *d_ev = d_res.p + k * per, *d_st = d_ev + k * per_ev;
+        OKB(hipMemcpyAsync(d_blobs.p, blobs + off, k * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        RC(coset_proofs_chunk(ctx, b, d_res.p, evals ? d_ev : nullptr, d_st, d_blobs.p, k, e));
+        OKB(hipMemcpyAsync(proofs + off * np, d_res.p, k * per, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+        if (evals)
+            OKB(hipMemcpyAsync(evals + off * FIELD_ELEMENTS_PER_EXT_BLOB, d_ev, k * per_ev, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+        OKB(hipMemcpyAsync(st.data(), d_st, k, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
+        for (uint64_t i = 0; i < k; i++) {
+            if (status) status[off + i] = st[i];
+            if (st[i]) ret = C_KZG_BADARGS;
+        }
+        off += k;
+    }
+    return ret;
+}
+
+}  // namespace
+
+extern "C" C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch(KZGProof *proofs, Bytes32 *evals, uint8_t *status, const Blob *blobs,
+                                                            uint64_t n, uint32_t log2_coset, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (log2_coset > CKZG_HIP_COSET_MAX_LOG2 || (n && (!proofs || !blobs))) return C_KZG_BADARGS;
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        const int e = (int)log2_coset;
+        const uint64_t np = coset_proofs_per_blob(e);
+        return for_each_device_shard(s, n, 1, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return coset_proofs_on(ctx, proofs + lo * np, evals ? evals + lo * FIELD_ELEMENTS_PER_EXT_BLOB : nullptr,
+                                   status ? status + lo : nullptr, blobs + lo, hi - lo, e);
+        });
+    });
+}
+
+extern "C" C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proofs, void *d_evals, void *d_status, const void *d_blobs,
+                                                                   uint64_t n, uint32_t log2_coset, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (log2_coset > CKZG_HIP_COSET_MAX_LOG2 || (n && (!d_proofs || !d_blobs))) return C_KZG_BADARGS;
+        SettingsCtx *sc = settings_of(s);
+        if (!sc) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        const void *ptrs[4] = {d_proofs, d_evals, d_status, d_blobs};
+        const int pool = pool_of_pointers(sc, ptrs, 4);
+        if (pool < 0) return C_KZG_BADARGS;
+        Lease lease(s, pool);
+        dev::DeviceCtx *ctx = lease.ctx;
+        if (!ctx) return C_KZG_ERROR;
+        const int e = (int)log2_coset;
+        const uint64_t CH = CKZG_HIP_COSET_CHUNK_BLOBS, per = (uint64_t)coset_proofs_per_blob(e) * 48;
+        const uint64_t per_ev = (uint64_t)FIELD_ELEMENTS_PER_EXT_BLOB * 32;
+        const uint64_t m = domain_chunk_size(n, CH, 0);
+        RC(dev::coset_xhat_ensure(ctx, e));
+        Arena &ar = ctx->api_arena;
+        OKM(ar.begin(CosetBufs::bytes(m)));
+        ArenaTrim trim(ar);
+        CosetBufs b(ar, m);
+        OKM(b.ok());
+        StreamDrain drain{ctx->stream};
+        uint8_t *out = static_cast<uint8_t *>(d_proofs), *ev = static_cast<uint8_t *>(d_evals), *st = static_cast<uint8_t *>(d_status);
+        const uint8_t *bl = static_cast<const uint8_t *>(d_blobs);
+        for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
+            const uint64_t k = domain_chunk_size(n, CH, c);
+            RC(coset_proofs_chunk(ctx, b, out + off * per, ev ? ev + off * per_ev : nullptr, st ? st + off : nullptr,
+                                  bl + off * BYTES_PER_BLOB, k, e));
+            off += k;
+        }
+        return C_KZG_OK;
+    });
+}

@@ -341,5 +341,179 @@ int domain_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint32_t *d_bad, 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// Openings on every coset of the extended domain, coset size l = 2^e (FK20 as in src/eip7594/fk20.c, at any cell size
+// up to 64).  k = 4096 / l; the l Toeplitz columns of length 2k fill one row of 8192 column-major, for the scalars, the
+// transformed setup and the products alike, so the scalar transform, the ladders and the sum of the GLV halves are
+// those of the single-point form.  Then the columns are added, and the row's first 2k entries go through the inverse
+// transform (DIT, natural out), lose their upper half and go through the forward transform (DIF): position c of its
+// output is the proof of coset c of the bit-reversed domain.  e = 0 is the single-point form on all 8192 points.
+// ------------------------------------------------------------------------------------------
+
+// xin[t] = g1_values_monomial[coset_setup_source(t)], the identity where that is -1 (g1_fft_plan.hpp)
+__global__ void k_coset_xext_gather(G1XYZZ *xin, const G1Affine *monomial, int e) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (uint32_t)N_EXT) return;
+    const int src = coset_setup_source(t, e, (uint32_t)N_BLOB);
+    xin[t] = src >= 0 ? xyzz_from_affine(monomial[src]) : G1XYZZ::inf();
+}
+
+// v[b][t]: the l circulant columns of blob b from its monomial coefficients (g1_fft_plan.hpp: coset_circulant_source)
+__global__ void k_coset_circulant(Fr *v, const Fr *poly, size_t total, int e) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const size_t b = g >> 13;
+    const int src = coset_circulant_source((uint32_t)g & (uint32_t)(N_EXT - 1), e, (uint32_t)N_BLOB);
+    const uint4 *q = reinterpret_cast<const uint4 *>(poly + b * N_BLOB + (src < 0 ? 0 : src));
+    uint4 lo = q[0], hi = q[1];
+    if (src < 0) lo = hi = make_uint4(0, 0, 0, 0);
+    uint4 *o = reinterpret_cast<uint4 *>(v + g);
+    o[0] = lo;
+    o[1] = hi;
+}
+
+// Column sum, one strided pass: a row of 8192 points holds columns of 2^logw points; column `part` of row b <- the sum
+// of its columns part, part + parts, ..., part + (ncols - 1) parts, at every position t.  One lane per (b, part, t), t
+// fastest: a wave reads 64 consecutive points of one column per step.  In place: a lane reads and writes position t of
+// the columns = part (mod parts) of its row, which no other lane of the launch touches.  The addition is complete.
+__global__ __launch_bounds__(64) void k_coset_colsum(G1XYZZ *u, int logw, uint32_t parts, uint32_t ncols, size_t total) {
+    const size_t g = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (g >= total) return;
+    const size_t t = g & (((size_t)1 << logw) - 1), rest = g >> logw;
+    const size_t b = rest / parts, part = rest - b * parts;
+    G1XYZZ *col = u + b * N_EXT + (part << logw) + t;
+    const size_t step = (size_t)parts << logw;
+    bool ai;
+    XYZZ28 a = xyzz28_from_xyzz(col[0], ai);
+    for (uint32_t j = 1; j < ncols; j++) {
+        bool pi;
+        const XYZZ28 p = xyzz28_from_xyzz(col[j * step], pi);
+        xyzz28_add(a, ai, p, pi);
+    }
+    col[0] = xyzz28_to_xyzz(a, ai);
+}
+
+// u[b][2^(logn-1) .. 2^logn - 1] <- the identity, on rows of 8192; total = rows * 2^(logn-1)
+__global__ void k_coset_zero_upper(G1XYZZ *u, int logn, size_t total) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const size_t half = (size_t)1 << (logn - 1);
+    u[(g >> (logn - 1)) * N_EXT + half + (g & (half - 1))] = G1XYZZ::inf();
+}
+
+// u[b][t] <- sum_{i < 2^e} u[b][i * 2k + t] for t < 2k = 8192 >> e, on rows of 8192: one pass up to COSET_COLSUM_RADIX
+// columns, two above (g1_fft_plan.hpp: coset_colsum_parts).  Enqueue-only.
+int coset_colsum_enqueue(DeviceCtx *ctx, G1XYZZ *d_u, int e, size_t rows) {
+    if (e < 0 || e > COSET_MAX_LOG || rows > ((size_t)1 << 17)) return 2;
+    if (e == 0 || rows == 0) return 0;
+    const int logw = G1_FFT_MAX_LOG - e;
+    const uint32_t l = 1u << e, parts = coset_colsum_parts(e);
+    if (parts > 1) {
+        const size_t total = (rows * parts) << logw;
+        hipLaunchKernelGGL(k_coset_colsum, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, d_u, logw, parts, l / parts, total);
+    }
+    const size_t total = rows << logw;
+    hipLaunchKernelGGL(k_coset_colsum, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, d_u, logw, 1u,
+                       parts > 1 ? parts : l, total);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The transformed setup of coset size 2^e, this slot's own: the l columns, each through the forward transform of length
+// 2k, affine, DIF order.  Built by the slot's first call with that e, kept until the slot goes; a failure keeps
+// nothing.  e = 0 is the single-point form's (d_domain_xhat), shared.
+int coset_xhat_ensure(DeviceCtx *ctx, int e) {
+    if (e < 0 || e > COSET_MAX_LOG) return 2;
+    if (e == 0) return domain_xhat_ensure(ctx);
+    if (ctx->d_coset_xhat[e]) return 0;
+    int rc = g1_fft_roots_ensure(ctx);
+    if (rc) return rc;
+    const int logn = G1_FFT_MAX_LOG - e;
+    const size_t l = (size_t)1 << e;
+    DevTmp xin, tmp, prefix, out;   // gone on every exit path
+    HIP_TRY(hipMalloc(&xin.p, (size_t)N_EXT * sizeof(G1XYZZ)));
+    HIP_TRY(hipMalloc(&tmp.p, g1_fft_tmp_points(logn, l) * sizeof(G1XYZZ)));
+    HIP_TRY(hipMalloc(&prefix.p, (size_t)N_EXT * sizeof(Fp)));
+    HIP_TRY(hipMalloc(&out.p, domain_xhat_bytes()));
+    G1XYZZ *d_xin = static_cast<G1XYZZ *>(xin.p);
+    hipLaunchKernelGGL(k_coset_xext_gather, dim3(N_EXT / 256), dim3(256), 0, ctx->stream, d_xin, ctx->d_mono, e);
+    rc = g1_fft_enqueue(ctx, d_xin, static_cast<G1XYZZ *>(tmp.p), logn, l, (size_t)1 << logn, /*dif=*/true, /*inverse=*/0);
+    if (!rc) rc = batch_to_affine_device(ctx, static_cast<G1Affine *>(out.p), d_xin, static_cast<Fp *>(prefix.p), N_EXT);
+    // the scratch is freed when this function returns: nothing may still be running on it, error or not
+    if (dev::sync_stream(ctx->stream) != hipSuccess && !rc) rc = 2;
+    if (rc) return rc;
+    ctx->d_coset_xhat[e] = static_cast<G1Affine *>(out.p);
+    out.p = nullptr;
+    return 0;
+}
+
+// the scratch of the single-point form serves every coset size: the affine points and the inversion prefixes of the
+// output (up to 8192 per blob at e = 0) lie on the rows of u once these have been gathered
+size_t coset_proofs_scratch_bytes(size_t k) { return domain_proofs_scratch_bytes(k); }
+
+// d_blobs[k] (bytes) -> d_proofs48[k][8192 >> e] and, if d_evals != nullptr, d_evals[k][8192][32], the extended
+// evaluations in cell order; d_bad[k] (zeroed by the caller on the stream) |= 1 for a blob with a non-canonical element.
+// Enqueue-only, on ctx->stream; `scratch` holds coset_proofs_scratch_bytes(k).
+int coset_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint8_t *d_evals, uint32_t *d_bad, const uint8_t *d_blobs, size_t k,
+                         int e, uint8_t *scratch) {
+    if (k == 0) return 0;
+    if (e < 0 || e > COSET_MAX_LOG || k > ((size_t)1 << 17)) return 2;
+    const G1Affine *xhat = e == 0 ? ctx->d_domain_xhat : ctx->d_coset_xhat[e];
+    if (!xhat) return 2;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        uint8_t *p = scratch + off;
+        off += al256(bytes);
+        return p;
+    };
+    Fr *poly = reinterpret_cast<Fr *>(take(k * N_BLOB * sizeof(Fr)));
+    Fr *v = reinterpret_cast<Fr *>(take(k * N_EXT * sizeof(Fr)));
+    uint32_t *glv = reinterpret_cast<uint32_t *>(take(k * N_EXT * 8 * sizeof(uint32_t)));
+    G1XYZZ *u = reinterpret_cast<G1XYZZ *>(take(k * N_EXT * sizeof(G1XYZZ)));
+    G1XYZZ *tmp = reinterpret_cast<G1XYZZ *>(take(2 * k * N_EXT * sizeof(G1XYZZ)));
+    const int logn = G1_FFT_MAX_LOG - e;
+    const size_t m = coset_proofs_per_blob(e), nout = k * m;
+    // the output's affine points and prefixes: on u, once its rows have been gathered into tmp
+    G1Affine *aff = reinterpret_cast<G1Affine *>(u);
+    Fp *prefix = reinterpret_cast<Fp *>(reinterpret_cast<uint8_t *>(u) + al256(nout * sizeof(G1Affine)));
+    static_assert(sizeof(G1Affine) + sizeof(Fp) + 1 <= sizeof(G1XYZZ), "the output's affine form fits the rows of u");
+    // monomial coefficients and, if wanted, the extended evaluations (v is their scratch); the l circulant columns,
+    // each through its transform / 2k
+    int rc = cells_stage_enqueue(ctx, d_evals, poly, v, d_bad, d_blobs, k);
+    if (rc) return rc;
+    const size_t total = k * N_EXT;
+    hipLaunchKernelGGL(k_coset_circulant, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, v, poly, total, e);
+    HIP_TRY(hipGetLastError());
+    rc = fr_ntt_batch(ctx, v, k << e, logn, /*dif=*/true, /*inverse=*/false, /*scale=*/true);
+    if (rc) return rc;
+    // product[i][t] = vhat_i[t] xhat_i[t], both in the DIF output order; u[t] = their sum over the columns
+    hipLaunchKernelGGL(k_domain_scalars, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, glv, v, total);
+    launch_ladders(total, [&](bool quad, dim3 grid, size_t items) {
+        if (quad)
+            hipLaunchKernelGGL(k_domain_ladder<true>, grid, dim3(64), 0, ctx->stream, tmp, xhat, glv, items);
+        else
+            hipLaunchKernelGGL(k_domain_ladder<false>, grid, dim3(64), 0, ctx->stream, tmp, xhat, glv, items);
+    });
+    hipLaunchKernelGGL(k_domain_sum, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, u, tmp, total);
+    HIP_TRY(hipGetLastError());
+    rc = coset_colsum_enqueue(ctx, u, e, k);
+    if (rc) return rc;
+    // h = the first k entries of the unscaled inverse transform; proofs = the forward transform of (h, 0), in place in
+    // the first 2k entries of the rows
+    rc = g1_fft_enqueue(ctx, u, tmp, logn, k, N_EXT, /*dif=*/false, /*inverse=*/1);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_coset_zero_upper, dim3((unsigned)((nout / 2 + 255) / 256)), dim3(256), 0, ctx->stream, u, logn, nout / 2);
+    rc = g1_fft_enqueue(ctx, u, tmp, logn, k, N_EXT, /*dif=*/true, /*inverse=*/0);
+    if (rc) return rc;
+    // the heads of the rows, contiguous (tmp is free again), normalised and compressed
+    HIP_TRY(hipMemcpy2DAsync(tmp, m * sizeof(G1XYZZ), u, (size_t)N_EXT * sizeof(G1XYZZ), m * sizeof(G1XYZZ), k,
+                             hipMemcpyDeviceToDevice, ctx->stream));
+    rc = batch_to_affine_device(ctx, aff, tmp, prefix, nout);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_domain_compress, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, d_proofs48, aff, nout);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 }  // namespace dev
 }  // namespace ckzg

@@ -1,7 +1,8 @@
 // g1_fft_plan.hpp -- the host decisions of the general G1 transform (g1_fft.hip; ckzg_hip_g1_fft) and of the
-// openings at every domain point (ckzg_hip_compute_domain_kzg_proofs_batch): the index maps of a stage, which ladder
-// form runs at which size, how a batch is cut into chunks.  Pure functions of their arguments, so that the CPU tests
-// reach them through libhost_shim.so and the kernels use the same maps (HD).
+// openings at every domain point (ckzg_hip_compute_domain_kzg_proofs_batch) and on every coset of the extended domain
+// (ckzg_hip_compute_coset_kzg_proofs_batch): the index maps of a stage, which ladder form runs at which size, how a
+// batch is cut into chunks, where a Toeplitz column reads its coefficients and its setup points.  Pure functions of
+// their arguments, so that the CPU tests reach them through libhost_shim.so and the kernels use the same maps (HD).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -60,5 +61,36 @@ HD int domain_circulant_source(uint32_t t, uint32_t N) {
     if (t >= N + 2u) return (int)(t - (N + 1u));
     return -1;
 }
+
+// ---- openings on every coset of the extended domain (ckzg_hip_compute_coset_kzg_proofs_batch) ----
+// Coset size l = 2^e, e <= COSET_MAX_LOG; k = 4096 / l rows; l Toeplitz columns of length 2k = 8192 / l, which fill one
+// row of 8192 column-major: slot t of a row is position t mod 2k of column t / 2k.  m = 2k proofs per blob.
+constexpr int COSET_MAX_LOG = 6;
+HD uint32_t coset_proofs_per_blob(int e) { return 8192u >> e; }
+
+// Column i of the circulant (toeplitz_coeffs_stride(p, i, l), src/eip7594/fk20.c): v_i[0] = p[4095 - i],
+// v_i[1 .. k+1] = 0, v_i[k+2+j] = p[2l - i - 1 + j l].  Returns the coefficient index that slot t of the row reads, or
+// -1 for a zero slot.  N = 4096 in the product; the tests also run smaller N.
+HD int coset_circulant_source(uint32_t t, int e, uint32_t N) {
+    const uint32_t l = 1u << e, k = N >> e, i = t / (2u * k), pos = t - i * 2u * k;
+    if (pos == 0) return (int)(N - 1u - i);
+    if (pos >= k + 2u) return (int)(2u * l - i - 1u + (pos - k - 2u) * l);
+    return -1;
+}
+
+// The setup vector of column i before its transform: X_i[j] = g1_values_monomial[N - l - 1 - i - j l] for j < k - 1,
+// the identity above (setup.c:238-330).  Returns the monomial index that slot t of the row reads, or -1 for the identity.
+HD int coset_setup_source(uint32_t t, int e, uint32_t N) {
+    const uint32_t l = 1u << e, k = N >> e, i = t / (2u * k), j = t - i * 2u * k;
+    if (j + 1u >= k) return -1;
+    return (int)(N - l - 1u - i - j * l);
+}
+
+// The column sum u[t] = sum_{i < l} product[i][t] runs as strided passes, one lane per output and pass, the lanes of a
+// wave on consecutive t.  One pass of l sequential additions leaves 8192 / l lanes per blob, so above
+// COSET_COLSUM_RADIX columns the sum is split: `parts` lanes per output each add the columns i = part (mod parts) into
+// row `part` (COSET_COLSUM_RADIX additions deep), then one lane adds the `parts` rows.  parts == 1: a single pass.
+constexpr uint32_t COSET_COLSUM_RADIX = 8;
+HD uint32_t coset_colsum_parts(int e) { return (1u << e) > COSET_COLSUM_RADIX ? (1u << e) / COSET_COLSUM_RADIX : 1u; }
 
 }  // namespace ckzg

@@ -1052,3 +1052,11 @@ extern "C" uint64_t hs_g1_fft_quad_max_default() { return G1_FFT_QUAD_MAX_DEFAUL
 extern "C" uint64_t hs_domain_chunk_count(uint64_t n, uint64_t chunk) { return domain_chunk_count(n, chunk); }
 extern "C" uint64_t hs_domain_chunk_size(uint64_t n, uint64_t chunk, uint64_t c) { return domain_chunk_size(n, chunk, c); }
 extern "C" int hs_domain_circulant_source(uint32_t t, uint32_t n) { return domain_circulant_source(t, n); }
+
+// ---- the openings on every coset of the extended domain (tests/test_coset_openings_cpu.py) ----
+extern "C" int hs_coset_max_log() { return COSET_MAX_LOG; }
+extern "C" uint32_t hs_coset_proofs_per_blob(int e) { return coset_proofs_per_blob(e); }
+extern "C" int hs_coset_circulant_source(uint32_t t, int e, uint32_t n) { return coset_circulant_source(t, e, n); }
+extern "C" int hs_coset_setup_source(uint32_t t, int e, uint32_t n) { return coset_setup_source(t, e, n); }
+extern "C" uint32_t hs_coset_colsum_radix() { return COSET_COLSUM_RADIX; }
+extern "C" uint32_t hs_coset_colsum_parts(int e) { return coset_colsum_parts(e); }

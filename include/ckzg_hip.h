@@ -460,6 +460,53 @@ C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch(KZGProof *proofs, uint8_t *st
 C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch_device(void *d_proofs, void *d_status, const void *d_blobs,
                                                           uint64_t n, const KZGSettings *s);
 
+/* The openings of n blobs on EVERY coset of the 8192-point extended domain, for any coset size l = 2^e, e = log2_coset
+ * <= CKZG_HIP_COSET_MAX_LOG2.  With m = 8192 >> e, proofs is [n][m]: proofs[m i + c] is the KZG multiproof of blob i's
+ * polynomial p on coset c, the points brp_roots_of_unity[c l .. c l + l - 1] -- its value is [q_c(tau)]_1 with q_c =
+ * floor(p / (X^l - x_c^l)), x_c = brp_roots_of_unity[c l].  Byte for byte:
+ *   e = 0  proofs[8192 i + j] is the *proof_out of compute_kzg_proof(blob_i, z_j), z_j = brp_roots_of_unity[j], all 8192
+ *          entries; for j < 4096 that is the output of ckzg_hip_compute_domain_kzg_proofs_batch;
+ *   e = 6  proofs[128 i + c] is proof c of compute_cells_and_kzg_proofs.
+ * evals (optional, [n][8192]) receives the extended evaluations in the same order: the bytes of the 128 cells of
+ * compute_cells_and_kzg_proofs back to back, the same for every e; the ys of coset c are evals[8192 i + c l ..].
+ * Who verifies the output: e = 0 by verify_kzg_proof and ckzg_hip_verify_kzg_proof_batch[_locate], e = 6 by
+ * verify_cell_kzg_proof_batch; for 1 <= e <= 5 this library has NO verifier.  The sizes are tied together by
+ * proof_e[c] = [1 / (2a)] (proof_{e-1}[2c] - proof_{e-1}[2c+1]), a = x_c^(l/2).
+ * Statuses and return values are those of ckzg_hip_compute_domain_kzg_proofs_batch: a blob with a non-canonical field
+ * element gets status[i] = 1, its outputs are unspecified, the other blobs are still computed and the call returns
+ * C_KZG_BADARGS.  status and evals may be NULL; n == 0 returns C_KZG_OK; NULL proofs or blobs with n > 0, or e > 6,
+ * give C_KZG_BADARGS with nothing written and nothing launched; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.
+ * With several devices contiguous runs of blobs go to each; on a device the blobs go in chunks of at most
+ * CKZG_HIP_COSET_CHUNK_BLOBS, with the scratch of the domain call (about 6.3 MB of HBM per blob of a chunk).
+ * The same algorithm at every size (FK20): 8192 one-term products per blob whatever e is, a sum over the l columns, an
+ * inverse and a forward G1 transform of length m.  The transformed setup of a size (8192 affine points, 768 KB) is
+ * built by the first call with that e on a stream slot and kept until free_trusted_setup (e = 0 shares the domain
+ * call's); a failed build keeps nothing and the next call builds it.  Load time and ckzg_hip_table_bytes do not change.
+ * NOT here: the fixed-base-table route for the 8192 products.  compute_cells_and_kzg_proofs has it, so at e = 6 that
+ * call is the faster one and this one is a second, independent road to the same bytes.
+ * Measured (profiles/coset_openings_bench.json): medians of 20 and minima of the wall time, default tables, evals wanted,
+ * first call on fresh settings 17.7 (e = 6) to 43.8 ms (e = 0) against 11.6 to 25.9 for the second.
+ *   e = 0  26.0 (min 25.7) / 47.6 (47.4) / 98.6 (98.3) ms for 1 / 4 / 16 blobs, against 161 (min 161) / 641 (min 640) ms
+ *          at 1 / 4 blobs for ckzg_hip_compute_kzg_proof_batch over the blob repeated at all 8192 points (1 GB of input
+ *          per blob) on a build of the parent commit in the same process: this call's median is below the alternative's
+ *          minimum at both (6.2x, 13.5x); at 16 blobs the alternative was not measured.
+ *   e = 6  11.8 / 13.4 / 19.5 ms against 3.2 (min 3.0) / 3.7 (3.6) / 4.6 (4.5) ms for
+ *          ckzg_hip_compute_cells_and_kzg_proofs_batch: this call is NOT faster, it takes about four times as long at
+ *          every size measured.  compute_cells_and_kzg_proofs wins at e = 6; use it for cells of 64.
+ *   e = 1 .. 5 have no alternative in the library: 20.7 / 18.3 / 16.7 / 15.0 / 13.4 ms for one blob, 58.6 / 45.8 / 30.4 /
+ *          25.2 / 21.5 ms for 16. */
+#define CKZG_HIP_COSET_MAX_LOG2 6
+#define CKZG_HIP_COSET_CHUNK_BLOBS 16
+C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch(KZGProof *proofs, Bytes32 *evals, uint8_t *status, const Blob *blobs,
+                                                  uint64_t n, uint32_t log2_coset, const KZGSettings *s);
+
+/* Same with blobs (n Blob), proofs (n x m x 48 bytes), evals (n x 8192 x 32 bytes; may be NULL) and status (n bytes;
+ * may be NULL) resident in HBM.  Invalid blobs are reported through d_status ONLY (d_status[i] = 1 = C_KZG_BADARGS):
+ * the return value is C_KZG_OK unless the call itself failed.  A host pointer, or buffers on different GPUs, give
+ * C_KZG_BADARGS and nothing is launched. */
+C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proofs, void *d_evals, void *d_status, const void *d_blobs,
+                                                         uint64_t n, uint32_t log2_coset, const KZGSettings *s);
+
 /* Timing hook for bench.py: elapsed milliseconds of the named kernel family inside the last
  * batch call, measured with hipEvents on the stream the kernels were launched on (for a call that was
  * processed in several chunks: the last chunk).
