@@ -3198,8 +3198,10 @@ extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_locate(bool *ok, uint8
 }
 
 // ------------------------------------------------------------------------------------------
-// The G1 transform at the boundary, and the openings of a blob at every point of the evaluation domain
-// (ckzg_hip_g1_fft, ckzg_hip_compute_domain_kzg_proofs_batch[_device]; g1_fft.hip, g1_fft_plan.hpp)
+// The G1 transform at the boundary, and the openings of a blob at every point of the evaluation domain and on every
+// coset of the extended domain, coset sizes 1 to 64: one scaffold for both calls (ckzg_hip_g1_fft,
+// ckzg_hip_compute_domain_kzg_proofs_batch[_device], ckzg_hip_compute_coset_kzg_proofs_batch[_device]; g1_fft.hip,
+// g1_fft_plan.hpp)
 // ------------------------------------------------------------------------------------------
 
 extern "C" C_KZG_RET ckzg_hip_g1_fft(g1_t *out, const g1_t *in, uint64_t n, uint64_t count, int inverse, const KZGSettings *s) {
@@ -3260,142 +3262,49 @@ extern "C" C_KZG_RET ckzg_hip_g1_fft(g1_t *out, const g1_t *in, uint64_t n, uint
 
 namespace {
 
-// what a chunk of up to m blobs needs next to the blobs and the proofs themselves
-struct DomainBufs {
-    ABuf<uint32_t> bad;
-    ABuf<uint8_t> scratch;
-    static size_t bytes(uint64_t m) { return m * sizeof(uint32_t) + dev::domain_proofs_scratch_bytes(m) + 2 * 256; }
-    DomainBufs(Arena &ar, uint64_t m) : bad(ar, m), scratch(ar, dev::domain_proofs_scratch_bytes(m)) {}
-    bool ok() const { return bad.p && scratch.p; }
-};
-
-// one chunk of k <= CKZG_HIP_DOMAIN_CHUNK_BLOBS blobs in HBM: enqueue-only, on the slot's compute stream; d_status may be null
-C_KZG_RET domain_proofs_chunk(dev::DeviceCtx *ctx, const DomainBufs &b, uint8_t *d_proofs48, uint8_t *d_status, const uint8_t *d_blobs,
-                              uint64_t k) {
-    OKB(hipMemsetAsync(b.bad.p, 0, k * sizeof(uint32_t), ctx->stream) == hipSuccess);
-    RC(dev::domain_proofs_enqueue(ctx, d_proofs48, b.bad.p, d_blobs, k, b.scratch.p));
-    if (d_status) RC(dev::flags_to_status_enqueue(ctx, d_status, b.bad.p, k));
-    return C_KZG_OK;
-}
-
-// One device's share of a host-pointer call: per chunk, blobs to HBM, the chunk, proofs | statuses back in one copy
-C_KZG_RET domain_proofs_on(dev::DeviceCtx *ctx, KZGProof *proofs, uint8_t *status, const Blob *blobs, uint64_t n) {
-    if (n == 0) return C_KZG_OK;
-    const uint64_t CH = CKZG_HIP_DOMAIN_CHUNK_BLOBS, per = (uint64_t)FIELD_ELEMENTS_PER_BLOB * 48;
-    const uint64_t m = domain_chunk_size(n, CH, 0);
-    RC(dev::domain_xhat_ensure(ctx));
-    Arena &ar = ctx->api_arena;
-    OKM(ar.begin(m * (BYTES_PER_BLOB + per + 1) + DomainBufs::bytes(m) + 2 * 256));
-    ArenaTrim trim(ar);
-    ABuf<uint8_t> d_blobs(ar, m * BYTES_PER_BLOB), d_res(ar, m * (per + 1));
-    DomainBufs b(ar, m);
-    OKM(d_blobs.p && d_res.p && b.ok());
-    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the caller's buffers or the arena's reuse
-    std::vector<uint8_t> st(m);
-    C_KZG_RET ret = C_KZG_OK;
-    for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
-        const uint64_t k = domain_chunk_size(n, CH, c);
-        OKB(hipMemcpyAsync(d_blobs.p, blobs + off, k * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-        RC(domain_proofs_chunk(ctx, b, d_res.p, d_res.p + k * per, d_blobs.p, k));
-        OKB(hipMemcpyAsync(proofs + off * FIELD_ELEMENTS_PER_BLOB, d_res.p, k * per, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-        OKB(hipMemcpyAsync(st.data(), d_res.p + k * per, k, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-        OKB(dev::sync_stream(ctx->stream) == hipSuccess);
-        for (uint64_t i = 0; i < k; i++) {
-            if (status) status[off + i] = st[i];
-            if (st[i]) ret = C_KZG_BADARGS;
-        }
-        off += k;
-    }
-    return ret;
-}
-
-}  // namespace
-
-extern "C" C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch(KZGProof *proofs, uint8_t *status, const Blob *blobs, uint64_t n,
-                                                             const KZGSettings *s) {
-    return guarded([&]() -> C_KZG_RET {
-        if (n && (!proofs || !blobs)) return C_KZG_BADARGS;
-        if (!settings_of(s)) return C_KZG_ERROR;
-        if (n == 0) return C_KZG_OK;
-        return for_each_device_shard(s, n, 1, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
-            return domain_proofs_on(ctx, proofs + lo * FIELD_ELEMENTS_PER_BLOB, status ? status + lo : nullptr, blobs + lo, hi - lo);
-        });
-    });
-}
-
-extern "C" C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch_device(void *d_proofs, void *d_status, const void *d_blobs,
-                                                                    uint64_t n, const KZGSettings *s) {
-    return guarded([&]() -> C_KZG_RET {
-        if (n && (!d_proofs || !d_blobs)) return C_KZG_BADARGS;
-        SettingsCtx *sc = settings_of(s);
-        if (!sc) return C_KZG_ERROR;
-        if (n == 0) return C_KZG_OK;
-        const void *ptrs[3] = {d_proofs, d_status, d_blobs};
-        const int pool = pool_of_pointers(sc, ptrs, 3);
-        if (pool < 0) return C_KZG_BADARGS;
-        Lease lease(s, pool);
-        dev::DeviceCtx *ctx = lease.ctx;
-        if (!ctx) return C_KZG_ERROR;
-        const uint64_t CH = CKZG_HIP_DOMAIN_CHUNK_BLOBS, per = (uint64_t)FIELD_ELEMENTS_PER_BLOB * 48;
-        const uint64_t m = domain_chunk_size(n, CH, 0);
-        RC(dev::domain_xhat_ensure(ctx));
-        Arena &ar = ctx->api_arena;
-        OKM(ar.begin(DomainBufs::bytes(m)));
-        ArenaTrim trim(ar);
-        DomainBufs b(ar, m);
-        OKM(b.ok());
-        StreamDrain drain{ctx->stream};
-        uint8_t *out = static_cast<uint8_t *>(d_proofs), *st = static_cast<uint8_t *>(d_status);
-        const uint8_t *bl = static_cast<const uint8_t *>(d_blobs);
-        for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
-            const uint64_t k = domain_chunk_size(n, CH, c);
-            RC(domain_proofs_chunk(ctx, b, out + off * per, st ? st + off : nullptr, bl + off * BYTES_PER_BLOB, k));
-            off += k;
-        }
-        return C_KZG_OK;
-    });
-}
-
-// ------------------------------------------------------------------------------------------
-// The openings of a blob on every coset of the extended domain, coset sizes 1 to 64
-// (ckzg_hip_compute_coset_kzg_proofs_batch[_device]; g1_fft.hip, g1_fft_plan.hpp)
-// ------------------------------------------------------------------------------------------
-
-namespace {
-
 static_assert(CKZG_HIP_COSET_MAX_LOG2 == COSET_MAX_LOG, "the header and g1_fft_plan.hpp name the same largest coset");
 
+// Which openings a call asks for (dev::openings_enqueue): coset size 2^e, 2^out_log proofs per blob, and how many blobs
+// make a chunk.
+struct Openings {
+    int e, out_log;
+    uint64_t chunk;
+    uint64_t proofs_per_blob() const { return (uint64_t)1 << out_log; }
+};
+Openings domain_openings() { return {0, G1_FFT_MAX_LOG - 1, CKZG_HIP_DOMAIN_CHUNK_BLOBS}; }
+Openings coset_openings(int e) { return {e, G1_FFT_MAX_LOG - e, CKZG_HIP_COSET_CHUNK_BLOBS}; }
+
 // what a chunk of up to m blobs needs next to the blobs and the outputs themselves
-struct CosetBufs {
+struct OpeningsBufs {
     ABuf<uint32_t> bad;
     ABuf<uint8_t> scratch;
-    static size_t bytes(uint64_t m) { return m * sizeof(uint32_t) + dev::coset_proofs_scratch_bytes(m) + 2 * 256; }
-    CosetBufs(Arena &ar, uint64_t m) : bad(ar, m), scratch(ar, dev::coset_proofs_scratch_bytes(m)) {}
+    static size_t bytes(uint64_t m) { return m * sizeof(uint32_t) + dev::openings_scratch_bytes(m) + 2 * 256; }
+    OpeningsBufs(Arena &ar, uint64_t m) : bad(ar, m), scratch(ar, dev::openings_scratch_bytes(m)) {}
     bool ok() const { return bad.p && scratch.p; }
 };
 
-// one chunk of k <= CKZG_HIP_COSET_CHUNK_BLOBS blobs in HBM: enqueue-only, on the slot's compute stream; d_evals and
-// d_status may be null
-C_KZG_RET coset_proofs_chunk(dev::DeviceCtx *ctx, const CosetBufs &b, uint8_t *d_proofs48, uint8_t *d_evals, uint8_t *d_status,
-                             const uint8_t *d_blobs, uint64_t k, int e) {
+// one chunk of k <= o.chunk blobs in HBM: enqueue-only, on the slot's compute stream; d_evals and d_status may be null
+C_KZG_RET openings_chunk(dev::DeviceCtx *ctx, const Openings &o, const OpeningsBufs &b, uint8_t *d_proofs48, uint8_t *d_evals,
+                         uint8_t *d_status, const uint8_t *d_blobs, uint64_t k) {
     OKB(hipMemsetAsync(b.bad.p, 0, k * sizeof(uint32_t), ctx->stream) == hipSuccess);
-    RC(dev::coset_proofs_enqueue(ctx, d_proofs48, d_evals, b.bad.p, d_blobs, k, e, b.scratch.p));
+    RC(dev::openings_enqueue(ctx, d_proofs48, d_evals, b.bad.p, d_blobs, k, o.e, o.out_log, b.scratch.p));
     if (d_status) RC(dev::flags_to_status_enqueue(ctx, d_status, b.bad.p, k));
     return C_KZG_OK;
 }
 
 // One device's share of a host-pointer call: per chunk, blobs to HBM, the chunk, proofs | evaluations | statuses back
-C_KZG_RET coset_proofs_on(dev::DeviceCtx *ctx, KZGProof *proofs, Bytes32 *evals, uint8_t *status, const Blob *blobs, uint64_t n, int e) {
+C_KZG_RET openings_on(dev::DeviceCtx *ctx, const Openings &o, KZGProof *proofs, Bytes32 *evals, uint8_t *status, const Blob *blobs,
+                      uint64_t n) {
     if (n == 0) return C_KZG_OK;
-    const uint64_t CH = CKZG_HIP_COSET_CHUNK_BLOBS, np = coset_proofs_per_blob(e), per = np * 48;
+    const uint64_t CH = o.chunk, np = o.proofs_per_blob(), per = np * 48;
     const uint64_t per_ev = evals ? (uint64_t)FIELD_ELEMENTS_PER_EXT_BLOB * 32 : 0;
     const uint64_t m = domain_chunk_size(n, CH, 0);
-    RC(dev::coset_xhat_ensure(ctx, e));
+    RC(dev::openings_xhat_ensure(ctx, o.e));
     Arena &ar = ctx->api_arena;
-    OKM(ar.begin(m * (BYTES_PER_BLOB + per + per_ev + 1) + CosetBufs::bytes(m) + 2 * 256));
+    OKM(ar.begin(m * (BYTES_PER_BLOB + per + per_ev + 1) + OpeningsBufs::bytes(m) + 2 * 256));
     ArenaTrim trim(ar);
     ABuf<uint8_t> d_blobs(ar, m * BYTES_PER_BLOB), d_res(ar, m * (per + per_ev + 1));
-    CosetBufs b(ar, m);
+    OpeningsBufs b(ar, m);
     OKM(d_blobs.p && d_res.p && b.ok());
     StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the caller's buffers or the arena's reuse
     std::vector<uint8_t> st(m);
@@ -3404,7 +3313,7 @@ C_KZG_RET coset_proofs_on(dev::DeviceCtx *ctx, KZGProof *proofs, Bytes32 *evals,
         const uint64_t k = domain_chunk_size(n, CH, c);
         uint8_t *d_ev = d_res.p + k * per, *d_st = d_ev + k * per_ev;
         OKB(hipMemcpyAsync(d_blobs.p, blobs + off, k * BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-        RC(coset_proofs_chunk(ctx, b, d_res.p, evals ? d_ev : nullptr, d_st, d_blobs.p, k, e));
+        RC(openings_chunk(ctx, o, b, d_res.p, evals ? d_ev : nullptr, d_st, d_blobs.p, k));
         OKB(hipMemcpyAsync(proofs + off * np, d_res.p, k * per, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
         if (evals)
             OKB(hipMemcpyAsync(evals + off * FIELD_ELEMENTS_PER_EXT_BLOB, d_ev, k * per_ev, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
@@ -3419,7 +3328,62 @@ C_KZG_RET coset_proofs_on(dev::DeviceCtx *ctx, KZGProof *proofs, Bytes32 *evals,
     return ret;
 }
 
+// A device-pointer call once its arguments are checked (n > 0): the device that holds the pointers, then chunk by chunk
+// from and into the caller's memory; d_evals and d_status may be null
+C_KZG_RET openings_device(const KZGSettings *s, SettingsCtx *sc, const Openings &o, void *d_proofs, void *d_evals, void *d_status,
+                          const void *d_blobs, uint64_t n) {
+    const void *ptrs[4] = {d_proofs, d_evals, d_status, d_blobs};
+    const int pool = pool_of_pointers(sc, ptrs, 4);
+    if (pool < 0) return C_KZG_BADARGS;
+    Lease lease(s, pool);
+    dev::DeviceCtx *ctx = lease.ctx;
+    if (!ctx) return C_KZG_ERROR;
+    const uint64_t CH = o.chunk, per = o.proofs_per_blob() * 48;
+    const uint64_t per_ev = (uint64_t)FIELD_ELEMENTS_PER_EXT_BLOB * 32;
+    const uint64_t m = domain_chunk_size(n, CH, 0);
+    RC(dev::openings_xhat_ensure(ctx, o.e));
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(OpeningsBufs::bytes(m)));
+    ArenaTrim trim(ar);
+    OpeningsBufs b(ar, m);
+    OKM(b.ok());
+    StreamDrain drain{ctx->stream};
+    uint8_t *out = static_cast<uint8_t *>(d_proofs), *ev = static_cast<uint8_t *>(d_evals), *st = static_cast<uint8_t *>(d_status);
+    const uint8_t *bl = static_cast<const uint8_t *>(d_blobs);
+    for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
+        const uint64_t k = domain_chunk_size(n, CH, c);
+        RC(openings_chunk(ctx, o, b, out + off * per, ev ? ev + off * per_ev : nullptr, st ? st + off : nullptr,
+                          bl + off * BYTES_PER_BLOB, k));
+        off += k;
+    }
+    return C_KZG_OK;
+}
+
 }  // namespace
+
+extern "C" C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch(KZGProof *proofs, uint8_t *status, const Blob *blobs, uint64_t n,
+                                                             const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (n && (!proofs || !blobs)) return C_KZG_BADARGS;
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        const Openings o = domain_openings();
+        return for_each_device_shard(s, n, 1, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return openings_on(ctx, o, proofs + lo * o.proofs_per_blob(), nullptr, status ? status + lo : nullptr, blobs + lo, hi - lo);
+        });
+    });
+}
+
+extern "C" C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch_device(void *d_proofs, void *d_status, const void *d_blobs,
+                                                                    uint64_t n, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (n && (!d_proofs || !d_blobs)) return C_KZG_BADARGS;
+        SettingsCtx *sc = settings_of(s);
+        if (!sc) return C_KZG_ERROR;
+        if (n == 0) return C_KZG_OK;
+        return openings_device(s, sc, domain_openings(), d_proofs, nullptr, d_status, d_blobs, n);
+    });
+}
 
 extern "C" C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch(KZGProof *proofs, Bytes32 *evals, uint8_t *status, const Blob *blobs,
                                                             uint64_t n, uint32_t log2_coset, const KZGSettings *s) {
@@ -3427,11 +3391,10 @@ extern "C" C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch(KZGProof *proofs, B
         if (log2_coset > CKZG_HIP_COSET_MAX_LOG2 || (n && (!proofs || !blobs))) return C_KZG_BADARGS;
         if (!settings_of(s)) return C_KZG_ERROR;
         if (n == 0) return C_KZG_OK;
-        const int e = (int)log2_coset;
-        const uint64_t np = coset_proofs_per_blob(e);
+        const Openings o = coset_openings((int)log2_coset);
         return for_each_device_shard(s, n, 1, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
-            return coset_proofs_on(ctx, proofs + lo * np, evals ? evals + lo * FIELD_ELEMENTS_PER_EXT_BLOB : nullptr,
-                                   status ? status + lo : nullptr, blobs + lo, hi - lo, e);
+            return openings_on(ctx, o, proofs + lo * o.proofs_per_blob(), evals ? evals + lo * FIELD_ELEMENTS_PER_EXT_BLOB : nullptr,
+                               status ? status + lo : nullptr, blobs + lo, hi - lo);
         });
     });
 }
@@ -3443,31 +3406,6 @@ extern "C" C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proo
         SettingsCtx *sc = settings_of(s);
         if (!sc) return C_KZG_ERROR;
         if (n == 0) return C_KZG_OK;
-        const void *ptrs[4] = {d_proofs, d_evals, d_status, d_blobs};
-        const int pool = pool_of_pointers(sc, ptrs, 4);
-        if (pool < 0) return C_KZG_BADARGS;
-        Lease lease(s, pool);
-        dev::DeviceCtx *ctx = lease.ctx;
-        if (!ctx) return C_KZG_ERROR;
-        const int e = (int)log2_coset;
-        const uint64_t CH = CKZG_HIP_COSET_CHUNK_BLOBS, per = (uint64_t)coset_proofs_per_blob(e) * 48;
-        const uint64_t per_ev = (uint64_t)FIELD_ELEMENTS_PER_EXT_BLOB * 32;
-        const uint64_t m = domain_chunk_size(n, CH, 0);
-        RC(dev::coset_xhat_ensure(ctx, e));
-        Arena &ar = ctx->api_arena;
-        OKM(ar.begin(CosetBufs::bytes(m)));
-        ArenaTrim trim(ar);
-        CosetBufs b(ar, m);
-        OKM(b.ok());
-        StreamDrain drain{ctx->stream};
-        uint8_t *out = static_cast<uint8_t *>(d_proofs), *ev = static_cast<uint8_t *>(d_evals), *st = static_cast<uint8_t *>(d_status);
-        const uint8_t *bl = static_cast<const uint8_t *>(d_blobs);
-        for (uint64_t c = 0, off = 0; c < domain_chunk_count(n, CH); c++) {
-            const uint64_t k = domain_chunk_size(n, CH, c);
-            RC(coset_proofs_chunk(ctx, b, out + off * per, ev ? ev + off * per_ev : nullptr, st ? st + off : nullptr,
-                                  bl + off * BYTES_PER_BLOB, k, e));
-            off += k;
-        }
-        return C_KZG_OK;
+        return openings_device(s, sc, coset_openings((int)log2_coset), d_proofs, d_evals, d_status, d_blobs, n);
     });
 }

@@ -369,11 +369,12 @@ struct DeviceCtx {
     Fr *d_brp_roots = nullptr;    // 8192
     uint32_t *d_brp_roots29 = nullptr;   // the first 4096 of them as fr29.hpp's nine 29-bit limbs, then 1/brp_roots[2m], m < 2048
     uint32_t *d_roots_raw = nullptr;  // GLV halves {k1, k2} of w^(64 i), i <= 128 (twiddles of the G1 FFT)
-    // the general G1 transform and the openings at every domain point (g1_fft.hip), this slot's own: built by the
-    // first call on the slot that needs them, kept until the slot goes
+    // the general G1 transform and the openings (g1_fft.hip), this slot's own: built by the first call on the slot that
+    // needs them, kept until the slot goes
     uint32_t *d_g1_fft_roots = nullptr;   // GLV halves {k1[4], k2[4]} of w^i, i < 8192 (256 KB)
-    G1Affine *d_domain_xhat = nullptr;    // the G1 transform of the reversed monomial setup, DIF order, affine, 8192 (768 KB)
-    G1Affine *d_coset_xhat[7] = {};       // the same for coset size 2^e, e = 1 .. 6: 2^e columns of 8192 >> e ([0] unused: d_domain_xhat)
+    // [e]: the G1 transform of the reversed monomial setup for coset size 2^e, 2^e columns of 8192 >> e, DIF order,
+    // affine (768 KB each); [0] also serves the openings at every domain point
+    G1Affine *d_openings_xhat[7] = {};
     // FK20
     FixedBaseTable fk20;          // over x_ext_fft columns: point index = col*64 + row
     G1Affine *d_xext = nullptr;   // [128][64] affine
@@ -618,23 +619,19 @@ int g1_prefix_scan_enqueue(DeviceCtx *ctx, G1XYZZ *d_data, G1XYZZ *d_scratch, si
 uint64_t g1_fft_quad_max();
 size_t g1_fft_tmp_points(int logn, size_t count);
 int g1_fft_enqueue(DeviceCtx *ctx, G1XYZZ *d_data, G1XYZZ *d_tmp, int logn, size_t count, size_t stride, bool dif, int inverse);
-// The openings of k blobs at every point of the evaluation domain: d_proofs48[k][4096][48], proof j of a blob opens its
-// field element j.  domain_xhat_ensure builds the slot's transformed setup on first use (waits for it; a failure keeps
-// nothing); domain_proofs_enqueue is enqueue-only on ctx->stream, d_bad[k] zeroed by the caller on that stream.
-size_t domain_xhat_bytes();
-int domain_xhat_ensure(DeviceCtx *ctx);
-size_t domain_proofs_scratch_bytes(size_t k);
-int domain_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint32_t *d_bad, const uint8_t *d_blobs, size_t k, uint8_t *scratch);
-// The openings of k blobs on every coset of size 2^e (e <= 6) of the extended domain: d_proofs48[k][8192 >> e][48], and
-// if d_evals != nullptr the extended evaluations d_evals[k][8192][32] in cell order.  coset_xhat_ensure builds the
-// slot's transformed setup of that size on first use (waits for it; a failure keeps nothing; e = 0 is d_domain_xhat);
-// coset_proofs_enqueue is enqueue-only on ctx->stream, d_bad[k] zeroed by the caller on that stream.
+// The openings of k blobs, one pipeline.  out_log = 13 - e: on every coset of size 2^e (e <= 6) of the extended domain,
+// d_proofs48[k][8192 >> e][48].  e = 0 and out_log = 12: at every point of the evaluation domain, d_proofs48[k][4096][48],
+// proof j of a blob opens its field element j (the first 4096 proofs of coset size one, with a last transform of half
+// the length).  If d_evals != nullptr, also the extended evaluations d_evals[k][8192][32] in cell order.
+// openings_xhat_ensure builds the slot's transformed setup of that e on first use (waits for it; a failure keeps
+// nothing); openings_enqueue is enqueue-only on ctx->stream, d_bad[k] zeroed by the caller on that stream, `scratch` of
+// openings_scratch_bytes(k).
 // coset_colsum_enqueue: d_u[b][t] <- sum_{i < 2^e} d_u[b][i (8192 >> e) + t] on `rows` rows of 8192 points, in place.
-int coset_xhat_ensure(DeviceCtx *ctx, int e);
-size_t coset_proofs_scratch_bytes(size_t k);
+int openings_xhat_ensure(DeviceCtx *ctx, int e);
+size_t openings_scratch_bytes(size_t k);
 int coset_colsum_enqueue(DeviceCtx *ctx, G1XYZZ *d_u, int e, size_t rows);
-int coset_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint8_t *d_evals, uint32_t *d_bad, const uint8_t *d_blobs, size_t k,
-                         int e, uint8_t *scratch);
+int openings_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint8_t *d_evals, uint32_t *d_bad, const uint8_t *d_blobs, size_t k,
+                     int e, int out_log, uint8_t *scratch);
 // generic helpers
 int batch_to_affine_device(DeviceCtx *ctx, G1Affine *d_out, const G1XYZZ *d_in, Fp *d_prefix, size_t n);
 

@@ -193,8 +193,7 @@ static void destroy_slot(dev::DeviceCtx *ctx) {
     }
     if (ctx->cell_interp.d_table) (void)hipFree(ctx->cell_interp.d_table);   // (every slot's own, built on first use)
     if (ctx->d_g1_fft_roots) (void)hipFree(ctx->d_g1_fft_roots);             // (likewise: g1_fft.hip)
-    if (ctx->d_domain_xhat) (void)hipFree(ctx->d_domain_xhat);
-    for (G1Affine *p : ctx->d_coset_xhat) {
+    for (G1Affine *p : ctx->d_openings_xhat) {
         if (p) (void)hipFree(p);
     }
     if (ctx->scratch.ptr) (void)hipFree(ctx->scratch.ptr);

@@ -1,6 +1,7 @@
 // g1_fft.hip -- the G1 Fourier transform at any power of two up to 8192 (g1_fft / g1_ifft_unscaled,
-// src/eip7594/fft.c:164-240) and, on top of it, the openings of a blob at every point of the evaluation domain
-// (FK20 in its single-point form; src/eip7594/fk20.c with cell size 1, setup.c:238-330 for the transformed setup).
+// src/eip7594/fft.c:164-240) and, on top of it, one FK20 pipeline for the openings of a blob on every coset of 1 to 64
+// points of the extended domain and at every point of the evaluation domain (src/eip7594/fk20.c at those cell sizes,
+// setup.c:238-330 for the transformed setup).
 //
 // fk20.hip's transforms are hard-wired to length 128 and order their lanes transform-fastest, so that a wave holds ONE
 // twiddle and the digit-driven NAF ladder stays uniform.  One transform of length 8192 has no such order: in the stages
@@ -182,172 +183,16 @@ int g1_fft_enqueue(DeviceCtx *ctx, G1XYZZ *d_data, G1XYZZ *d_tmp, int logn, size
 }
 
 // ------------------------------------------------------------------------------------------
-// Openings at every domain point: pi(w^k) = sum_m [w^(km)] h_m, h = the Toeplitz product of the coefficients with the
-// setup, through a circulant of length 8192.  Nothing is permuted: the scalar transform and the setup transform are
-// both DIF (bit-reversed out), their pointwise product feeds a DIT inverse (natural out), whose first 4096 entries
-// feed a DIF forward transform -- position j of its output is pi(w^brp12(j)), the proof of blob element j.
-// ------------------------------------------------------------------------------------------
-
-// xin[t] = g1_values_monomial[4094 - t] for t <= 4094, infinity above (setup.c:238-330 at cell size 1)
-__global__ void k_domain_xext_gather(G1XYZZ *xin, const G1Affine *monomial) {
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (uint32_t)N_EXT) return;
-    xin[t] = t <= (uint32_t)N_BLOB - 2u ? xyzz_from_affine(monomial[N_BLOB - 2 - t]) : G1XYZZ::inf();
-}
-
-// v[b][t]: the circulant vector of blob b from its monomial coefficients (g1_fft_plan.hpp: domain_circulant_source)
-__global__ void k_domain_circulant(Fr *v, const Fr *poly, size_t total) {
-    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    const size_t b = g >> 13;
-    const int src = domain_circulant_source((uint32_t)g & (uint32_t)(N_EXT - 1), (uint32_t)N_BLOB);
-    const uint4 *q = reinterpret_cast<const uint4 *>(poly + b * N_BLOB + (src < 0 ? 0 : src));
-    uint4 lo = q[0], hi = q[1];
-    if (src < 0) lo = hi = make_uint4(0, 0, 0, 0);
-    uint4 *o = reinterpret_cast<uint4 *>(v + g);
-    o[0] = lo;
-    o[1] = hi;
-}
-
-// glv[g] = the GLV halves of the canonical value of vhat[g] (Montgomery)
-__global__ __launch_bounds__(64) void k_domain_scalars(uint32_t *glv, const Fr *vhat, size_t total) {
-    const size_t g = blockIdx.x * (size_t)64 + threadIdx.x;
-    if (g >= total) return;
-    uint32_t raw[8];
-    to_raw<FrParams>(raw, ld_fr(vhat + g));
-    glv_split(raw, glv + g * 8, glv + g * 8 + 4);
-}
-
-// tmp[2 g + h] = half-product h of xhat[g mod 8192] with the scalar glv[g]
-template <bool QUAD>
-__global__ __launch_bounds__(64) void k_domain_ladder(
-    G1XYZZ *tmp, const G1Affine *xhat, const uint32_t *glv, size_t total) {
-    size_t item;
-    int ql;
-    const bool store = ladder_item<QUAD>(total, item, ql);
-    const size_t g = item >> 1;
-    const bool second = (item & 1) != 0;
-    const G1Affine a = xhat[g & (size_t)(N_EXT - 1)];
-    XYZZ28 p;
-    p.x = widen<1, 10>(f28_from_fp(a.x));
-    p.y = widen<1, 6>(f28_from_fp(a.y));
-    p.zz = widen<1, 2>(f28_one());
-    p.zzz = p.zz;
-    const G1XYZZ r = half_product<QUAD>(p, a.is_inf(), glv + g * 8 + (second ? 4 : 0), second, ql);
-    if (store) tmp[item] = r;
-}
-
-// u[g] = tmp[2 g] + tmp[2 g + 1]
-__global__ __launch_bounds__(64) void k_domain_sum(G1XYZZ *u, const G1XYZZ *tmp, size_t total) {
-    const size_t g = blockIdx.x * (size_t)64 + threadIdx.x;
-    if (g >= total) return;
-    bool ai, bi;
-    XYZZ28 a = xyzz28_from_xyzz(tmp[2 * g], ai), b = xyzz28_from_xyzz(tmp[2 * g + 1], bi);
-    xyzz28_add(a, ai, b, bi);
-    u[g] = xyzz28_to_xyzz(a, ai);
-}
-
-// out48[b][j] = compress(aff[b][j]), j < 4096, from rows of 8192
-__global__ void k_domain_compress(uint8_t *out48, const G1Affine *aff, size_t total) {
-    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (g >= total) return;
-    uint8_t buf[48];
-    g1_compress_affine(buf, aff[g]);
-    for (int k = 0; k < 48; k++) out48[g * 48 + k] = buf[k];
-}
-
-size_t domain_xhat_bytes() { return (size_t)N_EXT * sizeof(G1Affine); }
-
-// The transformed setup, this slot's own: built by its first call, kept until the slot goes.  A failure keeps nothing.
-int domain_xhat_ensure(DeviceCtx *ctx) {
-    if (ctx->d_domain_xhat) return 0;
-    int rc = g1_fft_roots_ensure(ctx);
-    if (rc) return rc;
-    DevTmp xin, tmp, prefix, out;   // gone on every exit path
-    HIP_TRY(hipMalloc(&xin.p, (size_t)N_EXT * sizeof(G1XYZZ)));
-    HIP_TRY(hipMalloc(&tmp.p, g1_fft_tmp_points(G1_FFT_MAX_LOG, 1) * sizeof(G1XYZZ)));
-    HIP_TRY(hipMalloc(&prefix.p, (size_t)N_EXT * sizeof(Fp)));
-    HIP_TRY(hipMalloc(&out.p, domain_xhat_bytes()));
-    G1XYZZ *d_xin = static_cast<G1XYZZ *>(xin.p);
-    hipLaunchKernelGGL(k_domain_xext_gather, dim3(N_EXT / 256), dim3(256), 0, ctx->stream, d_xin, ctx->d_mono);
-    rc = g1_fft_enqueue(ctx, d_xin, static_cast<G1XYZZ *>(tmp.p), G1_FFT_MAX_LOG, 1, N_EXT, /*dif=*/true, /*inverse=*/0);
-    if (!rc) rc = batch_to_affine_device(ctx, static_cast<G1Affine *>(out.p), d_xin, static_cast<Fp *>(prefix.p), N_EXT);
-    // the scratch is freed when this function returns: nothing may still be running on it, error or not
-    if (dev::sync_stream(ctx->stream) != hipSuccess && !rc) rc = 2;
-    if (rc) return rc;
-    ctx->d_domain_xhat = static_cast<G1Affine *>(out.p);
-    out.p = nullptr;
-    return 0;
-}
-
-static size_t al256(size_t v) { return (v + 255) / 256 * 256; }
-
-size_t domain_proofs_scratch_bytes(size_t k) {
-    return al256(k * N_BLOB * sizeof(Fr)) + al256(k * N_EXT * sizeof(Fr)) + al256(k * N_EXT * 8 * sizeof(uint32_t)) +
-           al256(k * N_EXT * sizeof(G1XYZZ)) + al256(2 * k * N_EXT * sizeof(G1XYZZ)) + al256(k * N_BLOB * sizeof(G1Affine)) +
-           al256(k * N_BLOB * sizeof(Fp));
-}
-
-// d_blobs[k] (bytes) -> d_proofs48[k][4096]; d_bad[k] (zeroed by the caller on the stream) |= 1 for a blob with a
-// non-canonical element.  Enqueue-only, on ctx->stream; `scratch` holds domain_proofs_scratch_bytes(k).
-int domain_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint32_t *d_bad, const uint8_t *d_blobs, size_t k, uint8_t *scratch) {
-    if (k == 0) return 0;
-    if (!ctx->d_domain_xhat || k > ((size_t)1 << 17)) return 2;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        uint8_t *p = scratch + off;
-        off += al256(bytes);
-        return p;
-    };
-    Fr *poly = reinterpret_cast<Fr *>(take(k * N_BLOB * sizeof(Fr)));
-    Fr *v = reinterpret_cast<Fr *>(take(k * N_EXT * sizeof(Fr)));
-    uint32_t *glv = reinterpret_cast<uint32_t *>(take(k * N_EXT * 8 * sizeof(uint32_t)));
-    G1XYZZ *u = reinterpret_cast<G1XYZZ *>(take(k * N_EXT * sizeof(G1XYZZ)));
-    G1XYZZ *tmp = reinterpret_cast<G1XYZZ *>(take(2 * k * N_EXT * sizeof(G1XYZZ)));
-    G1Affine *aff = reinterpret_cast<G1Affine *>(take(k * N_BLOB * sizeof(G1Affine)));
-    Fp *prefix = reinterpret_cast<Fp *>(take(k * N_BLOB * sizeof(Fp)));
-    // monomial coefficients (poly_lagrange_to_monomial, poly.c:58-80), the circulant vector, its transform / 8192
-    int rc = cells_stage_enqueue(ctx, nullptr, poly, nullptr, d_bad, d_blobs, k);
-    if (rc) return rc;
-    const size_t total = k * N_EXT;
-    hipLaunchKernelGGL(k_domain_circulant, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, v, poly, total);
-    HIP_TRY(hipGetLastError());
-    rc = fr_ntt_batch(ctx, v, k, G1_FFT_MAX_LOG, /*dif=*/true, /*inverse=*/false, /*scale=*/true);
-    if (rc) return rc;
-    // u = vhat (.) xhat, both in the DIF output order
-    hipLaunchKernelGGL(k_domain_scalars, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, glv, v, total);
-    launch_ladders(total, [&](bool quad, dim3 grid, size_t items) {
-        if (quad)
-            hipLaunchKernelGGL(k_domain_ladder<true>, grid, dim3(64), 0, ctx->stream, tmp, ctx->d_domain_xhat, glv, items);
-        else
-            hipLaunchKernelGGL(k_domain_ladder<false>, grid, dim3(64), 0, ctx->stream, tmp, ctx->d_domain_xhat, glv, items);
-    });
-    hipLaunchKernelGGL(k_domain_sum, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, u, tmp, total);
-    HIP_TRY(hipGetLastError());
-    // h = the first 4096 entries of the unscaled inverse transform; proofs = the forward transform of h, in place in
-    // the rows of 8192
-    rc = g1_fft_enqueue(ctx, u, tmp, G1_FFT_MAX_LOG, k, N_EXT, /*dif=*/false, /*inverse=*/1);
-    if (rc) return rc;
-    rc = g1_fft_enqueue(ctx, u, tmp, G1_FFT_MAX_LOG - 1, k, N_EXT, /*dif=*/true, /*inverse=*/0);
-    if (rc) return rc;
-    // the low halves of the rows, contiguous (tmp is free again), normalised and compressed
-    HIP_TRY(hipMemcpy2DAsync(tmp, (size_t)N_BLOB * sizeof(G1XYZZ), u, (size_t)N_EXT * sizeof(G1XYZZ), (size_t)N_BLOB * sizeof(G1XYZZ), k,
-                             hipMemcpyDeviceToDevice, ctx->stream));
-    rc = batch_to_affine_device(ctx, aff, tmp, prefix, k * N_BLOB);
-    if (rc) return rc;
-    const size_t nout = k * N_BLOB;
-    hipLaunchKernelGGL(k_domain_compress, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, d_proofs48, aff, nout);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Openings on every coset of the extended domain, coset size l = 2^e (FK20 as in src/eip7594/fk20.c, at any cell size
-// up to 64).  k = 4096 / l; the l Toeplitz columns of length 2k fill one row of 8192 column-major, for the scalars, the
-// transformed setup and the products alike, so the scalar transform, the ladders and the sum of the GLV halves are
-// those of the single-point form.  Then the columns are added, and the row's first 2k entries go through the inverse
-// transform (DIT, natural out), lose their upper half and go through the forward transform (DIF): position c of its
-// output is the proof of coset c of the bit-reversed domain.  e = 0 is the single-point form on all 8192 points.
+// FK20 openings on every coset of size l = 2^e, e <= 6 (src/eip7594/fk20.c at any cell size up to 64; setup.c:238-330
+// for the transformed setup).  k = 4096 / l; the l Toeplitz columns of length 2k fill one row of 8192 column-major, for
+// the scalars, the transformed setup and the products alike, so the scalar transform, the ladders and the sum of the
+// GLV halves have one shape whatever e is.  Then the columns are added and the row's first 2k entries go through the
+// inverse transform, whose first k entries are h, the Toeplitz product of the coefficients with the setup.  Nothing is
+// permuted: the scalar transform and the setup transform are both DIF (bit-reversed out), their pointwise product
+// feeds the DIT inverse (natural out), and h feeds a DIF forward transform.  Which one is the caller's choice:
+//   of (h, 0) at length 2k: position c of the output is the proof of coset c of the bit-reversed extended domain;
+//   at e = 0 also of h alone at length 4096: pi(w^brp12(j)), the proof of blob element j.  These are the first 4096
+//   outputs of the length-8192 transform -- its first DIF stage leaves h in the lower half -- at half its cost.
 // ------------------------------------------------------------------------------------------
 
 // xin[t] = g1_values_monomial[coset_setup_source(t)], the identity where that is -1 (g1_fft_plan.hpp)
@@ -370,6 +215,53 @@ __global__ void k_coset_circulant(Fr *v, const Fr *poly, size_t total, int e) {
     uint4 *o = reinterpret_cast<uint4 *>(v + g);
     o[0] = lo;
     o[1] = hi;
+}
+
+// glv[g] = the GLV halves of the canonical value of vhat[g] (Montgomery)
+__global__ __launch_bounds__(64) void k_openings_scalars(uint32_t *glv, const Fr *vhat, size_t total) {
+    const size_t g = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (g >= total) return;
+    uint32_t raw[8];
+    to_raw<FrParams>(raw, ld_fr(vhat + g));
+    glv_split(raw, glv + g * 8, glv + g * 8 + 4);
+}
+
+// tmp[2 g + h] = half-product h of xhat[g mod 8192] with the scalar glv[g]
+template <bool QUAD>
+__global__ __launch_bounds__(64) void k_openings_ladder(
+    G1XYZZ *tmp, const G1Affine *xhat, const uint32_t *glv, size_t total) {
+    size_t item;
+    int ql;
+    const bool store = ladder_item<QUAD>(total, item, ql);
+    const size_t g = item >> 1;
+    const bool second = (item & 1) != 0;
+    const G1Affine a = xhat[g & (size_t)(N_EXT - 1)];
+    XYZZ28 p;
+    p.x = widen<1, 10>(f28_from_fp(a.x));
+    p.y = widen<1, 6>(f28_from_fp(a.y));
+    p.zz = widen<1, 2>(f28_one());
+    p.zzz = p.zz;
+    const G1XYZZ r = half_product<QUAD>(p, a.is_inf(), glv + g * 8 + (second ? 4 : 0), second, ql);
+    if (store) tmp[item] = r;
+}
+
+// u[g] = tmp[2 g] + tmp[2 g + 1]
+__global__ __launch_bounds__(64) void k_openings_sum(G1XYZZ *u, const G1XYZZ *tmp, size_t total) {
+    const size_t g = blockIdx.x * (size_t)64 + threadIdx.x;
+    if (g >= total) return;
+    bool ai, bi;
+    XYZZ28 a = xyzz28_from_xyzz(tmp[2 * g], ai), b = xyzz28_from_xyzz(tmp[2 * g + 1], bi);
+    xyzz28_add(a, ai, b, bi);
+    u[g] = xyzz28_to_xyzz(a, ai);
+}
+
+// out48[g] = compress(aff[g])
+__global__ void k_openings_compress(uint8_t *out48, const G1Affine *aff, size_t total) {
+    const size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    uint8_t buf[48];
+    g1_compress_affine(buf, aff[g]);
+    for (int k = 0; k < 48; k++) out48[g * 48 + k] = buf[k];
 }
 
 // Column sum, one strided pass: a row of 8192 points holds columns of 2^logw points; column `part` of row b <- the sum
@@ -421,11 +313,10 @@ int coset_colsum_enqueue(DeviceCtx *ctx, G1XYZZ *d_u, int e, size_t rows) {
 
 // The transformed setup of coset size 2^e, this slot's own: the l columns, each through the forward transform of length
 // 2k, affine, DIF order.  Built by the slot's first call with that e, kept until the slot goes; a failure keeps
-// nothing.  e = 0 is the single-point form's (d_domain_xhat), shared.
-int coset_xhat_ensure(DeviceCtx *ctx, int e) {
+// nothing.
+int openings_xhat_ensure(DeviceCtx *ctx, int e) {
     if (e < 0 || e > COSET_MAX_LOG) return 2;
-    if (e == 0) return domain_xhat_ensure(ctx);
-    if (ctx->d_coset_xhat[e]) return 0;
+    if (ctx->d_openings_xhat[e]) return 0;
     int rc = g1_fft_roots_ensure(ctx);
     if (rc) return rc;
     const int logn = G1_FFT_MAX_LOG - e;
@@ -434,7 +325,7 @@ int coset_xhat_ensure(DeviceCtx *ctx, int e) {
     HIP_TRY(hipMalloc(&xin.p, (size_t)N_EXT * sizeof(G1XYZZ)));
     HIP_TRY(hipMalloc(&tmp.p, g1_fft_tmp_points(logn, l) * sizeof(G1XYZZ)));
     HIP_TRY(hipMalloc(&prefix.p, (size_t)N_EXT * sizeof(Fp)));
-    HIP_TRY(hipMalloc(&out.p, domain_xhat_bytes()));
+    HIP_TRY(hipMalloc(&out.p, (size_t)N_EXT * sizeof(G1Affine)));
     G1XYZZ *d_xin = static_cast<G1XYZZ *>(xin.p);
     hipLaunchKernelGGL(k_coset_xext_gather, dim3(N_EXT / 256), dim3(256), 0, ctx->stream, d_xin, ctx->d_mono, e);
     rc = g1_fft_enqueue(ctx, d_xin, static_cast<G1XYZZ *>(tmp.p), logn, l, (size_t)1 << logn, /*dif=*/true, /*inverse=*/0);
@@ -442,23 +333,32 @@ int coset_xhat_ensure(DeviceCtx *ctx, int e) {
     // the scratch is freed when this function returns: nothing may still be running on it, error or not
     if (dev::sync_stream(ctx->stream) != hipSuccess && !rc) rc = 2;
     if (rc) return rc;
-    ctx->d_coset_xhat[e] = static_cast<G1Affine *>(out.p);
+    ctx->d_openings_xhat[e] = static_cast<G1Affine *>(out.p);
     out.p = nullptr;
     return 0;
 }
 
-// the scratch of the single-point form serves every coset size: the affine points and the inversion prefixes of the
-// output (up to 8192 per blob at e = 0) lie on the rows of u once these have been gathered
-size_t coset_proofs_scratch_bytes(size_t k) { return domain_proofs_scratch_bytes(k); }
+static size_t al256(size_t v) { return (v + 255) / 256 * 256; }
 
-// d_blobs[k] (bytes) -> d_proofs48[k][8192 >> e] and, if d_evals != nullptr, d_evals[k][8192][32], the extended
+// the coefficients, the scalars and their GLV halves, the rows u and the ladders' halves; the affine points and the
+// inversion prefixes of the output (up to 8192 per blob) lie on the rows of u once these have been gathered
+size_t openings_scratch_bytes(size_t k) {
+    return al256(k * N_BLOB * sizeof(Fr)) + al256(k * N_EXT * sizeof(Fr)) + al256(k * N_EXT * 8 * sizeof(uint32_t)) +
+           al256(k * N_EXT * sizeof(G1XYZZ)) + al256(2 * k * N_EXT * sizeof(G1XYZZ));
+}
+
+// d_blobs[k] (bytes) -> d_proofs48[k][2^out_log] and, if d_evals != nullptr, d_evals[k][8192][32], the extended
 // evaluations in cell order; d_bad[k] (zeroed by the caller on the stream) |= 1 for a blob with a non-canonical element.
-// Enqueue-only, on ctx->stream; `scratch` holds coset_proofs_scratch_bytes(k).
-int coset_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint8_t *d_evals, uint32_t *d_bad, const uint8_t *d_blobs, size_t k,
-                         int e, uint8_t *scratch) {
+// out_log is the log length of the last forward transform: 13 - e, on (h, 0), for the proofs of every coset; at e = 0
+// also 12, on h alone, for those of the evaluation domain.  Enqueue-only, on ctx->stream; `scratch` holds
+// openings_scratch_bytes(k).
+int openings_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint8_t *d_evals, uint32_t *d_bad, const uint8_t *d_blobs, size_t k,
+                     int e, int out_log, uint8_t *scratch) {
     if (k == 0) return 0;
     if (e < 0 || e > COSET_MAX_LOG || k > ((size_t)1 << 17)) return 2;
-    const G1Affine *xhat = e == 0 ? ctx->d_domain_xhat : ctx->d_coset_xhat[e];
+    const int logn = G1_FFT_MAX_LOG - e;
+    if (out_log != logn && !(e == 0 && out_log == logn - 1)) return 2;
+    const G1Affine *xhat = ctx->d_openings_xhat[e];
     if (!xhat) return 2;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -471,8 +371,7 @@ int coset_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint8_t *d_evals, 
     uint32_t *glv = reinterpret_cast<uint32_t *>(take(k * N_EXT * 8 * sizeof(uint32_t)));
     G1XYZZ *u = reinterpret_cast<G1XYZZ *>(take(k * N_EXT * sizeof(G1XYZZ)));
     G1XYZZ *tmp = reinterpret_cast<G1XYZZ *>(take(2 * k * N_EXT * sizeof(G1XYZZ)));
-    const int logn = G1_FFT_MAX_LOG - e;
-    const size_t m = coset_proofs_per_blob(e), nout = k * m;
+    const size_t m = (size_t)1 << out_log, nout = k * m;
     // the output's affine points and prefixes: on u, once its rows have been gathered into tmp
     G1Affine *aff = reinterpret_cast<G1Affine *>(u);
     Fp *prefix = reinterpret_cast<Fp *>(reinterpret_cast<uint8_t *>(u) + al256(nout * sizeof(G1Affine)));
@@ -487,30 +386,31 @@ int coset_proofs_enqueue(DeviceCtx *ctx, uint8_t *d_proofs48, uint8_t *d_evals, 
     rc = fr_ntt_batch(ctx, v, k << e, logn, /*dif=*/true, /*inverse=*/false, /*scale=*/true);
     if (rc) return rc;
     // product[i][t] = vhat_i[t] xhat_i[t], both in the DIF output order; u[t] = their sum over the columns
-    hipLaunchKernelGGL(k_domain_scalars, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, glv, v, total);
+    hipLaunchKernelGGL(k_openings_scalars, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, glv, v, total);
     launch_ladders(total, [&](bool quad, dim3 grid, size_t items) {
         if (quad)
-            hipLaunchKernelGGL(k_domain_ladder<true>, grid, dim3(64), 0, ctx->stream, tmp, xhat, glv, items);
+            hipLaunchKernelGGL(k_openings_ladder<true>, grid, dim3(64), 0, ctx->stream, tmp, xhat, glv, items);
         else
-            hipLaunchKernelGGL(k_domain_ladder<false>, grid, dim3(64), 0, ctx->stream, tmp, xhat, glv, items);
+            hipLaunchKernelGGL(k_openings_ladder<false>, grid, dim3(64), 0, ctx->stream, tmp, xhat, glv, items);
     });
-    hipLaunchKernelGGL(k_domain_sum, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, u, tmp, total);
+    hipLaunchKernelGGL(k_openings_sum, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, ctx->stream, u, tmp, total);
     HIP_TRY(hipGetLastError());
     rc = coset_colsum_enqueue(ctx, u, e, k);
     if (rc) return rc;
-    // h = the first k entries of the unscaled inverse transform; proofs = the forward transform of (h, 0), in place in
-    // the first 2k entries of the rows
+    // h = the first half of the unscaled inverse transform of length 2^logn; proofs = the forward transform of (h, 0) at
+    // that length, or of h alone at half of it, which never reads the upper half; in place in the heads of the rows
     rc = g1_fft_enqueue(ctx, u, tmp, logn, k, N_EXT, /*dif=*/false, /*inverse=*/1);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_coset_zero_upper, dim3((unsigned)((nout / 2 + 255) / 256)), dim3(256), 0, ctx->stream, u, logn, nout / 2);
-    rc = g1_fft_enqueue(ctx, u, tmp, logn, k, N_EXT, /*dif=*/true, /*inverse=*/0);
+    if (out_log == logn)
+        hipLaunchKernelGGL(k_coset_zero_upper, dim3((unsigned)((nout / 2 + 255) / 256)), dim3(256), 0, ctx->stream, u, logn, nout / 2);
+    rc = g1_fft_enqueue(ctx, u, tmp, out_log, k, N_EXT, /*dif=*/true, /*inverse=*/0);
     if (rc) return rc;
     // the heads of the rows, contiguous (tmp is free again), normalised and compressed
     HIP_TRY(hipMemcpy2DAsync(tmp, m * sizeof(G1XYZZ), u, (size_t)N_EXT * sizeof(G1XYZZ), m * sizeof(G1XYZZ), k,
                              hipMemcpyDeviceToDevice, ctx->stream));
     rc = batch_to_affine_device(ctx, aff, tmp, prefix, nout);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_domain_compress, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, d_proofs48, aff, nout);
+    hipLaunchKernelGGL(k_openings_compress, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, ctx->stream, d_proofs48, aff, nout);
     HIP_TRY(hipGetLastError());
     return 0;
 }

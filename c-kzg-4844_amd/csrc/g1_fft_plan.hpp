@@ -1,8 +1,9 @@
-// g1_fft_plan.hpp -- the host decisions of the general G1 transform (g1_fft.hip; ckzg_hip_g1_fft) and of the
-// openings at every domain point (ckzg_hip_compute_domain_kzg_proofs_batch) and on every coset of the extended domain
-// (ckzg_hip_compute_coset_kzg_proofs_batch): the index maps of a stage, which ladder form runs at which size, how a
-// batch is cut into chunks, where a Toeplitz column reads its coefficients and its setup points.  Pure functions of
-// their arguments, so that the CPU tests reach them through libhost_shim.so and the kernels use the same maps (HD).
+// g1_fft_plan.hpp -- the host decisions of the general G1 transform (g1_fft.hip; ckzg_hip_g1_fft) and of the one
+// openings pipeline behind ckzg_hip_compute_coset_kzg_proofs_batch (every coset of the extended domain) and
+// ckzg_hip_compute_domain_kzg_proofs_batch (every domain point: coset size one with a shorter last transform): the
+// index maps of a stage, which ladder form runs at which size, how a batch is cut into chunks, where a Toeplitz column
+// reads its coefficients and its setup points.  Pure functions of their arguments, so that the CPU tests reach them
+// through libhost_shim.so and the kernels use the same maps (HD).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -54,23 +55,17 @@ inline uint64_t domain_chunk_size(uint64_t n, uint64_t chunk, uint64_t c) {
     return n - lo < chunk ? n - lo : chunk;
 }
 
-// The circulant vector of the single-point FK20 (N = 4096 coefficients c, length 2N): v[0] = c[N-1], v[1 .. N+1] = 0,
-// v[N+2+j] = c[1+j] for j = 0 .. N-3.  Returns the coefficient index that slot t reads, or -1 for a zero slot.
-HD int domain_circulant_source(uint32_t t, uint32_t N) {
-    if (t == 0) return (int)N - 1;
-    if (t >= N + 2u) return (int)(t - (N + 1u));
-    return -1;
-}
-
-// ---- openings on every coset of the extended domain (ckzg_hip_compute_coset_kzg_proofs_batch) ----
+// ---- the openings (ckzg_hip_compute_coset_kzg_proofs_batch, ckzg_hip_compute_domain_kzg_proofs_batch) ----
 // Coset size l = 2^e, e <= COSET_MAX_LOG; k = 4096 / l rows; l Toeplitz columns of length 2k = 8192 / l, which fill one
-// row of 8192 column-major: slot t of a row is position t mod 2k of column t / 2k.  m = 2k proofs per blob.
+// row of 8192 column-major: slot t of a row is position t mod 2k of column t / 2k.  m = 2k proofs per blob on the
+// cosets; the domain call is e = 0 and keeps the 4096 proofs of the evaluation domain.
 constexpr int COSET_MAX_LOG = 6;
 HD uint32_t coset_proofs_per_blob(int e) { return 8192u >> e; }
 
 // Column i of the circulant (toeplitz_coeffs_stride(p, i, l), src/eip7594/fk20.c): v_i[0] = p[4095 - i],
 // v_i[1 .. k+1] = 0, v_i[k+2+j] = p[2l - i - 1 + j l].  Returns the coefficient index that slot t of the row reads, or
-// -1 for a zero slot.  N = 4096 in the product; the tests also run smaller N.
+// -1 for a zero slot.  N = 4096 in the product; the tests also run smaller N.  At e = 0 (one column of length 2N):
+// v[0] = p[N-1], v[1 .. N+1] = 0, v[N+2+j] = p[1+j] for j = 0 .. N-3.
 HD int coset_circulant_source(uint32_t t, int e, uint32_t N) {
     const uint32_t l = 1u << e, k = N >> e, i = t / (2u * k), pos = t - i * 2u * k;
     if (pos == 0) return (int)(N - 1u - i);
@@ -80,6 +75,7 @@ HD int coset_circulant_source(uint32_t t, int e, uint32_t N) {
 
 // The setup vector of column i before its transform: X_i[j] = g1_values_monomial[N - l - 1 - i - j l] for j < k - 1,
 // the identity above (setup.c:238-330).  Returns the monomial index that slot t of the row reads, or -1 for the identity.
+// At e = 0: N - 2 - t for t <= N - 2.
 HD int coset_setup_source(uint32_t t, int e, uint32_t N) {
     const uint32_t l = 1u << e, k = N >> e, i = t / (2u * k), j = t - i * 2u * k;
     if (j + 1u >= k) return -1;

@@ -1051,9 +1051,8 @@ extern "C" int hs_g1_fft_form_at(int logn, uint64_t count, uint64_t quad_max) { 
 extern "C" uint64_t hs_g1_fft_quad_max_default() { return G1_FFT_QUAD_MAX_DEFAULT; }
 extern "C" uint64_t hs_domain_chunk_count(uint64_t n, uint64_t chunk) { return domain_chunk_count(n, chunk); }
 extern "C" uint64_t hs_domain_chunk_size(uint64_t n, uint64_t chunk, uint64_t c) { return domain_chunk_size(n, chunk, c); }
-extern "C" int hs_domain_circulant_source(uint32_t t, uint32_t n) { return domain_circulant_source(t, n); }
 
-// ---- the openings on every coset of the extended domain (tests/test_coset_openings_cpu.py) ----
+// ---- the maps of the openings, every coset size (tests/test_coset_openings_cpu.py, tests/test_domain_openings_cpu.py) ----
 extern "C" int hs_coset_max_log() { return COSET_MAX_LOG; }
 extern "C" uint32_t hs_coset_proofs_per_blob(int e) { return coset_proofs_per_blob(e); }
 extern "C" int hs_coset_circulant_source(uint32_t t, int e, uint32_t n) { return coset_circulant_source(t, e, n); }

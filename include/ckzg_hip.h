@@ -446,9 +446,10 @@ C_KZG_RET ckzg_hip_g1_fft(g1_t *out, const g1_t *in, uint64_t n, uint64_t count,
  * other blobs are still computed and the call returns C_KZG_BADARGS.  status may be NULL; n == 0 returns C_KZG_OK;
  * NULL proofs or blobs with n > 0 give C_KZG_BADARGS; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  With
  * several devices contiguous runs of blobs go to each; on a device the blobs go in chunks of at most
- * CKZG_HIP_DOMAIN_CHUNK_BLOBS (about 6.3 MB of HBM per blob of a chunk).  The transformed setup (8192 affine points,
- * 768 KB) is built by the first call on a stream slot and kept until free_trusted_setup; if it cannot be allocated the
- * call returns C_KZG_MALLOC, keeps nothing, and the next call builds it. */
+ * CKZG_HIP_DOMAIN_CHUNK_BLOBS (about 5.7 MB of HBM per blob of a chunk: 5.4 MB of scratch, the blob and its proofs).
+ * The transformed setup (8192 affine points, 768 KB; that of coset size one below, shared with it) is built by the
+ * first call on a stream slot and kept until free_trusted_setup; if it cannot be allocated the call returns
+ * C_KZG_MALLOC, keeps nothing, and the next call builds it. */
 #define CKZG_HIP_DOMAIN_CHUNK_BLOBS 16
 C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch(KZGProof *proofs, uint8_t *status, const Blob *blobs, uint64_t n,
                                                    const KZGSettings *s);
@@ -477,8 +478,9 @@ C_KZG_RET ckzg_hip_compute_domain_kzg_proofs_batch_device(void *d_proofs, void *
  * C_KZG_BADARGS.  status and evals may be NULL; n == 0 returns C_KZG_OK; NULL proofs or blobs with n > 0, or e > 6,
  * give C_KZG_BADARGS with nothing written and nothing launched; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.
  * With several devices contiguous runs of blobs go to each; on a device the blobs go in chunks of at most
- * CKZG_HIP_COSET_CHUNK_BLOBS, with the scratch of the domain call (about 6.3 MB of HBM per blob of a chunk).
- * The same algorithm at every size (FK20): 8192 one-term products per blob whatever e is, a sum over the l columns, an
+ * CKZG_HIP_COSET_CHUNK_BLOBS, with the scratch of the domain call (5.4 MB of HBM per blob of a chunk; with the blob
+ * and the outputs 5.5 MB at e = 6 without evals, 6.2 MB at e = 0 with them).
+ * The same algorithm at every size (FK20; the domain call runs it at e = 0 with a last transform of 4096): 8192 one-term products per blob whatever e is, a sum over the l columns, an
  * inverse and a forward G1 transform of length m.  The transformed setup of a size (8192 affine points, 768 KB) is
  * built by the first call with that e on a stream slot and kept until free_trusted_setup (e = 0 shares the domain
  * call's); a failed build keeps nothing and the next call builds it.  Load time and ckzg_hip_table_bytes do not change.

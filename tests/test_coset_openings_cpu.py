@@ -48,9 +48,9 @@ def test_circulant_source_matches_the_model(shim, e):
         assert [p[s] if s >= 0 else 0 for s in got] == flat
         assert got == [E.circulant_source(t, e, N) for t in range(2 * N)]
         assert sorted(s for s in got if s >= 0) == list(range(1 << e, N))
-    if e == 0:
+    if e == 0:   # the single-point form's vector: v[0] = c[N-1], v[1 .. N+1] = 0, v[N+2+j] = c[1+j] for j = 0 .. N-3
         assert [shim.hs_coset_circulant_source(C.c_uint32(t), 0, C.c_uint32(4096)) for t in range(8192)] == \
-            [shim.hs_domain_circulant_source(C.c_uint32(t), C.c_uint32(4096)) for t in range(8192)]
+            [4095 if t == 0 else t - 4097 if t >= 4098 else -1 for t in range(8192)]
 
 
 @pytest.mark.parametrize("e", range(7))

@@ -317,3 +317,41 @@ def test_lazy_setup_of_two_sizes(levels, two_blobs):
         api.close()
         for k, v in ((b"commit_wbits", 10), (b"proof_wbits", 8)):
             api.lib.ckzg_hip_set_option(k, v)
+
+
+# ---- one pipeline behind the domain call and the coset call ----
+
+def _on_fresh_settings(calls):
+    """the results of `calls` in turn on settings of their own, which have built no transformed setup yet"""
+    api = Kzg(HIP_SO, "", precompute=0, options={"commit_wbits": 8, "proof_wbits": 6})
+    try:
+        return [call(api) for call in calls]
+    finally:
+        api.close()
+        for k, v in ((b"commit_wbits", 10), (b"proof_wbits", 8)):
+            api.lib.ckzg_hip_set_option(k, v)
+
+
+def test_the_domain_call_and_size_one_share_their_setup_in_either_order(oracle, levels, two_blobs):
+    """both calls read the transformed setup of coset size one, whichever of them built it, and one scratch layout at
+    4096 and at 8192 proofs per blob"""
+    blob = two_blobs[0]
+    want, evals = levels(blob, 0)          # (pinned above to the per-point call and the CPU oracle)
+    domain = lambda api: api.compute_domain_kzg_proofs_batch([blob])
+    size_one = lambda api: api.compute_coset_kzg_proofs_batch([blob], 0, want_evals=True)
+    for calls in ([domain, size_one, domain], [size_one, domain, size_one]):
+        for call, got in zip(calls, _on_fresh_settings(calls)):
+            assert got == (([want[:4096]], [0]) if call is domain else ([want], [evals], [0]))
+    for j in (0, 4095) + tuple(random.Random(12).sample(range(1, 4095), 3)):
+        assert oracle.compute_kzg_proof(blob, EXT[j])[0] == want[j], j
+
+
+def test_the_domain_call_ignores_what_a_coset_call_left_in_the_rows(levels, two_blobs):
+    """size 8 works on the first 1024 entries of a row and leaves the products of its columns above them; the domain
+    call's last transform of 4096 reads none of the upper half, which it does not clear"""
+    blob = two_blobs[0]
+    size_8 = lambda api: api.compute_coset_kzg_proofs_batch([blob], 3, want_evals=True)
+    domain = lambda api: api.compute_domain_kzg_proofs_batch([blob])
+    got_8, got = _on_fresh_settings([size_8, domain])
+    assert got_8 == ([levels(blob, 3)[0]], [levels(blob, 3)[1]], [0])
+    assert got == ([levels(blob, 0)[0][:4096]], [0])
