@@ -428,6 +428,26 @@ class Kzg:
                    b"".join(cells), b"".join(proofs), C.c_uint64(n), self.sp)
         return ok.value
 
+    def verify_coset_kzg_proof_batch(self, commitments, coset_indices, evals, proofs, log2_coset):
+        """ckzg_hip_verify_coset_kzg_proof_batch: item i claims that commitments[i] takes the l = 2^log2_coset values
+        evals[i] (l * 32 bytes, in the order compute_coset_kzg_proofs_batch writes them) on coset coset_indices[i] of the
+        8192-point extended domain, with the multiproof proofs[i].  Returns the verdict of the whole batch; raises
+        KzgError unless the call returned C_KZG_OK (C_KZG_RET 1: an invalid size, index, point or value)."""
+        n = len(evals)
+        _check(len(commitments) == n and len(coset_indices) == n and len(proofs) == n, "list lengths")
+        _check(0 <= log2_coset < 1 << 32, "log2_coset")
+        for v in evals:
+            _check(len(v) == 32 << min(log2_coset, 6), "evals")
+        for c in list(commitments) + list(proofs):
+            _check(len(c) == 48, "commitment/proof")
+        for i in coset_indices:
+            _check(0 <= i < 1 << 64, "coset index")
+        idx = (C.c_uint64 * max(n, 1))(*coset_indices)
+        ok = C.c_bool(False)
+        self._call("ckzg_hip_verify_coset_kzg_proof_batch", C.byref(ok), b"".join(commitments), idx, b"".join(evals),
+                   b"".join(proofs), C.c_uint64(n), C.c_uint32(log2_coset), self.sp)
+        return ok.value
+
     def verify_cell_kzg_proof_batch_groups(self, groups):
         """ckzg_hip_verify_cell_kzg_proof_batch_groups: one verify_cell_kzg_proof_batch per group, in one call.  groups
         is a list of (commitments, cell_indices, cells, proofs) tuples.  Returns (ok, status): ok[g] is the group's

@@ -142,9 +142,23 @@ struct PreparedG2 {
     host::G2Prepared gen;     // [1]_2
     host::G2Prepared s1;      // [s]_2      = g2_values_monomial[1]
     host::G2Prepared s64;     // [s^64]_2   = g2_values_monomial[64]
+    // [s^(2^e)]_2 for e = 1 .. 5 (ckzg_hip_verify_coset_kzg_proof_batch): each built by the first call of its size on
+    // these settings (prepared_s_pow2), so that load_trusted_setup does what it did
+    mutable host::G2Prepared s_pow2[5];
+    mutable std::once_flag s_pow2_once[5];
 };
 inline const PreparedG2 *prepared_of(const dev::DeviceCtx *ctx) {
     return static_cast<const PreparedG2 *>(ctx->host_prepared);
+}
+// the line table of [s^(2^e)]_2 = g2_values_monomial[2^e], e <= 6; e = 1 .. 5 are built here, once per settings (a
+// second caller of the same size waits for the first one's ~0.1 ms of host arithmetic, nothing else)
+inline const host::G2Prepared &prepared_s_pow2(const PreparedG2 *pg, int e, const KZGSettings *s) {
+    if (e == 0) return pg->s1;
+    if (e == 6) return pg->s64;
+    std::call_once(pg->s_pow2_once[e - 1], [&]() {
+        host::g2_prepare(pg->s_pow2[e - 1], host::g2_to_affine(*as_g2(&s->g2_values_monomial[(size_t)1 << e])));
+    });
+    return pg->s_pow2[e - 1];
 }
 
 // The tables a pool serves calls from.  Immutable once published; a wider table replaces a narrower one by

@@ -14,6 +14,7 @@
 #include "blob_groups_plan.hpp"
 #include "cell_groups_plan.hpp"
 #include "combiner.hpp"
+#include "coset_verify_plan.hpp"
 #include "g1_fft_plan.hpp"
 #include "locate_plan.hpp"
 #include "recover_rows_plan.hpp"
@@ -2081,6 +2082,189 @@ extern "C" C_KZG_RET verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commit
             bool res = false;
             C_KZG_RET r = verify_cells_on(ctx, &res, commitments_bytes + lo, cell_indices + lo, cells + lo,
                                           proofs_bytes + lo, hi - lo, s);
+            if (r == C_KZG_OK && !res) all_ok.store(0);
+            return r;
+        });
+        if (ret == C_KZG_OK) *ok = all_ok.load() != 0;
+        return ret;
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Coset multiproof batch verification at every coset size l = 2^e, e <= 6 (ckzg_hip_verify_coset_kzg_proof_batch): the
+// cell check above with 64 replaced by l -- its own device stages (coset_verify.hip, index maps in
+// coset_verify_plan.hpp), the shared validation, sums and pairing.  DESIGN.md section 3i.
+// ------------------------------------------------------------------------------------------
+
+static C_KZG_RET verify_cosets_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *commitments_bytes,
+                                  const uint64_t *coset_indices, const Bytes32 *evals, const Bytes48 *proofs_bytes,
+                                  uint64_t num_cosets, int e, const KZGSettings *s) {
+    *ok = false;
+    const size_t n = num_cosets, l = (size_t)1 << e, m = coset_verify_cosets(e);
+    if (n >= ((size_t)1 << 24)) return C_KZG_ERROR;   // (the lane index of a power of r has 24 bits: coset_rlc_scalars_enqueue)
+    Trace tr("verify_cosets");
+    // deduplicate commitments (eip7594.c:345-376)
+    std::vector<Bytes48> uniq;
+    std::vector<uint64_t> cidx(n);
+    for (size_t i = 0; i < n; i++) {
+        size_t j;
+        for (j = 0; j < uniq.size(); j++) {
+            if (memcmp(uniq[j].bytes, commitments_bytes[i].bytes, 48) == 0) break;
+        }
+        if (j == uniq.size()) uniq.push_back(commitments_bytes[i]);
+        cidx[i] = j;
+    }
+    const size_t nc = uniq.size();
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin((n + nc) * (48 + 2 + sizeof(G1Affine)) + n * l * (32 + sizeof(Fr)) +
+                 (n + COSET_VERIFY_EXT + COSET_INTERP_BLOCKS * l + l) * sizeof(Fr) + (2 * n + nc) * 32 +
+                 (n + m + 1 + n + 2 * n + nc + 1) * 4 + 4096));
+    ABuf<uint8_t> d_ptb(ar, (n + nc) * 48), d_st(ar, n + nc), d_st2(ar, n + nc), d_ev(ar, n * l * 32);
+    ABuf<G1Affine> d_pts(ar, n + nc);
+    ABuf<Fr> d_agg(ar, COSET_VERIFY_EXT), d_partial(ar, COSET_INTERP_BLOCKS * l), d_evfr(ar, n * l), d_rp(ar, n);
+    ABuf<uint32_t> d_interp(ar, l * 8), d_sc(ar, (2 * n + nc) * 8);   // scalars: r^i [n] | r^i x_c^l [n] | weights [nc]
+    ABuf<uint32_t> d_bad(ar, n), d_csr(ar, m + 1 + n);
+    ABuf<uint32_t> d_grp(ar, 2 * n + nc + 1);   // coset of each item [n] | commitment groups: start [nc + 1], members [n]
+    OKM(d_ptb.p && d_st.p && d_st2.p && d_ev.p && d_pts.p && d_agg.p && d_partial.p && d_evfr.p && d_rp.p && d_interp.p &&
+        d_sc.p && d_bad.p && d_csr.p && d_grp.p);
+    ArenaTrim trim(ar);
+    tr.mark("dedup");
+    // The transcript is one SHA-256 stream over every value: from COSET_VERIFY_HASH_ON_POOL_FROM items on it runs on a
+    // worker thread, underneath the copies, the GPU validation and the grouping (as in verify_cells_on).
+    Fr r;
+    struct HashJob {
+        std::atomic<uint32_t> running{0};   // futex word
+        bool submitted = false;
+        void wait() {
+            if (submitted) wait_host_work_done(&running, "coset transcript hash job");
+        }
+        ~HashJob() { wait(); }   // nothing the worker reads or writes may die before it is through
+    } hash_job;
+    const uint64_t *cidx_p = cidx.data();
+    const Bytes48 *uniq_p = uniq.data();
+    auto hash_all = [&r, uniq_p, nc, cidx_p, coset_indices, evals, proofs_bytes, n, e]() {
+        uint8_t digest[32];
+        coset_verify_digest<Sha256>(digest, uniq_p->bytes, nc, cidx_p, coset_indices, evals->bytes, proofs_bytes->bytes, n, e);
+        r = fr_from_bytes_reduce(digest);
+    };
+    if (n >= COSET_VERIFY_HASH_ON_POOL_FROM) {
+        HashJob *hj = &hash_job;
+        hash_job.running.store(1, std::memory_order_relaxed);
+        hash_job.submitted = WorkerPool::get().submit([hash_all, hj]() {
+            hash_all();
+            hj->running.store(0, std::memory_order_release);
+            futex_wake(&hj->running, INT_MAX);
+        });
+    }
+    OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, 2 * (n + nc) + n * 4));
+    uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[0]), *h_st2 = h_st + (n + nc);
+    uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
+    // proofs [0, n), distinct commitments [n, n + nc): all copies from pageable memory first (such a copy returns only
+    // when it is done, so it must not queue behind a kernel), then values -> Fr and the decompression
+    OKB(hipMemcpyAsync(d_ptb.p, proofs_bytes, n * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_ptb.p + n * 48, uniq.data(), nc * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_ev.p, evals, n * l * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemsetAsync(d_bad.p, 0, n * 4, ctx->stream) == hipSuccess);
+    RC(dev::bytes_to_fr_batch(ctx, d_evfr.p, d_bad.p, d_ev.p, n * l, (uint32_t)l));
+    OKB(hipMemcpyAsync(h_bad, d_bad.p, n * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    RC(dev::decompress_g1_batch_device(ctx, d_pts.p, d_st.p, d_ptb.p, n + nc));
+    OKB(hipMemcpyAsync(h_st, d_st.p, n + nc, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess &&
+        dev::ensure_event(ctx->flags_ev) == hipSuccess);
+    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
+    // the subgroup test (~1 ms of dependent doublings) on the second stream, next to everything below; a point outside
+    // the subgroup makes the sums meaningless, not unsafe, and the call ends in BADARGS
+    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
+    RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pts.p, n + nc, ctx->copy_stream));
+    OKB(hipMemcpyAsync(h_st2, d_st2.p, n + nc, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
+    StreamDrain drain{ctx->copy_stream};   // whatever path leaves this function: idle before the arena is reused
+    // items grouped by coset (counting sort) for the aggregation, and by commitment for the weights
+    {
+        std::vector<uint32_t> csr(m + 1 + n, 0);
+        for (size_t i = 0; i < n; i++) csr[coset_indices[i] + 1]++;
+        for (size_t c = 0; c < m; c++) csr[c + 1] += csr[c];
+        std::vector<uint32_t> fill(csr.begin(), csr.begin() + m);
+        for (size_t i = 0; i < n; i++) csr[m + 1 + fill[coset_indices[i]]++] = (uint32_t)i;
+        OKB(hipMemcpyAsync(d_csr.p, csr.data(), csr.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        std::vector<uint32_t> grp(2 * n + nc + 1, 0);
+        uint32_t *col = grp.data(), *start = grp.data() + n, *members = grp.data() + n + nc + 1;
+        for (size_t i = 0; i < n; i++) {
+            col[i] = (uint32_t)coset_indices[i];
+            start[cidx[i] + 1]++;
+        }
+        for (size_t j = 0; j < nc; j++) start[j + 1] += start[j];
+        std::vector<uint32_t> gfill(start, start + nc);
+        for (size_t i = 0; i < n; i++) members[gfill[cidx[i]]++] = (uint32_t)i;
+        OKB(hipMemcpyAsync(d_grp.p, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    }
+    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
+    auto flags_ok = [&]() -> C_KZG_RET {
+        OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
+        for (size_t i = 0; i < n + nc; i++) {
+            if (h_st[i] || h_st2[i]) return C_KZG_BADARGS;  // bad encoding / off the curve / outside G1
+        }
+        for (size_t i = 0; i < n; i++) {
+            if (h_bad[i]) return C_KZG_BADARGS;  // a non-canonical value (bytes.c:67)
+        }
+        return C_KZG_OK;
+    };
+    tr.mark("copies, validation, grouping (underneath the transcript hash)");
+    if (hash_job.submitted)
+        hash_job.wait();
+    else
+        hash_all();
+    tr.mark("transcript hash");
+    // stage 2: the scalars, made on the GPU from r
+    uint32_t *d_vec_rp = d_sc.p, *d_vec_wrp = d_sc.p + n * 8, *d_vec_w = d_sc.p + 2 * n * 8;
+    RC(dev::coset_rlc_scalars_enqueue(ctx, d_rp.p, d_vec_rp, d_vec_wrp, d_vec_w, d_grp.p, d_grp.p + n, d_grp.p + n + nc + 1, r, n, nc, e));
+    // stages 3 to 5: sum of r^i y_i per coset (eip7594.c:661-683), each column's interpolation polynomial, their sum
+    // with the coset factors taken out (eip7594.c:549-566)
+    RC(dev::coset_aggregate_device(ctx, d_agg.p, d_evfr.p, d_rp.p, d_csr.p, d_csr.p + m + 1, n, e));
+    RC(dev::coset_interp_device(ctx, d_interp.p, d_partial.p, d_agg.p, e));
+    // the four sums (eip7594.c:926, :530, :807 and the commitment to the aggregated interpolation polynomial over the
+    // first l monomial setup points, :758) in one launch of ladders
+    G1Jac lc[4];
+    LincombJob jobs[4] = {{d_pts.p, nullptr, (const RawScalar *)d_vec_rp, n},
+                          {d_pts.p + n, nullptr, (const RawScalar *)d_vec_w, nc},
+                          {d_pts.p, nullptr, (const RawScalar *)d_vec_wrp, n},
+                          {ctx->d_mono, nullptr, (const RawScalar *)d_interp.p, l}};
+    RC(gpu_lincomb_multi(ctx, lc, jobs, 4));
+    RC(flags_ok());   // an invalid point or value makes the sums above meaningless, not unsafe: discarded
+    tr.mark("scalars, aggregation, interpolation, four lincombs");
+    const G1Jac &proof_lc = lc[0], &csum = lc[1], &wsum = lc[2], &interp_commit = lc[3];
+    G1Jac final_sum = jac_add(jac_add(csum, jac_neg(interp_commit)), wsum);
+    // e(final_sum, [1]_2) == e(proof_lc, [s^l]_2)
+    *ok = pairing_product_is_one(jac_to_affine_fast(final_sum), prepared_of(ctx)->gen, jac_to_affine_fast(jac_neg(proof_lc)),
+                                 prepared_s_pow2(prepared_of(ctx), e, s));
+    tr.mark("pairing check");
+    return C_KZG_OK;
+}
+
+extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes,
+                                                           const uint64_t *coset_indices, const Bytes32 *evals,
+                                                           const Bytes48 *proofs_bytes, uint64_t num_cosets,
+                                                           uint32_t log2_coset, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (ok == NULL) return C_KZG_BADARGS;
+        *ok = false;
+        if (log2_coset > CKZG_HIP_COSET_MAX_LOG2) return C_KZG_BADARGS;
+        if (num_cosets == 0) {
+            *ok = true;
+            return C_KZG_OK;
+        }
+        if (commitments_bytes == NULL || coset_indices == NULL || evals == NULL || proofs_bytes == NULL) return C_KZG_BADARGS;
+        const int e = (int)log2_coset;
+        for (size_t i = 0; i < num_cosets; i++) {
+            if (coset_indices[i] >= coset_verify_cosets(e)) return C_KZG_BADARGS;
+        }
+        if (!settings_of(s)) return C_KZG_ERROR;
+        // several devices: contiguous shards of items, each with its own challenge and pairing check, AND-ed
+        std::atomic<int> all_ok(1);
+        C_KZG_RET ret = for_each_device_shard(s, num_cosets, COSET_VERIFY_MIN_SHARD, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            bool res = false;
+            C_KZG_RET r = verify_cosets_on(ctx, &res, commitments_bytes + lo, coset_indices + lo, evals + (lo << e),
+                                           proofs_bytes + lo, hi - lo, e, s);
             if (r == C_KZG_OK && !res) all_ok.store(0);
             return r;
         });

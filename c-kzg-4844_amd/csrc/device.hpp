@@ -543,6 +543,19 @@ int cell_aggregate_device(DeviceCtx *ctx, Fr *d_agg, const Fr *d_cell_fr, const 
                           const uint32_t *d_order, size_t n_cells);
 // interpolation-polynomial coefficients summed over the 128 columns, as canonical MSM scalars
 int interp_sum_device(DeviceCtx *ctx, Fr *d_interp, const Fr *d_cols);
+// coset_verify.hip: the same steps at every coset size l = 2^e, e <= 6 (ckzg_hip_verify_coset_kzg_proof_batch; index
+// maps: coset_verify_plan.hpp).  All enqueue-only, on ctx->stream.
+//   d_rp[n] <- r^i (Montgomery), d_vec_rp[n][8] <- r^i, d_vec_wrp[n][8] <- r^i * x_c^l of the item's coset
+//   d_coset_idx[i], d_vec_w[nc][8] <- per-commitment sums of r^i over the member lists (d_grp_start[nc + 1], d_members[n])
+int coset_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_vec_rp, uint32_t *d_vec_wrp, uint32_t *d_vec_w,
+                              const uint32_t *d_coset_idx, const uint32_t *d_grp_start, const uint32_t *d_members, const Fr &r,
+                              size_t n, size_t nc, int e);
+//   agg[c l + j] = sum over the items i of coset c (CSR: col_start[(8192 >> e) + 1], order[n]) of rp[i] * item_fr[i l + j]
+int coset_aggregate_device(DeviceCtx *ctx, Fr *d_agg, const Fr *d_item_fr, const Fr *d_rp, const uint32_t *d_col_start,
+                           const uint32_t *d_order, size_t n_items, int e);
+//   d_agg[8192] <- each column's interpolation coefficients over the l-th roots of unity (in place); d_interp[l][8] <-
+//   their sum over the columns, each times x_c^-k, as canonical MSM scalars; d_partial: COSET_INTERP_BLOCKS * l scratch
+int coset_interp_device(DeviceCtx *ctx, uint32_t *d_interp, Fr *d_partial, Fr *d_agg, int e);
 // The same steps segmented by group (ckzg_hip_verify_cell_kzg_proof_batch_groups; index maps: cell_groups_plan.hpp over
 // the job layout of group_jobs.hpp, whose field names the parameters carry).  All enqueue-only, on ctx->stream.
 // d_sc: the scalars of every job ([total][8], zeroed by the caller), d_r: the groups' challenges (Montgomery).

@@ -1059,3 +1059,29 @@ extern "C" int hs_coset_circulant_source(uint32_t t, int e, uint32_t n) { return
 extern "C" int hs_coset_setup_source(uint32_t t, int e, uint32_t n) { return coset_setup_source(t, e, n); }
 extern "C" uint32_t hs_coset_colsum_radix() { return COSET_COLSUM_RADIX; }
 extern "C" uint32_t hs_coset_colsum_parts(int e) { return coset_colsum_parts(e); }
+
+// ---- coset multiproof verification, every coset size (tests/test_coset_verify_cpu.py) ----
+#include "coset_verify_plan.hpp"
+extern "C" uint32_t hs_coset_verify_cosets(int e) { return coset_verify_cosets(e); }
+extern "C" uint32_t hs_coset_verify_brp(uint32_t c, int e) { return coset_verify_brp(c, e); }
+extern "C" uint32_t hs_coset_verify_shift_root(uint32_t c, int e) { return coset_verify_shift_root(c, e); }
+extern "C" uint32_t hs_coset_verify_unshift_root(uint32_t c, int e, uint32_t k) { return coset_verify_unshift_root(c, e, k); }
+extern "C" uint32_t hs_coset_verify_slot(uint32_t c, int e, uint32_t j) { return coset_verify_slot(c, e, j); }
+extern "C" uint32_t hs_coset_verify_twiddle_root(uint32_t pos, int s) { return coset_verify_twiddle_root(pos, s); }
+extern "C" uint32_t hs_coset_verify_agg_parts(uint64_t items, int e) { return coset_verify_agg_parts(items, e); }
+// what[0] = items per lane, [1] = most parts, [2] = transcript on the pool from, [3] = smallest shard, [4] = slots per
+// aggregation workgroup, [5] = threads of an interpolation workgroup
+extern "C" void hs_coset_verify_constants(uint64_t *what) {
+    what[0] = COSET_AGG_ITEMS_PER_LANE;
+    what[1] = COSET_AGG_MAX_PARTS;
+    what[2] = COSET_VERIFY_HASH_ON_POOL_FROM;
+    what[3] = COSET_VERIFY_MIN_SHARD;
+    what[4] = COSET_AGG_SLOTS_PER_BLOCK;
+    what[5] = COSET_INTERP_THREADS;
+}
+extern "C" void hs_coset_verify_digest(uint8_t *digest32, const uint8_t *commitments48, uint64_t num_commitments,
+                                       const uint64_t *commitment_indices, const uint64_t *coset_indices,
+                                       const uint8_t *evals32, const uint8_t *proofs48, uint64_t num_cosets, int e) {
+    coset_verify_digest<Sha256>(digest32, commitments48, num_commitments, commitment_indices, coset_indices, evals32, proofs48,
+                                num_cosets, e);
+}
