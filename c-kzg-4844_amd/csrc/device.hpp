@@ -479,6 +479,13 @@ int proofs_stage_enqueue(DeviceCtx *ctx, uint8_t *d_proofs, const Fr *d_poly, si
 int bad_to_status_enqueue(DeviceCtx *ctx, uint8_t *d_status, const uint32_t *d_bad, size_t k);
 // FK20 proofs from monomial coefficients already on the device ([n][4096] Fr, Montgomery)
 int fk20_proofs_device(DeviceCtx *ctx, uint8_t *d_proofs, const Fr *d_poly_monomial, size_t n);
+// The two length-128 G1 transforms of FK20 as one stage: d_u[f][k] <- sum_{j < 64} w^(jk) sum_{g < 128} w^(-gj) d_u[f][g]
+// on n vectors of 128 points, in place, natural order in and out, no factor 1/128 (the MSM scalars carry it).  Which of
+// the six forms runs: fk20_fft_plan.hpp with the hand-over points of this build (fk20_fft_form_for).  Enqueue-only, on
+// ctx->stream; `scratch` of fk20_fft_scratch_bytes(n); builds the context's twiddle records on first use (needs d_roots).
+int fk20_fft_form_for(size_t n);
+size_t fk20_fft_scratch_bytes(size_t n);
+int fk20_fft_stage_enqueue(DeviceCtx *ctx, G1XYZZ *d_u, uint8_t *scratch, size_t n);
 void fk20_collect_times(DeviceCtx *ctx);
 // the six nodes of commit_blobs_enqueue(n = 1) between a host input and a host result buffer as an explicitly built,
 // instantiated graph (msm.hip says why not a capture); 0 ok, 4 geometry does not apply, 2 HIP error

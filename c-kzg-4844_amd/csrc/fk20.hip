@@ -14,6 +14,7 @@
 // The two G1 transforms use the DIF/DIT pair so that, as for Fr, no permutation pass exists.
 #include "device.hpp"
 #include "dev_inline.hpp"
+#include "fk20_fft_plan.hpp"
 #include "g1_28.hpp"
 #include "g1_quad.hpp"
 #include "g1_pipe.hpp"
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(64) void k_g1_fft_fold(G1XYZZ *data, size_t npairs)
 // on ONE (group, ladder) pair: one twiddle, uniform NAF digits.
 // ------------------------------------------------------------------------------------------
 
-constexpr int R4_LADDERS = 32 * 5;  // per transform and radix-4 step
+constexpr int R4_LADDERS = FK20_R4_LADDERS;  // per transform and radix-4 step (fk20_fft_plan.hpp: 32 groups x 5)
 
 __device__ __forceinline__ void r4_group(int grp, int s, int dif, int &t, int &p0, int &p1, int &p2, int &p3) {
     if (dif) {
@@ -397,8 +398,9 @@ __global__ __launch_bounds__(64) void k_g1_fft_r4_post(G1XYZZ *out, const G1XYZZ
 // ~390 doubling steps); the sums around the ladders by k_g1_fft_r8_post, one quad per output point.
 // ------------------------------------------------------------------------------------------
 
-constexpr int R8_PER_GROUP = 21;
-constexpr int R8_LADDERS = 16 * R8_PER_GROUP;  // per transform and radix-8 step
+constexpr int R8_PER_GROUP = FK20_R8_PER_GROUP;   // (fk20_fft_plan.hpp: 21)
+constexpr int R8_LADDERS = FK20_R8_LADDERS;       // per transform and radix-8 step: 16 groups
+static_assert(sizeof(G1XYZZ) == FK20_POINT_BYTES && quad::RAW_WORDS * sizeof(uint32_t) == FK20_RAW_BYTES, "fk20_fft_plan.hpp sizes the scratch");
 
 __device__ __forceinline__ int bitrev3(int v) { return ((v & 1) << 2) | (v & 2) | ((v >> 2) & 1); }
 
@@ -684,34 +686,37 @@ __global__ __launch_bounds__(64) void k_g1_fft_fold_raw(uint32_t *data, size_t n
     }
 }
 
-// Hand-over points (same-box A/Bs: profiles/r05_fk20_small_ab.txt).  Three-wave ladders while their 21 workgroups per
-// transform and step mostly find a SIMD per wave (<= 16 transforms: 336 workgroups); radix-8 steps with the one-wave
-// ladder while a step's waves fit the chip about once (<= 48 transforms: 1008 waves); radix-4 / radix-2 beyond.
-static size_t r8_pipe_max_transforms() {
-    static const size_t v = (size_t)ab_knob("CKZG_HIP_R8_PIPE_MAX", 16);
-    return v;
+// The hand-over points between the forms (fk20_fft_plan.hpp says what chose the defaults); the A/B build reads them
+// from the environment.
+static const Fk20FftLimits &fk20_fft_limits() {
+    static const Fk20FftLimits lim = [] {
+        Fk20FftLimits d, l;
+        l.r8_two_max = (uint64_t)ab_knob("CKZG_HIP_R8_TWO_MAX", (long)d.r8_two_max);
+        l.r8_pipe_max = (uint64_t)ab_knob("CKZG_HIP_R8_PIPE_MAX", (long)d.r8_pipe_max);
+        l.r8_max = (uint64_t)ab_knob("CKZG_HIP_R8_FFT_MAX", (long)d.r8_max);
+        l.r4_max = (uint64_t)ab_knob("CKZG_HIP_R4_FFT_MAX", (long)d.r4_max);
+        l.quad_max = (uint64_t)ab_knob("CKZG_HIP_QUAD_FFT_MAX", (long)d.quad_max);
+        return l;
+    }();
+    return lim;
 }
-static size_t r8_max_transforms() {
-    static const size_t v = (size_t)ab_knob("CKZG_HIP_R8_FFT_MAX", 48);
-    return v;
-}
+int fk20_fft_form_for(size_t n) { return fk20_fft_form(n, fk20_fft_limits()); }
 
 // Both transforms of FK20 for a small batch as radix-8 steps on raw records: inverse DIF (7,6,5), (4,3,2), the fold,
 // forward DIT (2,3,4), (5,6,7).  d_u: nfft x 128 points in and out (G1XYZZ); d_a, d_b: nfft x 128 raw records;
-// d_lad: nfft x R8_LADDERS raw records.
+// d_lad: nfft x R8_LADDERS raw records.  form: one of the three radix-8 forms of fk20_fft_plan.hpp.
 static int g1_fft_r8_fk20(DeviceCtx *ctx, G1XYZZ *d_u, uint32_t *d_a, uint32_t *d_b, uint32_t *d_lad, const uint32_t *d_glv,
-                          size_t nfft) {
+                          size_t nfft, int form) {
     const size_t pad = (nfft + 15) / 16 * 16;
     const dim3 lgrid((unsigned)(pad * R8_LADDERS / 16)), pgrid((unsigned)(nfft * 128 * 4 / 64)), block(64);
     hipLaunchKernelGGL(k_g1_to_raw, dim3((unsigned)((nfft * 128 + 63) / 64)), block, 0, ctx->stream, d_a, d_u, nfft * 128);
     uint32_t *cur = d_a, *nxt = d_b;
-    const bool pipe = nfft <= r8_pipe_max_transforms();
-    static const size_t two_max = (size_t)ab_knob("CKZG_HIP_R8_TWO_MAX", 8);
+    const bool pipe = form != FK20_FFT_R8_ONE;
     static const bool dual = ab_knob("CKZG_HIP_R8_DUAL", 1) != 0;
     static const bool one_full = ab_knob("CKZG_HIP_R8_ONE_FULL", 1) != 0;
     static const unsigned wg1 = (unsigned)ab_knob("CKZG_HIP_LADDER_WG", 256);   // threads per workgroup of the one-wave ladder kernels
     auto step = [&](int s, int dif, int inverse, G1XYZZ *final_out) {
-        if (pipe && nfft <= two_max) {   // two ladder indices per workgroup: 168 workgroups, one per compute unit
+        if (form == FK20_FFT_R8_PIPE_TWO) {   // two ladder indices per workgroup: 168 workgroups, one per compute unit
             hipLaunchKernelGGL(k_g1_fft_r8_ladder_pipe, dim3((unsigned)(R8_LADDERS / 2)), dim3(192), 0, ctx->stream, d_lad, cur, d_glv,
                                (uint32_t)nfft, s, dif, inverse, 1);
         } else if (pipe && dual)   // two-wave workgroups: two to a compute unit, a SIMD per wave
@@ -765,22 +770,13 @@ static int g1_fft_r4_pairs(DeviceCtx *ctx, G1XYZZ *d_data, G1XYZZ *d_tmp, G1XYZZ
     return 0;
 }
 
-static size_t r4_max_transforms() {
-    // measured hand-over (tools/bench_fk20_sizes.py, profiles/r02_quad_ab.txt): radix-4 pairs win up to ~100
-    // transforms, tie with the radix-2 four-lane form up to ~200, lose beyond
-    static const size_t v = (size_t)ab_knob("CKZG_HIP_R4_FFT_MAX", 128);
-    return v;
-}
-
+// use_quad: four lanes per butterfly while that is at most ~two waves per SIMD (64 butterflies x nfft x 4 lanes,
+// fk20_fft_plan.hpp: quad_max): up to there the one-lane form is latency-bound (a lone wave issues a mad every 9.4
+// cycles) and the quad form's 12 lane-products per doubling instead of 7 cost nothing
 static int g1_fft_stages(DeviceCtx *ctx, G1XYZZ *d_data, const uint32_t *d_glv, size_t nfft, bool dif,
-                         int s_from, int s_to, int inverse) {
+                         int s_from, int s_to, int inverse, bool use_quad) {
     // dif: s runs downwards from s_from to s_to; dit: upwards
     const dim3 grid((unsigned)((nfft + 63) / 64 * 64)), block(64);  // 64 butterflies x padded transforms / 64 lanes
-    // four lanes per butterfly while that is at most ~two waves per SIMD (64 butterflies x nfft x 4 lanes): up
-    // to there the one-lane form is latency-bound (a lone wave issues a mad every 9.4 cycles) and the quad
-    // form's 12 lane-products per doubling instead of 7 cost nothing
-    static const size_t quad_max = (size_t)ab_knob("CKZG_HIP_QUAD_FFT_MAX", 512);
-    const bool use_quad = nfft <= quad_max;
     const dim3 qgrid((unsigned)((nfft + 15) / 16 * 16 * 4));        // 64 butterflies x padded transforms x 4 / 64 lanes
     for (int s = s_from; dif ? s >= s_to : s <= s_to; s += dif ? -1 : 1) {
         if (dif) hipLaunchKernelGGL(k_g1_fft_addsub, grid, block, 0, ctx->stream, d_data, (uint32_t)nfft, s);
@@ -873,7 +869,7 @@ int fk20_setup_device(DeviceCtx *ctx, const G1Affine *d_monomial, G1Affine *h_xe
     Fp *d_prefix = static_cast<Fp *>(prefix.p);
     if (!ctx->d_xext) HIP_TRY(hipMalloc(&ctx->d_xext, npts * sizeof(G1Affine)));
     hipLaunchKernelGGL(k_xext_gather, dim3(npts / 256), dim3(256), 0, ctx->stream, d_xin, d_monomial);
-    rc = g1_fft_stages(ctx, d_xin, d_rr, 64, /*dif=*/true, 7, 1, /*inverse=*/0);
+    rc = g1_fft_stages(ctx, d_xin, d_rr, 64, /*dif=*/true, 7, 1, /*inverse=*/0, /*use_quad=*/64 <= fk20_fft_limits().quad_max);
     if (!rc) {
         hipLaunchKernelGGL(k_xext_transpose, dim3(npts / 256), dim3(256), 0, ctx->stream, d_cols, d_xin);
         if (hipGetLastError() != hipSuccess) rc = 2;
@@ -899,11 +895,57 @@ struct Fk20Scratch {
     G1XYZZ *u;         // [n][128]
     G1Affine *aff;     // [n][128]
     Fp *prefix;        // [n][128]
+    uint8_t *fft;      // the scratch of the two G1 transforms (Fk20FftScratch)
+    size_t bytes;
+};
+
+// Scratch of the two G1 transforms over n vectors, by the form fk20_fft_plan.hpp picks for n (none for radix-2)
+struct Fk20FftScratch {
     G1XYZZ *r4_tmp;    // [n][128]          (small batches: radix-4 G1 FFT steps)
     G1XYZZ *r4_lad;    // [n][R4_LADDERS]
     uint32_t *r8_a, *r8_b, *r8_lad;   // raw records (g1_pipe.hpp): [n][128] twice, [n][R8_LADDERS] -- the smallest batches
     size_t bytes;
 };
+
+static Fk20FftScratch fk20_fft_layout(uint8_t *base, size_t n, int form) {
+    const Fk20FftScratchPlan p = fk20_fft_scratch_plan(n, form);
+    Fk20FftScratch s;
+    s.r4_tmp = s.r4_lad = nullptr;
+    s.r8_a = s.r8_b = s.r8_lad = nullptr;
+    if (fk20_fft_is_r8(form)) {
+        s.r8_a = reinterpret_cast<uint32_t *>(base + p.a);
+        s.r8_b = reinterpret_cast<uint32_t *>(base + p.b);
+        s.r8_lad = reinterpret_cast<uint32_t *>(base + p.lad);
+    } else if (form == FK20_FFT_R4) {
+        s.r4_tmp = reinterpret_cast<G1XYZZ *>(base + p.a);
+        s.r4_lad = reinterpret_cast<G1XYZZ *>(base + p.lad);
+    }
+    s.bytes = (size_t)p.bytes;
+    return s;
+}
+
+size_t fk20_fft_scratch_bytes(size_t n) { return (size_t)fk20_fft_scratch_plan(n, fk20_fft_form_for(n)).bytes; }
+
+// h = IFFT(u) truncated to its first 64 entries, out = FFT(h) (fk20.c:257-269) on n vectors of 128 points, in place:
+// inverse DIF stages 7..2, the fused stage pair around the truncation, forward DIT stages 2..7, in the form n selects
+int fk20_fft_stage_enqueue(DeviceCtx *ctx, G1XYZZ *d_u, uint8_t *scratch, size_t n) {
+    if (n == 0) return 0;
+    uint32_t *d_rr = nullptr;
+    int rc = ensure_roots_raw(ctx, &d_rr);
+    if (rc) return rc;
+    const int form = fk20_fft_form_for(n);
+    const Fk20FftScratch s = fk20_fft_layout(scratch, n, form);
+    if (fk20_fft_is_r8(form))   // the smallest batches: stage triples on raw records (4 ladder depths)
+        return g1_fft_r8_fk20(ctx, d_u, s.r8_a, s.r8_b, s.r8_lad, d_rr, n, form);
+    const bool r4 = form == FK20_FFT_R4;   // small batch: stage pairs with independent ladders (6 ladder depths, not 12)
+    const bool quad = form == FK20_FFT_R2_QUAD;
+    rc = r4 ? g1_fft_r4_pairs(ctx, d_u, s.r4_tmp, s.r4_lad, d_rr, n, /*dif=*/true, 7, 2, /*inverse=*/1)
+            : g1_fft_stages(ctx, d_u, d_rr, n, /*dif=*/true, 7, 2, /*inverse=*/1, quad);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_g1_fft_fold, dim3((unsigned)((n * 64 + 63) / 64)), dim3(64), 0, ctx->stream, d_u, n * 64);
+    return r4 ? g1_fft_r4_pairs(ctx, d_u, s.r4_tmp, s.r4_lad, d_rr, n, /*dif=*/false, 2, 7, /*inverse=*/0)
+              : g1_fft_stages(ctx, d_u, d_rr, n, /*dif=*/false, 2, 7, /*inverse=*/0, quad);
+}
 
 static Fk20Scratch fk20_layout(uint8_t *base, size_t n, int nwin) {
     Fk20Scratch s;
@@ -918,22 +960,8 @@ static Fk20Scratch fk20_layout(uint8_t *base, size_t n, int nwin) {
     off += al(n * 128 * sizeof(G1Affine));
     s.prefix = reinterpret_cast<Fp *>(base + off);
     off += al(n * 128 * sizeof(Fp));
-    s.r4_tmp = s.r4_lad = nullptr;
-    s.r8_a = s.r8_b = s.r8_lad = nullptr;
-    if (n <= r8_max_transforms()) {
-        const size_t rec = quad::RAW_WORDS * sizeof(uint32_t);
-        s.r8_a = reinterpret_cast<uint32_t *>(base + off);
-        off += al(n * 128 * rec);
-        s.r8_b = reinterpret_cast<uint32_t *>(base + off);
-        off += al(n * 128 * rec);
-        s.r8_lad = reinterpret_cast<uint32_t *>(base + off);
-        off += al(n * R8_LADDERS * rec);
-    } else if (n <= r4_max_transforms()) {
-        s.r4_tmp = reinterpret_cast<G1XYZZ *>(base + off);
-        off += al(n * 128 * sizeof(G1XYZZ));
-        s.r4_lad = reinterpret_cast<G1XYZZ *>(base + off);
-        off += al(n * R4_LADDERS * sizeof(G1XYZZ));
-    }
+    s.fft = base + off;
+    off += fk20_fft_scratch_bytes(n);
     s.bytes = off;
     return s;
 }
@@ -961,20 +989,8 @@ static int fk20_run(DeviceCtx *ctx, uint8_t *d_proofs, const Fr *d_poly, size_t 
     // h = IFFT(u) truncated to its first 64 entries, proofs = FFT(h) (fk20.c:257-269): inverse DIF
     // stages 7..2, the fused stage pair around the truncation, forward DIT stages 2..7
     HIP_TRY(hipEventRecord(ctx->ev[7], ctx->stream));
-    if (s.r8_lad) {
-        // the smallest batches: stage triples on raw records (4 ladder depths)
-        rc = g1_fft_r8_fk20(ctx, s.u, s.r8_a, s.r8_b, s.r8_lad, d_rr, n);
-        if (rc) return rc;
-    } else {
-        const bool r4 = s.r4_lad != nullptr;   // small batch: stage pairs with independent ladders (6 ladder depths, not 12)
-        rc = r4 ? g1_fft_r4_pairs(ctx, s.u, s.r4_tmp, s.r4_lad, d_rr, n, /*dif=*/true, 7, 2, /*inverse=*/1)
-                : g1_fft_stages(ctx, s.u, d_rr, n, /*dif=*/true, 7, 2, /*inverse=*/1);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_g1_fft_fold, dim3((unsigned)((n * 64 + 63) / 64)), dim3(64), 0, ctx->stream, s.u, n * 64);
-        rc = r4 ? g1_fft_r4_pairs(ctx, s.u, s.r4_tmp, s.r4_lad, d_rr, n, /*dif=*/false, 2, 7, /*inverse=*/0)
-                : g1_fft_stages(ctx, s.u, d_rr, n, /*dif=*/false, 2, 7, /*inverse=*/0);
-        if (rc) return rc;
-    }
+    rc = fk20_fft_stage_enqueue(ctx, s.u, s.fft, n);
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(ctx->ev[8], ctx->stream));
     rc = batch_to_affine_device(ctx, s.aff, s.u, s.prefix, n * 128);
     if (rc) return rc;

@@ -1060,6 +1060,12 @@ extern "C" int hs_coset_setup_source(uint32_t t, int e, uint32_t n) { return cos
 extern "C" uint32_t hs_coset_colsum_radix() { return COSET_COLSUM_RADIX; }
 extern "C" uint32_t hs_coset_colsum_parts(int e) { return coset_colsum_parts(e); }
 
+// ---- fk20_fft_plan.hpp: which form the two G1 transforms of FK20 take for n transforms, at the default hand-over
+// ---- points (tests/test_fk20_expect_cpu.py) ----
+#include "fk20_fft_plan.hpp"
+extern "C" int hs_fk20_fft_form(uint64_t n) { return fk20_fft_form(n); }
+extern "C" uint64_t hs_fk20_fft_scratch_bytes(uint64_t n) { return fk20_fft_scratch_plan(n, fk20_fft_form(n)).bytes; }
+
 // ---- coset multiproof verification, every coset size (tests/test_coset_verify_cpu.py) ----
 #include "coset_verify_plan.hpp"
 extern "C" uint32_t hs_coset_verify_cosets(int e) { return coset_verify_cosets(e); }

@@ -5,6 +5,7 @@ import hashlib
 
 import pytest
 
+import fk20_edge as fe
 import golden_util as G
 from test_gpu_commitment import rand_blob
 
@@ -98,18 +99,31 @@ def test_large_batch_takes_fk20_and_16_lane_msm_path(hip):
         assert b"".join(p) == proofs.raw[i * 128 * 48:(i + 1) * 128 * 48]
 
 
-# The sizes on BOTH sides of every point where the G1 transforms or the small MSMs change form (fk20.hip:
-# r8_pipe_max_transforms = 16, r8_max_transforms = 48, r4_max_transforms = 128; two twiddles per workgroup up to 8;
+# The sizes on BOTH sides of every point where the G1 transforms or the small MSMs change form (fk20_fft_plan.hpp:
+# r8_pipe_max = 16, r8_max = 48, r4_max = 128, quad_max = 512; two twiddles per workgroup up to r8_two_max = 8;
 # msm.hip msm_small_vectors_device: one wave per vector below 8192 vectors = 64 blobs, 16 lanes per vector from there,
 # 8 lanes from 65,536 vectors = 512 blobs), plus interior sizes.
 FORM_SIZES = [2, 3, 5, 8, 9, 16, 17, 24, 32, 33, 48, 49, 63, 64, 128, 129, 511, 512]
 
 
+def blob_c_x64(c, seed):
+    """c x^64 + r(x) with a random r of degree < 64, in evaluation form over the bit-reversed domain (as
+    fk20_edge.blob_with_fk20_scalars builds its blobs): only row 63 of the circulant scalars is not zero, the inverse G1
+    transform is [c] G at j = 0 and the identity at j = 1..63, so 63 of the 64 fold additions of every form cancel, the
+    forward transform runs on one point among identities, and all 128 proofs are [c] G"""
+    poly = [int.from_bytes(hashlib.sha256(b"low%d.%d" % (seed, j)).digest(), "big") % fe.R for j in range(64)]
+    poly += [c % fe.R] + [0] * (4096 - 65)
+    ev = fe._ntt(poly, fe.W4096)
+    return b"".join(ev[fe._brp(i, 12)].to_bytes(32, "big") for i in range(4096))
+
+
 @pytest.fixture(scope="module")
 def form_blobs(oracle):
-    """five distinct blobs -- three random, the zero blob (all proofs at infinity: every ladder input is the point at
-    infinity), a constant polynomial -- and what the ORACLE says their cells and proofs are"""
+    """seven distinct blobs -- three random, the zero blob (all proofs at infinity: every ladder input is the point at
+    infinity), a constant polynomial, and c x^64 + r(x) for a random c and for c = R - 1 (cancellations at the fold, then one
+    point among identities) -- and what the ORACLE says their cells and proofs are"""
     base = [rand_blob(77, i) for i in range(3)] + [bytes(131072), (b"\x00" * 31 + b"\x07") * 4096]
+    base += [blob_c_x64(int.from_bytes(hashlib.sha256(b"c x^64").digest(), "big"), 0), blob_c_x64(fe.R - 1, 1)]
     exp = []
     for b in base:
         c, p = oracle.compute_cells_and_kzg_proofs(b)
@@ -125,7 +139,7 @@ def test_small_batches_take_every_g1_fft_form(hip, form_blobs, n):
     (17..48); radix-4 steps with the one-wave quad ladder (49..128), radix-2 stages beyond.  EVERY blob of every batch
     against the oracle, at the last size of each form and the first of the next."""
     base, exp = form_blobs
-    blobs = [base[(i + i // 5) % 5] for i in range(n)]
+    blobs = [base[(i + i // 7) % 7] for i in range(n)]
     cells = C.create_string_buffer(n * 128 * 2048)
     proofs = C.create_string_buffer(n * 128 * 48)
     status = C.create_string_buffer(n)
@@ -136,7 +150,7 @@ def test_small_batches_take_every_g1_fft_form(hip, form_blobs, n):
     assert status.raw == bytes(n)
     craw, praw = memoryview(cells).cast("B"), memoryview(proofs).cast("B")
     for i in range(n):
-        ec, ep, _ = exp[(i + i // 5) % 5]
+        ec, ep, _ = exp[(i + i // 7) % 7]
         assert praw[i * 128 * 48:(i + 1) * 128 * 48] == ep, i
         assert craw[i * 128 * 2048:(i + 1) * 128 * 2048] == ec, i
 
@@ -150,7 +164,7 @@ def test_recover_batches_take_every_g1_fft_form(hip, form_blobs, rows):
     idx = [(3 * j + 1) % 128 for j in range(128) if j % 2 == 0]   # 64 columns, not sorted by construction ...
     idx = sorted(set(idx))                                         # ... the API wants them ascending
     assert len(idx) == 64
-    which = [(r + r // 3) % 5 for r in range(rows)]
+    which = [(r + r // 3) % 7 for r in range(rows)]
     row_cells = [[exp[w][2][j] for j in idx] for w in which]
     rc, rp = hip.recover_cells_and_kzg_proofs_batch(idx, row_cells)
     for r, w in enumerate(which):
