@@ -415,6 +415,42 @@ class Kzg:
                                          for i in range(CELLS_PER_EXT_BLOB)] for r in range(nr)] if want_proofs else None
         return out_c, out_p, status
 
+    def recover_cosets_and_kzg_proofs_rows(self, rows, log2_coset, want_evals=True, want_proofs=True):
+        """ckzg_hip_recover_cosets_and_kzg_proofs_rows: recovery by rows at coset size l = 2^log2_coset, m = 8192 >>
+        log2_coset cosets a row.  rows is a list of (coset_indices, evals) tuples, evals being the held cosets' values back
+        to back (32 * l bytes each, in the order compute_coset_kzg_proofs_batch writes them).  Returns (evals_per_row,
+        proofs_per_row, status): a row's evaluations are one bytes object of 8192 * 32 bytes, its proofs one of m * 48;
+        status[r] is the row's C_KZG_RET (1 = C_KZG_BADARGS) and the entries of a row with a non-zero status are None, as is
+        a whole list that was not asked for."""
+        _check(want_evals or want_proofs, "no output requested")
+        _check(isinstance(log2_coset, int) and 0 <= log2_coset <= 6, "log2_coset")
+        nr, item = len(rows), 32 << log2_coset
+        start, flat_idx, flat_evals = [0], [], []
+        for row in rows:
+            _check(len(row) == 2, "a row is (coset_indices, evals)")
+            coset_indices, evals = row
+            _check(len(evals) == len(coset_indices) * item, "evals")
+            for i in coset_indices:
+                _check(isinstance(i, int) and 0 <= i < 1 << 64, "coset index")
+            flat_idx.extend(coset_indices)
+            flat_evals.append(bytes(evals))
+            start.append(start[-1] + len(coset_indices))
+        es, ps = 32 * 8192, 48 * (8192 >> log2_coset)
+        re = C.create_string_buffer(max(nr, 1) * es) if want_evals else None
+        rp = C.create_string_buffer(max(nr, 1) * ps) if want_proofs else None
+        st = (C.c_uint8 * max(nr, 1))()
+        ret = self._fn("ckzg_hip_recover_cosets_and_kzg_proofs_rows")(
+            re, rp, st, (C.c_uint64 * max(start[-1], 1))(*flat_idx), b"".join(flat_evals),
+            (C.c_uint64 * (nr + 1))(*start), C.c_uint64(nr), C.c_uint32(log2_coset), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_recover_cosets_and_kzg_proofs_rows -> C_KZG_RET %d" % ret)
+        status = [int(v) for v in st[:nr]]
+        eraw = memoryview(re) if want_evals else None
+        praw = memoryview(rp) if want_proofs else None
+        out_e = [None if status[r] else bytes(eraw[r * es:(r + 1) * es]) for r in range(nr)] if want_evals else None
+        out_p = [None if status[r] else bytes(praw[r * ps:(r + 1) * ps]) for r in range(nr)] if want_proofs else None
+        return out_e, out_p, status
+
     def verify_cell_kzg_proof_batch(self, commitments, cell_indices, cells, proofs):
         n = len(cells)
         _check(len(commitments) == n and len(cell_indices) == n and len(proofs) == n, "list lengths")

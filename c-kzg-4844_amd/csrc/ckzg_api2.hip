@@ -18,6 +18,7 @@
 #include "g1_fft_plan.hpp"
 #include "locate_plan.hpp"
 #include "recover_rows_plan.hpp"
+#include "coset_recover_plan.hpp"
 #include "slice_starts.hpp"
 
 using namespace ckzg;
@@ -1482,16 +1483,36 @@ static void vanishing_poly_from_roots(std::vector<Fr> &poly, const std::vector<F
 //     mul_z(ctx, c, d_e), mul_zinv(...)    d_e *= Z over the domain, d_e *= 1 / Z over the coset
 //     for_each_run(c, f)                   f(device row, caller row, rows) for every run of rows that goes back in one copy
 //     caller_row(c, i)                     the caller row of device row i (status)
+//     proofs_per_row(), tail_bytes()       proofs of a row (48 bytes each); the scratch of the proof tail
+//     proof_tail(ctx, c, d_e, d_img, img_final, d_proofs, d_tail)
+//                                          chunk c's proofs from its evaluations d_e (cell order) or its byte image d_img
+//                                          (img_final: it holds the recovered bytes); ends in a wait for the stream
+//     tail_times(ctx)                      the tail's share of the timing epilogue
+// The outputs are byte pointers: a row is 8192 x 32 bytes of evaluations and proofs_per_row() x 48 bytes of proofs.
 // Caller rows index recovered_cells, recovered_proofs and status as they are passed.  A row flagged in status[] holds
 // unspecified output; the return value is `result` (what the caller found before) or C_KZG_BADARGS if a row is flagged.
 constexpr size_t RECOVER_CHUNK_ROWS = 512;  // 512 rows: 128 MiB of byte image + 128 MiB of Fr + 64 MiB of coefficients
 
+// The proof tail of the two cell sources: FK20 over the fixed-base tables, 128 proofs a row
+static C_KZG_RET fk20_proof_tail(dev::DeviceCtx *ctx, size_t k, Fr *d_e, uint8_t *d_proofs, uint8_t *d_tail) {
+    const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
+    Fr *d_poly = reinterpret_cast<Fr *>(d_tail);
+    // cell order is bit-reversed evaluation order: DIT inverse gives the coefficients
+    // (poly_lagrange_to_monomial over 8192 points, eip7594.c:270); FK20 reads the low 4096
+    RC(dev::fr_ntt_batch(ctx, d_e, k, 13, false, true, true));
+    OKB(hipMemcpy2DAsync(d_poly, FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), d_e, n * sizeof(Fr),
+                         FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), k, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
+    RC(dev::fk20_proofs_device(ctx, d_proofs, d_poly, k));   // (ends in a wait for the stream)
+    return C_KZG_OK;
+}
+
 template <class Source>
-static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs, uint8_t *status,
+static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, void *recovered_cells, void *recovered_proofs, uint8_t *status,
                                 C_KZG_RET result, Source &&src) {
     if (src.chunks() == 0) return result;
     const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
     const size_t m = src.max_rows();
+    const size_t pr_row = src.proofs_per_row() * 48;
     // Batches drain their outputs (256 KB of cells + 6 KB of proofs per row) through an OutPipe: the cells
     // of a chunk cross PCIe while its proofs are computed, the proofs while the next chunk starts.  Output
     // buffers alternate between chunks.  A call with a few rows copies directly (no helper thread).
@@ -1501,14 +1522,15 @@ static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGP
     Arena &ar = ctx->api_arena;
     // image(s) + Fr + flags per row; input; the source's own; proofs
     OKM(ar.begin(m * (nbuf * n * 32 + n * sizeof(Fr) + 4) + src.in_bytes() + src.extra_bytes() +
-                 (recovered_proofs ? m * (nbuf * CELLS_PER_EXT_BLOB * 48 + FIELD_ELEMENTS_PER_BLOB * sizeof(Fr)) : 0) + 4096));
+                 (recovered_proofs ? m * nbuf * pr_row + src.tail_bytes() : 0) + 4096));
     ArenaTrim trim(ar);
     ABuf<uint8_t> d_img0(ar, m * n * 32), d_img1(ar, piped ? m * n * 32 : 1), d_in(ar, src.in_bytes());
-    ABuf<uint8_t> d_pr0(ar, recovered_proofs ? m * CELLS_PER_EXT_BLOB * 48 : 1);
-    ABuf<uint8_t> d_pr1(ar, recovered_proofs && piped ? m * CELLS_PER_EXT_BLOB * 48 : 1);
-    ABuf<Fr> d_e(ar, m * n), d_poly(ar, recovered_proofs ? m * FIELD_ELEMENTS_PER_BLOB : 1);
+    ABuf<uint8_t> d_pr0(ar, recovered_proofs ? m * pr_row : 1);
+    ABuf<uint8_t> d_pr1(ar, recovered_proofs && piped ? m * pr_row : 1);
+    ABuf<Fr> d_e(ar, m * n);
+    ABuf<uint8_t> d_tail(ar, recovered_proofs ? src.tail_bytes() : 1);
     ABuf<uint32_t> d_bad(ar, m);
-    OKM(d_img0.p && d_img1.p && d_in.p && d_pr0.p && d_pr1.p && d_e.p && d_poly.p && d_bad.p && src.take(ar));
+    OKM(d_img0.p && d_img1.p && d_in.p && d_pr0.p && d_pr1.p && d_e.p && d_tail.p && d_bad.p && src.take(ar));
     uint8_t *img_buf[2] = {d_img0.p, piped ? d_img1.p : d_img0.p}, *pr_buf[2] = {d_pr0.p, piped ? d_pr1.p : d_pr0.p};
     // the pipe's page-locked staging, taken here so that running out of it is C_KZG_MALLOC like every other allocation
     if (piped) OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, OutPipe::PIECE));
@@ -1553,14 +1575,8 @@ static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGP
         }
         if (recovered_cells) OKB(give_back(c, d_img, recovered_cells, n * 32));
         if (recovered_proofs) {
-            // cell order is bit-reversed evaluation order: DIT inverse gives the coefficients
-            // (poly_lagrange_to_monomial over 8192 points, eip7594.c:270); FK20 reads the low 4096
-            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));
-            OKB(hipMemcpy2DAsync(d_poly.p, FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), d_e.p, n * sizeof(Fr),
-                                 FIELD_ELEMENTS_PER_BLOB * sizeof(Fr), k, hipMemcpyDeviceToDevice,
-                                 ctx->stream) == hipSuccess);
-            RC(dev::fk20_proofs_device(ctx, d_proofs, d_poly.p, k));   // (ends in a wait for the stream)
-            OKB(give_back(c, d_proofs, recovered_proofs, CELLS_PER_EXT_BLOB * 48));
+            RC(src.proof_tail(ctx, c, d_e.p, d_img, recovered_cells != nullptr || src.all_full(c), d_proofs, d_tail.p));
+            OKB(give_back(c, d_proofs, recovered_proofs, pr_row));
         }
         mark.push_back(pipe.pushed_count());
     }
@@ -1570,7 +1586,7 @@ static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGP
     {   // ckzg_hip_last_kernel_ms: 3 = the device section of the call, 1 / 4 = k_msm_small / G1 FFTs of the last chunk
         float ms;
         if (hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[4]) == hipSuccess) ctx->last_ms[3] = ms;
-        if (recovered_proofs) dev::fk20_collect_times(ctx);
+        if (recovered_proofs) src.tail_times(ctx);
         (void)hipGetLastError();
     }
     return result;
@@ -1637,6 +1653,12 @@ struct RecoverSameCells {
     template <class F>
     bool for_each_run(size_t c, F &&f) const { return f((size_t)0, c * CH, rows(c)); }
     size_t caller_row(size_t c, size_t i) const { return c * CH + i; }
+    static constexpr size_t proofs_per_row() { return CELLS_PER_EXT_BLOB; }
+    size_t tail_bytes() const { return max_rows() * FIELD_ELEMENTS_PER_BLOB * sizeof(Fr); }
+    C_KZG_RET proof_tail(dev::DeviceCtx *ctx, size_t c, Fr *d_e, uint8_t *, bool, uint8_t *d_proofs, uint8_t *d_tail) {
+        return fk20_proof_tail(ctx, rows(c), d_e, d_proofs, d_tail);
+    }
+    void tail_times(dev::DeviceCtx *ctx) const { dev::fk20_collect_times(ctx); }
 };
 
 static C_KZG_RET recover_batch_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs,
@@ -1725,6 +1747,12 @@ struct RecoverByRows {
         return true;
     }
     size_t caller_row(size_t c, size_t i) const { return (size_t)(lo + plan.chunks[c].row_caller[i]); }
+    static constexpr size_t proofs_per_row() { return CELLS_PER_EXT_BLOB; }
+    size_t tail_bytes() const { return max_rows() * FIELD_ELEMENTS_PER_BLOB * sizeof(Fr); }
+    C_KZG_RET proof_tail(dev::DeviceCtx *ctx, size_t c, Fr *d_e, uint8_t *, bool, uint8_t *d_proofs, uint8_t *d_tail) {
+        return fk20_proof_tail(ctx, rows(c), d_e, d_proofs, d_tail);
+    }
+    void tail_times(dev::DeviceCtx *ctx) const { dev::fk20_collect_times(ctx); }
 };
 
 // Structurally invalid rows get C_KZG_BADARGS here and no device row: they are neither copied, computed nor written
@@ -1754,6 +1782,133 @@ extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_
         // whole rows are the unit of splitting: contiguous runs of rows per device, chunks of rows on a device
         return for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
             return recover_rows_on(ctx, recovered_cells, recovered_proofs, status, cell_indices, cells, row_start, lo, hi);
+        });
+    });
+}
+
+// The source of the call by rows at coset size l = 2^e, m = 8192 >> e cosets a row: caller rows [lo, hi) of the call on
+// one device.  RecoverByRows with the coset size a parameter (plan: coset_recover_plan.hpp; kernels: coset_recover.hip),
+// and a proof tail of its own: the proofs of a recovered row are the coset openings of its blob, the first 4096 values
+// of the row's byte image, through dev::openings_enqueue in sub-batches of CKZG_HIP_COSET_CHUNK_BLOBS rows.  No
+// fixed-base table, at e = 6 neither.
+struct RecoverCosetsByRows {
+    static constexpr size_t n = FIELD_ELEMENTS_PER_EXT_BLOB, SUB = CKZG_HIP_COSET_CHUNK_BLOBS;
+    const CosetRecoverPlan &plan;
+    const Bytes32 *evals;
+    uint64_t lo;
+    bool want_proofs;
+    ABuf<Fr> d_zdom, d_zinv;      // m factors per set
+    ABuf<uint32_t> d_meta;        // row_set [k] | coset_dst [cosets] | miss_start [sets + 1] | miss
+    std::vector<uint32_t> meta;
+
+    int e() const { return plan.e; }
+    size_t m() const { return coset_recover_cosets(plan.e); }
+    size_t item_bytes() const { return (size_t)32 << plan.e; }
+    size_t chunks() const { return plan.chunks.size(); }
+    size_t rows(size_t c) const { return plan.chunks[c].rows(); }
+    bool all_full(size_t c) const { return plan.chunks[c].all_full; }
+    size_t max_rows() const { return plan.max_rows; }
+    size_t in_bytes() const { return plan.max_cosets * item_bytes(); }
+    size_t meta_words() const { return plan.max_rows + plan.max_cosets + plan.max_sets + 1 + plan.max_miss; }
+    size_t extra_bytes() const { return meta_words() * 4 + plan.max_sets * 2 * m() * sizeof(Fr) + 3 * 256; }
+    bool take(Arena &ar) {
+        d_zdom = ABuf<Fr>(ar, plan.max_sets * m()), d_zinv = ABuf<Fr>(ar, plan.max_sets * m());
+        d_meta = ABuf<uint32_t>(ar, meta_words());
+        return d_zdom.p && d_zinv.p && d_meta.p;
+    }
+    C_KZG_RET prepare(dev::DeviceCtx *ctx) {
+        if (want_proofs) RC(dev::openings_xhat_ensure(ctx, e()));
+        return C_KZG_OK;
+    }
+    C_KZG_RET cells_in(dev::DeviceCtx *ctx, size_t c, uint8_t *d_img, uint8_t *d_in) {
+        const CosetRecoverChunk &ch = plan.chunks[c];
+        const uint32_t *d_coset_dst = d_meta.p + ch.rows(), *d_miss_start = d_coset_dst + ch.cosets();
+        const uint32_t *d_miss = d_miss_start + ch.sets() + 1;
+        meta.clear();
+        meta.insert(meta.end(), ch.row_set.begin(), ch.row_set.end());
+        meta.insert(meta.end(), ch.coset_dst.begin(), ch.coset_dst.end());
+        meta.insert(meta.end(), ch.miss_start.begin(), ch.miss_start.end());
+        meta.insert(meta.end(), ch.miss.begin(), ch.miss.end());
+        // (the stream was waited for in the chunk before, after its last use of d_meta: nothing reads it or `meta` any more)
+        OKB(hipMemcpyAsync(d_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        for (const CosetRecoverRun &run : ch.runs) {
+            OKB(hipMemcpyAsync(d_in + (size_t)run.dev_coset * item_bytes(), evals + (run.src_coset << plan.e),
+                               (size_t)run.cosets * item_bytes(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        }
+        if (!ch.all_full)
+            RC(dev::coset_recover_factors_enqueue(ctx, d_zdom.p, d_zinv.p, d_miss, d_miss_start, ch.sets(), e(),
+                                                  coset_recover_parts(ch.sets(), e())));
+        RC(dev::scatter_cosets_rows_enqueue(ctx, d_img, d_in, d_coset_dst, ch.cosets(), e()));
+        return C_KZG_OK;
+    }
+    int mul_z(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_coset_factor_enqueue(ctx, d_e, d_zdom.p, d_meta.p, rows(c), e()); }
+    int mul_zinv(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_coset_factor_enqueue(ctx, d_e, d_zinv.p, d_meta.p, rows(c), e()); }
+    template <class F>
+    bool for_each_run(size_t c, F &&f) const {
+        for (const CosetRecoverRun &run : plan.chunks[c].runs) {
+            if (!f((size_t)run.dev_row, (size_t)(lo + run.caller_row), (size_t)run.rows)) return false;
+        }
+        return true;
+    }
+    size_t caller_row(size_t c, size_t i) const { return (size_t)(lo + plan.chunks[c].row_caller[i]); }
+    size_t proofs_per_row() const { return m(); }
+    size_t sub_rows() const { return plan.max_rows < SUB ? plan.max_rows : SUB; }
+    // the blobs of a sub-batch, its flags, the scratch of the openings
+    size_t tail_bytes() const {
+        return sub_rows() * (BYTES_PER_BLOB + 4) + dev::openings_scratch_bytes(sub_rows()) + 3 * 256;
+    }
+    C_KZG_RET proof_tail(dev::DeviceCtx *ctx, size_t c, Fr *d_e, uint8_t *d_img, bool img_final, uint8_t *d_proofs,
+                         uint8_t *d_tail) {
+        const size_t k = rows(c), sub = sub_rows();
+        uint8_t *d_blobs = d_tail;
+        uint32_t *d_flags = reinterpret_cast<uint32_t *>(d_tail + (sub * BYTES_PER_BLOB + 255) / 256 * 256);
+        uint8_t *scratch = reinterpret_cast<uint8_t *>(d_flags) + (sub * 4 + 255) / 256 * 256;
+        if (!img_final) RC(dev::fr_to_bytes_batch(ctx, d_img, d_e, k * n));
+        for (size_t j = 0; j < k; j += sub) {
+            const size_t kk = k - j < sub ? k - j : sub;
+            // the blob of a row: its first 4096 values (the even natural indices, in the blob's own order)
+            OKB(hipMemcpy2DAsync(d_blobs, BYTES_PER_BLOB, d_img + j * n * 32, n * 32, BYTES_PER_BLOB, kk,
+                                 hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
+            // (a non-canonical row was flagged when its values came in; its proofs are unspecified)
+            OKB(hipMemsetAsync(d_flags, 0, kk * 4, ctx->stream) == hipSuccess);
+            RC(dev::openings_enqueue(ctx, d_proofs + j * m() * 48, nullptr, d_flags, d_blobs, kk, e(), G1_FFT_MAX_LOG - e(), scratch));
+        }
+        OKB(dev::sync_stream(ctx->stream) == hipSuccess);   // the proofs go back by copies that do not wait for the stream
+        return C_KZG_OK;
+    }
+    void tail_times(dev::DeviceCtx *) const {}
+};
+
+static_assert(CKZG_HIP_COSET_MAX_LOG2 == COSET_RECOVER_MAX_LOG, "the header and coset_recover_plan.hpp name the same largest coset");
+
+// Structurally invalid rows get C_KZG_BADARGS here and no device row: they are neither copied, computed nor written
+static C_KZG_RET recover_cosets_rows_on(dev::DeviceCtx *ctx, Bytes32 *recovered_evals, KZGProof *recovered_proofs,
+                                        uint8_t *status, const uint64_t *coset_indices, const Bytes32 *evals,
+                                        const uint64_t *row_start, uint64_t lo, uint64_t hi, int e) {
+    CosetRecoverPlan plan;
+    build_coset_recover_plan(plan, coset_indices, row_start + lo, hi - lo, e, CKZG_HIP_COSET_RECOVER_CHUNK_ROWS);
+    if (status) {
+        for (uint64_t r = lo; r < hi; r++) status[r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
+    }
+    return recover_chunks(ctx, recovered_evals, recovered_proofs, status, plan.any_invalid ? C_KZG_BADARGS : C_KZG_OK,
+                          RecoverCosetsByRows{plan, evals, lo, recovered_proofs != NULL});
+}
+
+extern "C" C_KZG_RET ckzg_hip_recover_cosets_and_kzg_proofs_rows(Bytes32 *recovered_evals, KZGProof *recovered_proofs,
+                                                                 uint8_t *status, const uint64_t *coset_indices,
+                                                                 const Bytes32 *evals, const uint64_t *row_start,
+                                                                 uint64_t num_rows, uint32_t log2_coset,
+                                                                 const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (log2_coset > CKZG_HIP_COSET_MAX_LOG2) return C_KZG_BADARGS;
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_rows == 0) return C_KZG_OK;
+        if (recovered_evals == NULL && recovered_proofs == NULL) return C_KZG_BADARGS;
+        if (!slice_starts_ok(row_start, num_rows)) return C_KZG_BADARGS;
+        if (row_start[num_rows] != 0 && (coset_indices == NULL || evals == NULL)) return C_KZG_BADARGS;
+        return for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return recover_cosets_rows_on(ctx, recovered_evals, recovered_proofs, status, coset_indices, evals, row_start,
+                                          lo, hi, (int)log2_coset);
         });
     });
 }

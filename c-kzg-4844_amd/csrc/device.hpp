@@ -596,6 +596,17 @@ int scatter_cells_rows_enqueue(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *
                                size_t ncells);
 //   a[row][p] *= f[row_set[row]][p / 64] over nrows rows of 8192
 int fr_mul_cell_factor_enqueue(DeviceCtx *ctx, Fr *d_a, const Fr *d_f, const uint32_t *d_row_set, size_t nrows);
+// coset_recover.hip: the same three at coset size 2^e, m = 8192 >> e cosets a row (ckzg_hip_recover_cosets_and_kzg_proofs_rows;
+// index maps: coset_recover_plan.hpp).  All enqueue-only, on ctx->stream.
+//   d_z_domain[s][m], d_z_coset_inv[s][m] <- Z over the domain and 1 / Z over the shifted coset of set s, per coset;
+//   d_miss[d_miss_start[s] .. d_miss_start[s + 1]): the root indices of the set's missing cosets; parts: lanes per coset
+int coset_recover_factors_enqueue(DeviceCtx *ctx, Fr *d_z_domain, Fr *d_z_coset_inv, const uint32_t *d_miss,
+                                  const uint32_t *d_miss_start, size_t nsets, int e, uint32_t parts);
+//   item i (32 << e bytes) -> image[coset_dst[i]] (coset_dst = device row * m + coset; zero-filled by the caller)
+int scatter_cosets_rows_enqueue(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *d_in, const uint32_t *d_coset_dst,
+                                size_t ncosets, int e);
+//   a[row][p] *= f[row_set[row]][p >> e] over nrows rows of 8192
+int fr_mul_coset_factor_enqueue(DeviceCtx *ctx, Fr *d_a, const Fr *d_f, const uint32_t *d_row_set, size_t nrows, int e);
 // pairing.hip: verify_kzg_proof for n independent items (ckzg_api2.hip: verify_point_proofs_on).  Enqueue-only, on
 // ctx->stream.  d_pts: commitments [0, n), proofs [n, 2n), decompressed; d_st_dec / d_st_sub: their 2n flags from
 // decompress_g1_batch_device / subgroup_g1_batch_device; d_z32 / d_y32: n x 32 big-endian bytes.  Writes the check's

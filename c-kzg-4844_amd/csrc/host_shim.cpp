@@ -784,6 +784,114 @@ extern "C" void hs_recover_set_factors(uint32_t *z_domain, uint32_t *z_coset_inv
     }
 }
 
+// ---- ckzg_hip_recover_cosets_and_kzg_proofs_rows: the same two at coset size 2^e (coset_recover_plan.hpp,
+// coset_recover_factors.hpp; tests/test_coset_recover_cpu.py).
+// Plan: as hs_recover_rows_plan, with row_mask [num_rows][m / 32], the per-coset position and scatter target, and
+// chunk_info [chunks][5] = rows, cosets, sets, all_full, entries of the missing lists.  Returns the number of chunks, -1
+// for a malformed row_start or e > 6, -2 beyond cap_chunks. ----
+#include "coset_recover_plan.hpp"
+#include "coset_recover_factors.hpp"
+extern "C" long hs_coset_recover_plan(uint8_t *valid, uint32_t *row_chunk, uint32_t *row_dev, uint32_t *row_set,
+                                      uint32_t *row_mask, uint32_t *coset_pos, uint32_t *coset_dst, uint32_t *chunk_info,
+                                      size_t cap_chunks, const uint64_t *coset_indices, const uint64_t *row_start,
+                                      uint64_t num_rows, int e, size_t chunk_rows) {
+    if (e < 0 || e > COSET_RECOVER_MAX_LOG || !slice_starts_ok(row_start, num_rows)) return -1;
+    const uint32_t W = coset_recover_mask_words(e);
+    CosetRecoverPlan p;
+    build_coset_recover_plan(p, coset_indices, row_start, num_rows, e, chunk_rows);
+    if (p.chunks.size() > cap_chunks) return -2;
+    for (uint64_t r = 0; r < num_rows; r++) {
+        valid[r] = p.valid[(size_t)r];
+        row_chunk[r] = row_dev[r] = row_set[r] = 0xffffffffu;
+        for (uint32_t w = 0; w < W; w++) row_mask[W * r + w] = 0;
+    }
+    for (uint64_t i = 0; i < row_start[num_rows]; i++) coset_pos[i] = coset_dst[i] = 0xffffffffu;
+    for (size_t c = 0; c < p.chunks.size(); c++) {
+        const CosetRecoverChunk &ch = p.chunks[c];
+        chunk_info[5 * c] = (uint32_t)ch.rows();
+        chunk_info[5 * c + 1] = (uint32_t)ch.cosets();
+        chunk_info[5 * c + 2] = (uint32_t)ch.sets();
+        chunk_info[5 * c + 3] = ch.all_full ? 1 : 0;
+        chunk_info[5 * c + 4] = (uint32_t)ch.miss.size();
+        for (size_t d = 0; d < ch.rows(); d++) {
+            const uint64_t r = ch.row_caller[d];
+            row_chunk[r] = (uint32_t)c;
+            row_dev[r] = (uint32_t)d;
+            row_set[r] = ch.row_set[d];
+            for (uint32_t w = 0; w < W; w++) row_mask[W * r + w] = ch.set_mask[(size_t)W * ch.row_set[d] + w];
+        }
+        for (const CosetRecoverRun &run : ch.runs) {
+            for (uint32_t j = 0; j < run.cosets; j++) {
+                coset_pos[run.src_coset + j] = run.dev_coset + j;
+                coset_dst[run.src_coset + j] = ch.coset_dst[run.dev_coset + j];
+            }
+        }
+    }
+    return (long)p.chunks.size();
+}
+
+// the missing list of set `set` of chunk `chunk` of the same plan, as the device gets it: the number of entries (up to
+// `cap` of them copied), -1 as above or for a chunk or set the plan does not have; runs[cap_runs][4] = caller row, device
+// row, rows, cosets of the chunk's copy runs, *num_runs how many it has
+extern "C" long hs_coset_recover_plan_set(uint32_t *miss, size_t cap, uint64_t *runs, size_t cap_runs, uint32_t *num_runs,
+                                          const uint64_t *coset_indices, const uint64_t *row_start, uint64_t num_rows, int e,
+                                          size_t chunk_rows, size_t chunk, size_t set) {
+    if (e < 0 || e > COSET_RECOVER_MAX_LOG || !slice_starts_ok(row_start, num_rows)) return -1;
+    CosetRecoverPlan p;
+    build_coset_recover_plan(p, coset_indices, row_start, num_rows, e, chunk_rows);
+    if (chunk >= p.chunks.size() || set >= p.chunks[chunk].sets()) return -1;
+    const CosetRecoverChunk &ch = p.chunks[chunk];
+    const uint32_t a = ch.miss_start[set], b = ch.miss_start[set + 1];
+    for (uint32_t i = a; i < b && i - a < cap; i++) miss[i - a] = ch.miss[i];
+    *num_runs = (uint32_t)ch.runs.size();
+    for (size_t i = 0; i < ch.runs.size() && i < cap_runs; i++) {
+        runs[4 * i] = ch.runs[i].caller_row;
+        runs[4 * i + 1] = ch.runs[i].dev_row;
+        runs[4 * i + 2] = ch.runs[i].rows;
+        runs[4 * i + 3] = ch.runs[i].cosets;
+    }
+    return (long)(b - a);
+}
+
+extern "C" uint32_t hs_coset_recover_parts(uint64_t sets, int e) { return coset_recover_parts((size_t)sets, e); }
+extern "C" uint32_t hs_coset_recover_block(int e, uint32_t parts) { return coset_recover_block(e, parts); }
+extern "C" uint32_t hs_coset_recover_slice_len(uint32_t count, uint32_t parts) { return coset_recover_slice_len(count, parts); }
+extern "C" uint32_t hs_coset_recover_slice_valid(uint32_t count, uint32_t parts, uint32_t q) {
+    return coset_recover_slice_valid(count, parts, q);
+}
+
+// The factor kernel replayed for the cosets cosets[ncosets] of ONE set, with `parts` lanes a coset: the slices of
+// coset_recover_plan.hpp, the chain of coset_recover_factors.hpp per (coset, part), the kernel's fold over the parts.
+// Field elements cross as canonical little-endian limbs: roots w^i [8193], seven_l = 7^l; miss[count] as the plan makes
+// it.  out: Z over the domain and 1 / Z over the shifted coset, [ncosets] each.
+extern "C" void hs_coset_recover_factors(uint32_t *z_domain, uint32_t *z_coset_inv, const uint32_t *miss, uint32_t count,
+                                         const uint32_t *cosets, uint32_t ncosets, int e, uint32_t parts,
+                                         const uint32_t *roots_raw, const uint32_t *seven_l_raw) {
+    std::vector<Fr> roots(8193);
+    for (size_t i = 0; i < roots.size(); i++) roots[i] = from_raw<FrParams>(roots_raw + 8 * i);
+    const Fr seven_l = from_raw<FrParams>(seven_l_raw);
+    const uint32_t len = coset_recover_slice_len(count, parts);
+    std::vector<Fr> pd(parts), pc(parts);
+    for (uint32_t i = 0; i < ncosets; i++) {
+        const Fr xd = roots[coset_recover_brp(cosets[i], e) << e], xc = mul(seven_l, xd);
+        for (uint32_t q = 0; q < parts; q++) {
+            pd[q] = pc[q] = Fr::one();
+            coset_recover_chain(pd[q], pc[q], xd, xc, len, coset_recover_slice_valid(count, parts, q), [&](uint32_t t) {
+                const uint32_t at = q * len + t;
+                return roots[at < count ? miss[at] : 0u];
+            });
+        }
+        for (uint32_t s2 = parts >> 1; s2 >= 1; s2 >>= 1) {
+            for (uint32_t q = 0; q < s2; q++) {
+                pd[q] = mul(pd[q], pd[q + s2]);
+                pc[q] = mul(pc[q], pc[q + s2]);
+            }
+        }
+        to_raw<FrParams>(z_domain + 8 * i, pd[0]);
+        to_raw<FrParams>(z_coset_inv + 8 * i, fr_inv_safegcd(pc[0]));
+    }
+}
+
 // ---- raw-limb entry points: the F28 operations at the bound combinations the group law instantiates
 // (f28_test_ops.hpp), limbs taken as they come so that a test can pass lazily reduced operands at the edge of
 // their bounds.  n items of 14 words per operand; returns 0, or 1 for an operation number past the list. ----

@@ -546,6 +546,63 @@ C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitm
                                                 const Bytes32 *evals, const Bytes48 *proofs_bytes, uint64_t num_cosets,
                                                 uint32_t log2_coset, const KZGSettings *s);
 
+/* Recovery by rows at any coset size l = 2^e, e = log2_coset <= CKZG_HIP_COSET_MAX_LOG2: a node that holds at least half
+ * of a row's cosets gets the row back, with its multiproofs -- the third leg next to
+ * ckzg_hip_compute_coset_kzg_proofs_batch and ckzg_hip_verify_coset_kzg_proof_batch.  With m = 8192 >> e, coset_indices
+ * and evals are flat, row_start has num_rows + 1 entries, starts at 0 and does not decrease, and row r is the slice
+ * [row_start[r], row_start[r + 1]) of coset_indices.  Held coset i of the flat list carries evals[i l .. i l + l - 1],
+ * the values at brp_roots_of_unity[c l .. c l + l - 1], c = coset_indices[i]: the order of the evals output of
+ * ckzg_hip_compute_coset_kzg_proofs_batch.  Outputs, either may be NULL, not both:
+ *   recovered_evals  [num_rows][8192], the row's extended evaluations in that same order; the bytes of the 128 cells of
+ *                    compute_cells_and_kzg_proofs, at every e;
+ *   recovered_proofs [num_rows][m]: recovered_proofs[m r + c] is byte for byte proofs[m b + c] of
+ *                    ckzg_hip_compute_coset_kzg_proofs_batch on the recovered blob (the row's first 4096 values).
+ * Rows and return values are those of ckzg_hip_recover_cells_and_kzg_proofs_rows with 128 replaced by m and 64 by m / 2:
+ *   - a row with fewer than m / 2 or more than m cosets, an index >= m or indices not strictly ascending has status
+ *     C_KZG_BADARGS; its output rows are not written, it costs no device work and the other rows are recovered;
+ *   - a row with a non-canonical value has status C_KZG_BADARGS and unspecified output;
+ *   - a row with all m cosets returns its values unchanged, and their proofs.
+ * Returns C_KZG_BADARGS if any row is invalid, or -- with nothing written and nothing launched -- for log2_coset > 6, a
+ * malformed row_start, both outputs NULL, or NULL inputs with work to do; C_KZG_OK otherwise (also for num_rows == 0);
+ * C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  With several devices, contiguous runs of whole rows go to each.
+ * At e = 6 the call is byte for byte ckzg_hip_recover_cells_and_kzg_proofs_rows, status included; it gets there through
+ * its own factor kernel and through the coset openings, not through the FK20 tables.
+ * How: the transform sequence of recovery does not depend on e and is shared with the two cell calls; what depends on e
+ * is the vanishing polynomial of the missing set, constant over a coset: 2 m values per DISTINCT set of a chunk (a hash
+ * over the m-bit masks on the host), each a product of up to m / 2 factors, evaluated directly on the GPU
+ * (coset_recover.hip: O(m^2) products per distinct set, 67 M at e = 0, split over several lanes per coset where the sets
+ * of a chunk do not fill the chip).  The subquadratic route (a product tree for the coefficients of Z and two
+ * transforms) is not built.  Rows are processed in chunks of CKZG_HIP_COSET_RECOVER_CHUNK_ROWS: 32 MiB of byte image
+ * (64 MiB from 9 rows on, two alternating) + 32 MiB of field elements, at most 64 MiB of factors (e = 0, 128 distinct
+ * sets: 512 KB a set; 8 KB a set at e = 6) and, with proofs, 2 x 48 MiB of proofs at e = 0 plus the openings' scratch
+ * for CKZG_HIP_COSET_CHUNK_BLOBS rows (5.4 MB of HBM a row).
+ * NOT here: device pointers, and a fixed-base-table route for the proofs -- they are the coset openings of the recovered
+ * blob at every e, one extra transform to bytes and back a row.
+ * Measured (profiles/coset_recover_bench.json): medians of 20 (of 5 where a call takes more than 0.4 s) and minima of
+ * the wall time, default tables, a fresh process, rows of 8 blobs that hold m / 2 + 3 cosets each.
+ *   e = 6  evaluations only: 0.89 (min 0.88) ms for 16 rows of one set, 3.43 (3.35) / 3.53 (3.43) / 3.72 (3.60) ms for 256
+ *          rows of 1 / 16 / 256 distinct sets, against 0.98 (0.94) and 3.96 (3.86) / 3.89 (3.84) / 3.96 (3.88) ms for
+ *          ckzg_hip_recover_cells_and_kzg_proofs_rows on the same rows (a build of the parent commit in the same
+ *          process): this call's median is below that call's minimum in all five shapes, by 4 to 11 %.  With proofs:
+ *          19.9 (19.6) ms for 16 rows and 308.6 (307.0) ms for 256 against 5.07 (4.98) and 24.2 (23.5) ms: this call is
+ *          NOT faster, it is 4x and 13x slower -- that call's proofs are FK20 over the fixed-base tables, this call's
+ *          are ladders.  Use ckzg_hip_recover_cells_and_kzg_proofs_rows for cells of 64 with proofs.
+ *   e = 0 .. 5 have no alternative in the library.  Evaluations only, 256 rows of 1 / 16 / 256 distinct sets:
+ *          e = 0  8.2 / 39.6 / 227.8 ms, e = 1  5.3 / 14.9 / 65.9, e = 2  3.9 / 6.7 / 22.0, e = 3  3.7 / 4.3 / 9.0,
+ *          e = 4  3.5 / 3.6 / 5.4, e = 5  3.4 / 3.5 / 4.0; 16 rows of 1 / 16 sets: e = 0  2.4 / 16.9, e = 1  1.26 / 6.25,
+ *          e = 2  0.96 / 2.31, e = 3  0.96 / 1.21, e = 4  0.92 / 0.95, e = 5  0.89 / 0.91.  With proofs the openings are the
+ *          cost, whatever the sets: 256 rows of one set 1,585 / 876 / 728 / 466 / 396 / 340 ms at e = 0 .. 5 (6.2 / 3.4 /
+ *          2.8 / 1.8 / 1.5 / 1.3 ms a row), 16 rows 101 / 56 / 46 / 30 / 25 / 22 ms.
+ *   The factor kernel, from one kernel trace: e = 0  1.46 ms for one set (8 lanes a coset; 9.82 ms with one lane a
+ *          coset, so the split is kept), 16.5 ms for 16 sets, 206.5 ms for 256 = 0.81 ms a set on a full chip -- nine
+ *          tenths of the evaluations-only call with 256 distinct sets, which is where the product-tree route would pay;
+ *          e = 3  0.14 / 0.40 / 4.30 ms; e = 6  0.12 / 0.12 / 0.13 ms. */
+#define CKZG_HIP_COSET_RECOVER_CHUNK_ROWS 128
+C_KZG_RET ckzg_hip_recover_cosets_and_kzg_proofs_rows(Bytes32 *recovered_evals, KZGProof *recovered_proofs, uint8_t *status,
+                                                      const uint64_t *coset_indices, const Bytes32 *evals,
+                                                      const uint64_t *row_start, uint64_t num_rows, uint32_t log2_coset,
+                                                      const KZGSettings *s);
+
 /* Timing hook for bench.py: elapsed milliseconds of the named kernel family inside the last
  * batch call, measured with hipEvents on the stream the kernels were launched on (for a call that was
  * processed in several chunks: the last chunk).
