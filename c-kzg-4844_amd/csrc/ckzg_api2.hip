@@ -1957,39 +1957,86 @@ extern "C" C_KZG_RET recover_cells_and_kzg_proofs(Cell *recovered_cells, KZGProo
 // EIP-7594: cell proof batch verification
 // ------------------------------------------------------------------------------------------
 
+constexpr int CELL_LOG = 6;   // a Cell is a coset of 2^6 values
+static_assert((1 << CELL_LOG) == FIELD_ELEMENTS_PER_CELL && CELL_LOG <= COSET_MAX_LOG, "cells are cosets of 64");
+
 extern "C" C_KZG_RET compute_verify_cell_kzg_proof_batch_challenge(
     fr_t *challenge_out, const Bytes48 *commitments_bytes, uint64_t num_commitments,
     const uint64_t *commitment_indices, const uint64_t *cell_indices, const Cell *cells,
     const Bytes48 *proofs_bytes, uint64_t num_cells) {
-    // eip7594.c:390-482
-    Sha256 h;
-    uint8_t head[48], idx[16], digest[32];
-    memcpy(head, "RCKZGCBATCH__V1_", 16);
-    be64(head + 16, FIELD_ELEMENTS_PER_BLOB);
-    be64(head + 24, FIELD_ELEMENTS_PER_CELL);
-    be64(head + 32, num_commitments);
-    be64(head + 40, num_cells);
-    h.update(head, 48);
-    for (uint64_t i = 0; i < num_commitments; i++) h.update(commitments_bytes[i].bytes, 48);
-    for (uint64_t i = 0; i < num_cells; i++) {
-        be64(idx, commitment_indices[i]);
-        be64(idx + 8, cell_indices[i]);
-        h.update(idx, 16);
-        h.update(cells[i].bytes, BYTES_PER_CELL);
-        h.update(proofs_bytes[i].bytes, 48);
-    }
-    h.finish(digest);
+    // eip7594.c:390-482: the transcript of a coset batch (coset_verify_plan.hpp) at cosets of 64
+    static_assert(sizeof(Bytes48) == 48 && sizeof(Cell) == 32 << CELL_LOG && FIELD_ELEMENTS_PER_BLOB == 4096, "the digest's strides");
+    uint8_t digest[32];
+    coset_verify_digest<Sha256>(digest, reinterpret_cast<const uint8_t *>(commitments_bytes), num_commitments, commitment_indices,
+                                cell_indices, reinterpret_cast<const uint8_t *>(cells), reinterpret_cast<const uint8_t *>(proofs_bytes),
+                                num_cells, CELL_LOG);
     *as_fr(challenge_out) = fr_from_bytes_reduce(digest);
     return C_KZG_OK;
 }
 
-static C_KZG_RET verify_cells_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *commitments_bytes,
-                                 const uint64_t *cell_indices, const Cell *cells, const Bytes48 *proofs_bytes,
-                                 uint64_t num_cells, const KZGSettings *s) {
+// ------------------------------------------------------------------------------------------
+// The cell check (eip7594.c:825-974) at every coset size l = 2^e, e <= 6, once: verify_cell_kzg_proof_batch and its
+// callers by groups run it at e = 6 (a Cell is 64 values), ckzg_hip_verify_coset_kzg_proof_batch at its e.  Device
+// stages: coset_verify.hip, index maps: coset_verify_plan.hpp.  DESIGN.md section 3i.
+// ------------------------------------------------------------------------------------------
+
+// The transcript hash of a batch as a job of the worker pool
+struct HashJob {
+    std::atomic<uint32_t> running{0};   // futex word
+    bool submitted = false;
+    template <class F>
+    void submit(F hash_all) {
+        running.store(1, std::memory_order_relaxed);
+        submitted = WorkerPool::get().submit([hash_all, this]() {
+            hash_all();
+            running.store(0, std::memory_order_release);
+            futex_wake(&running, INT_MAX);
+        });
+    }
+    void wait() {
+        if (submitted) wait_host_work_done(&running, "batch transcript hash job");
+    }
+    ~HashJob() { wait(); }   // nothing the worker reads or writes may die before it is through
+};
+
+// Call-time table (msm.hip), as in verify_blobs_core: the transcript of a batch is ONE SHA-256 stream over every value
+// (1 us per cell on a SHA-NI core) during which the GPU has nothing to do once the points are decompressed -- time
+// enough to build a 6-bit fixed-base table (accumulator form, ~1.2 ms of latency + 0.15 us per point) over the batch's
+// proofs, its distinct commitments and the l setup points of the interpolation commitment, so that the four sums that
+// follow the challenge are table sums (0.45 ms) instead of ladders (1.0-2.2 ms).  Measured at l = 64 with the table
+// off / on (tools/bench_verify_cells.py, same box, profiles/r03_verify_x28_sweep.txt): n = 1024 3.20 -> 2.88 ms,
+// 2048 4.56 -> 3.20, 4096 7.54 -> 5.50, 6144 9.81 -> 7.67, and n = 128 2.38 -> 2.31, 256 2.42 -> 2.32, 384 2.55 -> 2.36,
+// 768 2.91 -> 2.49; below a blob's worth of cells the two forms tie at the 2.3 ms latency floor of the call: from 128
+// items upwards.  At l = 64 only: the threshold has not been measured at smaller cosets, which take the ladders.
+static int verify_call_table_wbits() {
+    static const int wbits = (int)dev::ab_knob("CKZG_HIP_VERIFY_TABLE_WBITS", 6);
+    return wbits;
+}
+static bool verify_cosets_wants_table(size_t n, int e) {
+    static const size_t table_min = (size_t)dev::ab_knob("CKZG_HIP_VERIFY_CELL_TABLE_MIN", 128);
+    const int wbits = verify_call_table_wbits();
+    return e == CELL_LOG && g_verify_call_table.load(std::memory_order_relaxed) != 0 && wbits >= 4 && wbits <= 10 &&
+           n >= table_min;
+}
+
+// What verify_cosets_on takes from the arena: n items of nc distinct commitments, with the call-time table (tbl: its
+// geometry over n + nc + l points) or without
+static size_t verify_cosets_arena_bytes(size_t n, size_t nc, int e, bool use_table, const dev::FixedBaseTable &tbl) {
+    const size_t l = (size_t)1 << e, m = coset_verify_cosets(e), npts = n + nc + (use_table ? l : 0);
+    const size_t scalars = use_table ? 4 * npts : 2 * n + nc + l;   // the table's 4 x npts matrix, or the four vectors
+    return (n + nc) * (48 + 2) + npts * sizeof(G1Affine) + n * l * (32 + sizeof(Fr)) +
+           (n + COSET_VERIFY_EXT + COSET_INTERP_BLOCKS * l) * sizeof(Fr) + scalars * 32 + (n + m + 1 + n + 2 * n + nc + 1) * 4 +
+           (use_table ? dev::call_table_bytes(tbl) + dev::call_table_tmp_bytes(tbl) + dev::table_sums_scratch_bytes(tbl, 4) + 4 * sizeof(G1XYZZ) : 0) +
+           4096;
+}
+
+static C_KZG_RET verify_cosets_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *commitments_bytes,
+                                  const uint64_t *coset_indices, const Bytes32 *evals, const Bytes48 *proofs_bytes,
+                                  uint64_t num_cosets, int e, const KZGSettings *s) {
     *ok = false;
-    const size_t n = num_cells, l = FIELD_ELEMENTS_PER_CELL;
-    Trace tr("verify_cells");
-    const Fr *rou = as_fr(s->roots_of_unity);
+    const size_t n = num_cosets, l = (size_t)1 << e, m = coset_verify_cosets(e);
+    if (n >= ((size_t)1 << 24)) return C_KZG_ERROR;   // (the lane index of a power of r has 24 bits: coset_rlc_scalars_enqueue)
+    Trace tr(e == CELL_LOG ? "verify_cells" : "verify_cosets");
     // deduplicate commitments (eip7594.c:345-376)
     std::vector<Bytes48> uniq;
     std::vector<uint64_t> cidx(n);
@@ -2002,94 +2049,64 @@ static C_KZG_RET verify_cells_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *c
         cidx[i] = j;
     }
     const size_t nc = uniq.size();
-    // Call-time table (msm.hip), as in verify_blobs_core: the transcript of a cell batch is ONE SHA-256 stream over
-    // every cell (1 us per cell on a SHA-NI core) during which the GPU has nothing to do once the points are
-    // decompressed -- time enough to build a 6-bit fixed-base table (accumulator form, ~1.2 ms of latency + 0.15 us per
-    // point) over the batch's proofs, its distinct commitments and the 64 setup points of the interpolation
-    // commitment, so that the four sums that follow the challenge are table sums (0.45 ms) instead of ladders
-    // (1.0-2.2 ms).  Measured with the table off / on (tools/bench_verify_cells.py, same box,
-    // profiles/r03_verify_x28_sweep.txt): n = 1024 3.20 -> 2.88 ms, 2048 4.56 -> 3.20, 4096 7.54 -> 5.50,
-    // 6144 9.81 -> 7.67, and n = 128 2.38 -> 2.31, 256 2.42 -> 2.32, 384 2.55 -> 2.36, 768 2.91 -> 2.49; below a
-    // blob's worth of cells the two forms tie at the 2.3 ms latency floor of the call: from 128 cells upwards.
-    static const int call_table_wbits = (int)dev::ab_knob("CKZG_HIP_VERIFY_TABLE_WBITS", 6);
-    static const size_t cell_table_min = (size_t)dev::ab_knob("CKZG_HIP_VERIFY_CELL_TABLE_MIN", 128);
-    bool use_table = g_verify_call_table.load(std::memory_order_relaxed) != 0 && call_table_wbits >= 4 && call_table_wbits <= 10 &&
-                     n >= cell_table_min;
-    size_t npts = n + nc + (use_table ? l : 0);   // proofs, distinct commitments [, g1_values_monomial[0..63]]
+    bool use_table = verify_cosets_wants_table(n, e);
     dev::FixedBaseTable tbl;
-    size_t tbl_bytes = 0, tbl_tmp = 0, sums_scratch = 0;
     Arena &ar = ctx->api_arena;
-    const size_t plain_bytes = (n + nc + l) * (48 + 2 + sizeof(G1Affine)) + ((size_t)CELLS_PER_EXT_BLOB * l + l + n * l + n) * sizeof(Fr) +
-                               n * BYTES_PER_CELL + (n + CELLS_PER_EXT_BLOB + 1 + n) * 4 + 4096;
     if (use_table) {
-        dev::call_table_geometry(&tbl, (int)npts, call_table_wbits);
-        tbl_bytes = dev::call_table_bytes(tbl);
-        tbl_tmp = dev::call_table_tmp_bytes(tbl);
-        sums_scratch = dev::table_sums_scratch_bytes(tbl, 4);
+        dev::call_table_geometry(&tbl, (int)(n + nc + l), verify_call_table_wbits());
         // the table is an optimisation: a device too full for it still verifies, by ladders
-        if (!ar.begin(plain_bytes + tbl_bytes + tbl_tmp + sums_scratch + 4 * npts * 32 + (2 * n + nc + 1) * 4 + 4096)) {
-            use_table = false;
-            tbl_bytes = tbl_tmp = sums_scratch = 0;
-            npts = n + nc;
-        }
+        use_table = ar.begin(verify_cosets_arena_bytes(n, nc, e, true, tbl));
     }
-    if (!use_table) OKM(ar.begin(plain_bytes));
-    ABuf<uint8_t> d_ptb(ar, (n + nc) * 48), d_st(ar, n + nc), d_st2(ar, n + nc), d_cells(ar, n * BYTES_PER_CELL);
+    if (!use_table) OKM(ar.begin(verify_cosets_arena_bytes(n, nc, e, false, tbl)));
+    const size_t npts = n + nc + (use_table ? l : 0);   // proofs, distinct commitments [, g1_values_monomial[0 .. l - 1]]
+    ABuf<uint8_t> d_ptb(ar, (n + nc) * 48), d_st(ar, n + nc), d_st2(ar, n + nc), d_ev(ar, n * l * 32);
     ABuf<G1Affine> d_pts(ar, npts);
-    ABuf<uint8_t> d_tbl(ar, use_table ? tbl_bytes : 1), d_tbl_tmp(ar, use_table ? tbl_tmp : 1), d_sums_scr(ar, use_table ? sums_scratch : 1);
-    ABuf<uint32_t> d_sc(ar, use_table ? 4 * npts * 8 : 1);
-    ABuf<uint32_t> d_grp(ar, use_table ? 2 * n + nc + 1 : 1);   // column of each cell [n] | commitment groups: start [nc + 1], members [n]
-    ABuf<G1XYZZ> d_sums(ar, 4);
-    OKM(d_tbl.p && d_tbl_tmp.p && d_sums_scr.p && d_sc.p && d_grp.p && d_sums.p);
-    ABuf<Fr> d_agg(ar, (size_t)CELLS_PER_EXT_BLOB * l), d_interp(ar, l), d_cellfr(ar, n * l), d_rp(ar, n);
-    ABuf<uint32_t> d_bad(ar, n), d_csr(ar, CELLS_PER_EXT_BLOB + 1 + n);
-    OKM(d_ptb.p && d_st.p && d_st2.p && d_cells.p && d_pts.p && d_agg.p && d_interp.p && d_cellfr.p && d_rp.p &&
-        d_bad.p && d_csr.p);
+    ABuf<uint8_t> d_tbl(ar, use_table ? dev::call_table_bytes(tbl) : 1), d_tbl_tmp(ar, use_table ? dev::call_table_tmp_bytes(tbl) : 1),
+        d_sums_scr(ar, use_table ? dev::table_sums_scratch_bytes(tbl, 4) : 1);
+    ABuf<G1XYZZ> d_sums(ar, use_table ? 4 : 1);
+    ABuf<Fr> d_agg(ar, COSET_VERIFY_EXT), d_partial(ar, COSET_INTERP_BLOCKS * l), d_evfr(ar, n * l), d_rp(ar, n);
+    ABuf<uint32_t> d_sc(ar, (use_table ? 4 * npts : 2 * n + nc + l) * 8);
+    ABuf<uint32_t> d_bad(ar, n), d_csr(ar, m + 1 + n);
+    ABuf<uint32_t> d_grp(ar, 2 * n + nc + 1);   // coset of each item [n] | commitment groups: start [nc + 1], members [n]
+    OKM(d_ptb.p && d_st.p && d_st2.p && d_ev.p && d_pts.p && d_tbl.p && d_tbl_tmp.p && d_sums_scr.p && d_sums.p && d_agg.p &&
+        d_partial.p && d_evfr.p && d_rp.p && d_sc.p && d_bad.p && d_csr.p && d_grp.p);
+    // The scalars of the four sums, 8 words each: r^i on the proofs, the weights on the distinct commitments, r^i x_c^l on
+    // the proofs, the interpolation coefficients on the setup points.  With the table: rows 0 .. 3 of its 4 x npts
+    // matrix, zero where a point has no part in a sum; without: four vectors back to back.
+    const size_t row = npts * 8;
+    uint32_t *const v_rp = d_sc.p, *const v_w = use_table ? d_sc.p + row + n * 8 : d_sc.p + 2 * n * 8,
+                    *const v_wrp = use_table ? d_sc.p + 2 * row : d_sc.p + n * 8,
+                    *const v_interp = use_table ? d_sc.p + 3 * row + (n + nc) * 8 : d_sc.p + (2 * n + nc) * 8;
     ArenaTrim trim(ar);
     tr.mark("dedup");
-    // The transcript is ONE SHA-256 stream over every cell (eip7594.c:390-482): the longest thing in this call, on one
-    // host core.  It starts now, on a worker thread, and everything below that does not need the challenge -- the
-    // copies (blocking, from pageable memory), the GPU validation, the grouping of cells by column and by commitment,
-    // the check of the validation flags -- happens underneath it.
+    // The transcript is ONE SHA-256 stream over every value (eip7594.c:390-482): the longest thing in this call, on one
+    // host core.  From COSET_VERIFY_HASH_ON_POOL_FROM items on it starts now, on a worker thread, and everything below
+    // that does not need the challenge -- the copies (blocking, from pageable memory), the GPU validation, the grouping
+    // of the items by coset and by commitment, with the table the check of the validation flags -- happens underneath it.
     Fr r;
-    struct HashJob {
-        std::atomic<uint32_t> running{0};   // futex word
-        bool submitted = false;
-        void wait() {
-            if (submitted) wait_host_work_done(&running, "cell transcript hash job");
-        }
-        ~HashJob() { wait(); }   // nothing the worker reads or writes may die before it is through
-    } hash_job;
+    HashJob hash_job;
     const uint64_t *cidx_p = cidx.data();
     const Bytes48 *uniq_p = uniq.data();
-    auto hash_all = [&r, uniq_p, nc, cidx_p, cell_indices, cells, proofs_bytes, n]() {
-        compute_verify_cell_kzg_proof_batch_challenge((fr_t *)&r, uniq_p, nc, cidx_p, cell_indices, cells, proofs_bytes, n);
+    auto hash_all = [&r, uniq_p, nc, cidx_p, coset_indices, evals, proofs_bytes, n, e]() {
+        uint8_t digest[32];
+        coset_verify_digest<Sha256>(digest, uniq_p->bytes, nc, cidx_p, coset_indices, evals->bytes, proofs_bytes->bytes, n, e);
+        r = fr_from_bytes_reduce(digest);
     };
-    if (n >= 256) {
-        HashJob *hj = &hash_job;
-        hash_job.running.store(1, std::memory_order_relaxed);
-        hash_job.submitted = WorkerPool::get().submit([hash_all, hj]() {
-            hash_all();
-            hj->running.store(0, std::memory_order_release);
-            futex_wake(&hj->running, INT_MAX);
-        });
-    }
+    if (n >= COSET_VERIFY_HASH_ON_POOL_FROM) hash_job.submit(hash_all);
     OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, 2 * (n + nc) + n * 4));
     uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[0]), *h_st2 = h_st + (n + nc);
     uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
-    // proofs [0,n), unique commitments [n, n+nc): decompression and subgroup checks start on the GPU,
-    // followed by the cells' bytes -> Fr conversion, while the transcript is being hashed
-    // (all copies from pageable memory first: such a copy returns only when it is done, so it must not
-    // queue behind the validation kernel)
+    // proofs [0, n), distinct commitments [n, n + nc): all copies from pageable memory first (such a copy returns only
+    // when it is done, so it must not queue behind a kernel), then values -> Fr and the decompression
     OKB(hipMemcpyAsync(d_ptb.p, proofs_bytes, n * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     OKB(hipMemcpyAsync(d_ptb.p + n * 48, uniq.data(), nc * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemcpyAsync(d_cells.p, cells, n * BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_ev.p, evals, n * l * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     OKB(hipMemsetAsync(d_bad.p, 0, n * 4, ctx->stream) == hipSuccess);
-    RC(dev::bytes_to_fr_batch(ctx, d_cellfr.p, d_bad.p, d_cells.p, n * l, (uint32_t)l));
+    RC(dev::bytes_to_fr_batch(ctx, d_evfr.p, d_bad.p, d_ev.p, n * l, (uint32_t)l));
     OKB(hipMemcpyAsync(h_bad, d_bad.p, n * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-    // Validation in two launches: decompression (a square root, ~0.35 ms) here, the subgroup test
-    // (~1 ms of dependent doublings) on the second stream, next to the table build that already uses the points.
-    // A point outside the subgroup makes table and sums meaningless, not unsafe; the call ends in BADARGS below.
+    // Validation in two launches: decompression (a square root, ~0.35 ms) here, the subgroup test (~1 ms of dependent
+    // doublings) on the second stream, next to the table build that already uses the points and to everything below.
+    // A point outside the subgroup makes table and sums meaningless, not unsafe; the call ends in BADARGS.
     RC(dev::decompress_g1_batch_device(ctx, d_pts.p, d_st.p, d_ptb.p, n + nc));
     OKB(hipMemcpyAsync(h_st, d_st.p, n + nc, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
     if (use_table)
@@ -2110,230 +2127,6 @@ static C_KZG_RET verify_cells_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *c
         OKB(hipEventRecord(ctx->table_ev, ctx->aux_stream) == hipSuccess);
     }
     StreamDrain drain_aux{use_table ? ctx->aux_stream : nullptr};
-    // cells grouped by column (counting sort) for the aggregation kernel
-    std::vector<uint32_t> csr(CELLS_PER_EXT_BLOB + 1 + n, 0);
-    for (size_t i = 0; i < n; i++) csr[cell_indices[i] + 1]++;
-    for (size_t c = 0; c < CELLS_PER_EXT_BLOB; c++) csr[c + 1] += csr[c];
-    {
-        std::vector<uint32_t> fill(csr.begin(), csr.begin() + CELLS_PER_EXT_BLOB);
-        for (size_t i = 0; i < n; i++) csr[CELLS_PER_EXT_BLOB + 1 + fill[cell_indices[i]]++] = (uint32_t)i;
-    }
-    OKB(hipMemcpyAsync(d_csr.p, csr.data(), csr.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    if (use_table) {
-        // ... and by commitment, for the weights; the column of each cell, for its coset factor (k_cell_rlc_scalars)
-        std::vector<uint32_t> grp(2 * n + nc + 1, 0);
-        uint32_t *col = grp.data(), *start = grp.data() + n, *members = grp.data() + n + nc + 1;
-        for (size_t i = 0; i < n; i++) {
-            col[i] = (uint32_t)cell_indices[i];
-            start[cidx[i] + 1]++;
-        }
-        for (size_t j = 0; j < nc; j++) start[j + 1] += start[j];
-        std::vector<uint32_t> fill(start, start + nc);
-        for (size_t i = 0; i < n; i++) members[fill[cidx[i]]++] = (uint32_t)i;
-        OKB(hipMemcpyAsync(d_grp.p, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-        OKB(hipMemsetAsync(d_sc.p, 0, 4 * npts * 32, ctx->stream) == hipSuccess);
-    }
-    // The validation flags.  A large batch: both streams are through long before the transcript is, so they are
-    // checked here, underneath it.  A small one (ladder sums): the subgroup test (~1 ms of dependent doublings) keeps
-    // running on the second stream next to the sums, and the flags are checked after those.
-    auto flags_ok = [&]() -> C_KZG_RET {
-        OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
-        for (size_t i = 0; i < n + nc; i++) {
-            if (h_st[i] || h_st2[i]) return C_KZG_BADARGS;  // bad encoding / off the curve / outside G1
-        }
-        for (size_t i = 0; i < n; i++) {
-            if (h_bad[i]) return C_KZG_BADARGS;  // a non-canonical field element in a cell (bytes.c:67)
-        }
-        return C_KZG_OK;
-    };
-    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
-    if (use_table) RC(flags_ok());
-    tr.mark("copies, validation, grouping (underneath the transcript hash)");
-    if (hash_job.submitted)
-        hash_job.wait();
-    else
-        hash_all();
-    tr.mark("transcript hash");
-    const size_t row = npts * 8;   // words per scalar vector of the table path
-    std::vector<RawScalar> rp_raw, wrp_raw, wts_raw;
-    if (use_table) {
-        // scalars made on the GPU from r: [proofs | distinct commitments | 64 monomial setup points] x 4 vectors
-        RC(dev::cell_rlc_scalars_enqueue(ctx, d_rp.p, d_sc.p + 0 * row, d_sc.p + 2 * row, d_sc.p + 1 * row + n * 8, d_grp.p,
-                                         d_grp.p + n, d_grp.p + n + nc + 1, r, n, nc));
-    } else {
-        std::vector<Fr> rp(n);
-        {
-            Fr pw = Fr::one();
-            for (size_t i = 0; i < n; i++) {
-                rp[i] = pw;
-                pw = mul(pw, r);
-            }
-        }
-        rp_raw.resize(n);
-        wrp_raw.resize(n);
-        wts_raw.resize(nc);
-        std::vector<Fr> wts(nc, Fr::zero());
-        for (size_t i = 0; i < n; i++) {
-            rp_raw[i] = raw_of(rp[i]);
-            wts[cidx[i]] = add(wts[cidx[i]], rp[i]);
-            size_t rb = reverse_bits_limited(CELLS_PER_EXT_BLOB, cell_indices[i]);
-            wrp_raw[i] = raw_of(mul(rp[i], rou[rb * l]));  // r^i * h_k^64 (eip7594.c:784-812)
-        }
-        for (size_t j = 0; j < nc; j++) wts_raw[j] = raw_of(wts[j]);
-        OKB(d_rp.up(rp.data(), n));
-    }
-    tr.mark("powers of r + weights");
-    // aggregated column data: sum of r^i * cell_i per column (eip7594.c:661-683)
-    RC(dev::cell_aggregate_device(ctx, d_agg.p, d_cellfr.p, d_rp.p, d_csr.p, d_csr.p + CELLS_PER_EXT_BLOB + 1, n));
-    // per column: cell data is in bit-reversed order -> DIT inverse NTT(64) gives the interpolation
-    // polynomial over the coset; unused columns are all-zero and stay zero
-    RC(dev::fr_ntt_batch(ctx, d_agg.p, CELLS_PER_EXT_BLOB, 6, false, true, true));
-    RC(dev::interp_sum_device(ctx, d_interp.p, d_agg.p));
-    // all four lincombs (eip7594.c:926, :530, :807 and the commitment to the aggregated interpolation
-    // polynomial over the first 64 monomial setup points, :758) in one launch
-    G1Jac lc[4];
-    if (use_table) {
-        OKB(hipMemcpyAsync(d_sc.p + 3 * row + (n + nc) * 8, d_interp.p, l * 32, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
-        OKB(hipStreamWaitEvent(ctx->stream, ctx->table_ev, 0) == hipSuccess);   // the table is complete
-        RC(dev::table_sums_enqueue(ctx->stream, tbl, d_sums.p, d_sc.p, 4, d_sums_scr.p));
-        G1XYZZ hs[4];
-        OKB(d_sums.down(hs, 4));
-        for (int j = 0; j < 4; j++) lc[j] = jac_from_xyzz(hs[j]);
-    } else {
-        LincombJob jobs[4] = {{d_pts.p, &rp_raw}, {d_pts.p + n, &wts_raw}, {d_pts.p, &wrp_raw},
-                              {ctx->d_mono, nullptr, (const RawScalar *)d_interp.p, l}};
-        C_KZG_RET ret = gpu_lincomb_multi(ctx, lc, jobs, 4);
-        if (ret != C_KZG_OK) return ret;
-        RC(flags_ok());   // a point outside G1 makes the sums above meaningless, not unsafe: discarded
-    }
-    tr.mark("aggregation + IFFTs + four lincombs");
-    const G1Jac &proof_lc = lc[0], &csum = lc[1], &wsum = lc[2], &interp_commit = lc[3];
-    G1Jac final_sum = jac_add(jac_add(csum, jac_neg(interp_commit)), wsum);
-    // e(final_sum, G2) == e(proof_lc, [s^64]G2)
-    *ok = pairing_product_is_one(jac_to_affine_fast(final_sum), prepared_of(ctx)->gen, jac_to_affine_fast(jac_neg(proof_lc)),
-                                 prepared_of(ctx)->s64);
-    tr.mark("pairing check");
-    return C_KZG_OK;
-}
-
-extern "C" C_KZG_RET verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes,
-                                                 const uint64_t *cell_indices, const Cell *cells,
-                                                 const Bytes48 *proofs_bytes, uint64_t num_cells,
-                                                 const KZGSettings *s) {
-    // eip7594.c:825-974
-    return guarded([&]() -> C_KZG_RET {
-        *ok = false;
-        if (num_cells == 0) {
-            *ok = true;
-            return C_KZG_OK;
-        }
-        for (size_t i = 0; i < num_cells; i++) {
-            if (cell_indices[i] >= CELLS_PER_EXT_BLOB) return C_KZG_BADARGS;
-        }
-        if (!settings_of(s)) return C_KZG_ERROR;
-        // several devices: contiguous shards of cells, each with its own challenge and pairing check, AND-ed
-        std::atomic<int> all_ok(1);
-        C_KZG_RET ret = for_each_device_shard(s, num_cells, 2048, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
-            bool res = false;
-            C_KZG_RET r = verify_cells_on(ctx, &res, commitments_bytes + lo, cell_indices + lo, cells + lo,
-                                          proofs_bytes + lo, hi - lo, s);
-            if (r == C_KZG_OK && !res) all_ok.store(0);
-            return r;
-        });
-        if (ret == C_KZG_OK) *ok = all_ok.load() != 0;
-        return ret;
-    });
-}
-
-// ------------------------------------------------------------------------------------------
-// Coset multiproof batch verification at every coset size l = 2^e, e <= 6 (ckzg_hip_verify_coset_kzg_proof_batch): the
-// cell check above with 64 replaced by l -- its own device stages (coset_verify.hip, index maps in
-// coset_verify_plan.hpp), the shared validation, sums and pairing.  DESIGN.md section 3i.
-// ------------------------------------------------------------------------------------------
-
-static C_KZG_RET verify_cosets_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *commitments_bytes,
-                                  const uint64_t *coset_indices, const Bytes32 *evals, const Bytes48 *proofs_bytes,
-                                  uint64_t num_cosets, int e, const KZGSettings *s) {
-    *ok = false;
-    const size_t n = num_cosets, l = (size_t)1 << e, m = coset_verify_cosets(e);
-    if (n >= ((size_t)1 << 24)) return C_KZG_ERROR;   // (the lane index of a power of r has 24 bits: coset_rlc_scalars_enqueue)
-    Trace tr("verify_cosets");
-    // deduplicate commitments (eip7594.c:345-376)
-    std::vector<Bytes48> uniq;
-    std::vector<uint64_t> cidx(n);
-    for (size_t i = 0; i < n; i++) {
-        size_t j;
-        for (j = 0; j < uniq.size(); j++) {
-            if (memcmp(uniq[j].bytes, commitments_bytes[i].bytes, 48) == 0) break;
-        }
-        if (j == uniq.size()) uniq.push_back(commitments_bytes[i]);
-        cidx[i] = j;
-    }
-    const size_t nc = uniq.size();
-    Arena &ar = ctx->api_arena;
-    OKM(ar.begin((n + nc) * (48 + 2 + sizeof(G1Affine)) + n * l * (32 + sizeof(Fr)) +
-                 (n + COSET_VERIFY_EXT + COSET_INTERP_BLOCKS * l + l) * sizeof(Fr) + (2 * n + nc) * 32 +
-                 (n + m + 1 + n + 2 * n + nc + 1) * 4 + 4096));
-    ABuf<uint8_t> d_ptb(ar, (n + nc) * 48), d_st(ar, n + nc), d_st2(ar, n + nc), d_ev(ar, n * l * 32);
-    ABuf<G1Affine> d_pts(ar, n + nc);
-    ABuf<Fr> d_agg(ar, COSET_VERIFY_EXT), d_partial(ar, COSET_INTERP_BLOCKS * l), d_evfr(ar, n * l), d_rp(ar, n);
-    ABuf<uint32_t> d_interp(ar, l * 8), d_sc(ar, (2 * n + nc) * 8);   // scalars: r^i [n] | r^i x_c^l [n] | weights [nc]
-    ABuf<uint32_t> d_bad(ar, n), d_csr(ar, m + 1 + n);
-    ABuf<uint32_t> d_grp(ar, 2 * n + nc + 1);   // coset of each item [n] | commitment groups: start [nc + 1], members [n]
-    OKM(d_ptb.p && d_st.p && d_st2.p && d_ev.p && d_pts.p && d_agg.p && d_partial.p && d_evfr.p && d_rp.p && d_interp.p &&
-        d_sc.p && d_bad.p && d_csr.p && d_grp.p);
-    ArenaTrim trim(ar);
-    tr.mark("dedup");
-    // The transcript is one SHA-256 stream over every value: from COSET_VERIFY_HASH_ON_POOL_FROM items on it runs on a
-    // worker thread, underneath the copies, the GPU validation and the grouping (as in verify_cells_on).
-    Fr r;
-    struct HashJob {
-        std::atomic<uint32_t> running{0};   // futex word
-        bool submitted = false;
-        void wait() {
-            if (submitted) wait_host_work_done(&running, "coset transcript hash job");
-        }
-        ~HashJob() { wait(); }   // nothing the worker reads or writes may die before it is through
-    } hash_job;
-    const uint64_t *cidx_p = cidx.data();
-    const Bytes48 *uniq_p = uniq.data();
-    auto hash_all = [&r, uniq_p, nc, cidx_p, coset_indices, evals, proofs_bytes, n, e]() {
-        uint8_t digest[32];
-        coset_verify_digest<Sha256>(digest, uniq_p->bytes, nc, cidx_p, coset_indices, evals->bytes, proofs_bytes->bytes, n, e);
-        r = fr_from_bytes_reduce(digest);
-    };
-    if (n >= COSET_VERIFY_HASH_ON_POOL_FROM) {
-        HashJob *hj = &hash_job;
-        hash_job.running.store(1, std::memory_order_relaxed);
-        hash_job.submitted = WorkerPool::get().submit([hash_all, hj]() {
-            hash_all();
-            hj->running.store(0, std::memory_order_release);
-            futex_wake(&hj->running, INT_MAX);
-        });
-    }
-    OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, 2 * (n + nc) + n * 4));
-    uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[0]), *h_st2 = h_st + (n + nc);
-    uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
-    // proofs [0, n), distinct commitments [n, n + nc): all copies from pageable memory first (such a copy returns only
-    // when it is done, so it must not queue behind a kernel), then values -> Fr and the decompression
-    OKB(hipMemcpyAsync(d_ptb.p, proofs_bytes, n * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemcpyAsync(d_ptb.p + n * 48, uniq.data(), nc * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemcpyAsync(d_ev.p, evals, n * l * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemsetAsync(d_bad.p, 0, n * 4, ctx->stream) == hipSuccess);
-    RC(dev::bytes_to_fr_batch(ctx, d_evfr.p, d_bad.p, d_ev.p, n * l, (uint32_t)l));
-    OKB(hipMemcpyAsync(h_bad, d_bad.p, n * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-    RC(dev::decompress_g1_batch_device(ctx, d_pts.p, d_st.p, d_ptb.p, n + nc));
-    OKB(hipMemcpyAsync(h_st, d_st.p, n + nc, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-    OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess &&
-        dev::ensure_event(ctx->flags_ev) == hipSuccess);
-    OKB(hipEventRecord(ctx->pts_ev, ctx->stream) == hipSuccess);
-    // the subgroup test (~1 ms of dependent doublings) on the second stream, next to everything below; a point outside
-    // the subgroup makes the sums meaningless, not unsafe, and the call ends in BADARGS
-    OKB(hipStreamWaitEvent(ctx->copy_stream, ctx->pts_ev, 0) == hipSuccess);
-    RC(dev::subgroup_g1_batch_device(ctx, d_st2.p, d_pts.p, n + nc, ctx->copy_stream));
-    OKB(hipMemcpyAsync(h_st2, d_st2.p, n + nc, hipMemcpyDeviceToHost, ctx->copy_stream) == hipSuccess);
-    OKB(hipEventRecord(ctx->subgroup_ev, ctx->copy_stream) == hipSuccess);
-    StreamDrain drain{ctx->copy_stream};   // whatever path leaves this function: idle before the arena is reused
     // items grouped by coset (counting sort) for the aggregation, and by commitment for the weights
     {
         std::vector<uint32_t> csr(m + 1 + n, 0);
@@ -2353,7 +2146,10 @@ static C_KZG_RET verify_cosets_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *
         for (size_t i = 0; i < n; i++) members[gfill[cidx[i]]++] = (uint32_t)i;
         OKB(hipMemcpyAsync(d_grp.p, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     }
-    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
+    if (use_table) OKB(hipMemsetAsync(d_sc.p, 0, 4 * npts * 32, ctx->stream) == hipSuccess);
+    // The validation flags.  With the table (a large batch): both streams are through long before the transcript is, so
+    // they are checked here, underneath it.  Without (ladder sums): the subgroup test keeps running on the second stream
+    // next to the sums, and the flags are checked after those.
     auto flags_ok = [&]() -> C_KZG_RET {
         OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
         for (size_t i = 0; i < n + nc; i++) {
@@ -2364,29 +2160,39 @@ static C_KZG_RET verify_cosets_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *
         }
         return C_KZG_OK;
     };
+    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
+    if (use_table) RC(flags_ok());
     tr.mark("copies, validation, grouping (underneath the transcript hash)");
     if (hash_job.submitted)
         hash_job.wait();
     else
         hash_all();
     tr.mark("transcript hash");
-    // stage 2: the scalars, made on the GPU from r
-    uint32_t *d_vec_rp = d_sc.p, *d_vec_wrp = d_sc.p + n * 8, *d_vec_w = d_sc.p + 2 * n * 8;
-    RC(dev::coset_rlc_scalars_enqueue(ctx, d_rp.p, d_vec_rp, d_vec_wrp, d_vec_w, d_grp.p, d_grp.p + n, d_grp.p + n + nc + 1, r, n, nc, e));
+    // stage 2: the scalars, made on the GPU from r -- only r (a kernel argument) crosses PCIe after the transcript
+    RC(dev::coset_rlc_scalars_enqueue(ctx, d_rp.p, v_rp, v_wrp, v_w, d_grp.p, d_grp.p + n, d_grp.p + n + nc + 1, r, n, nc, e));
+    tr.mark("powers of r + weights");
     // stages 3 to 5: sum of r^i y_i per coset (eip7594.c:661-683), each column's interpolation polynomial, their sum
     // with the coset factors taken out (eip7594.c:549-566)
     RC(dev::coset_aggregate_device(ctx, d_agg.p, d_evfr.p, d_rp.p, d_csr.p, d_csr.p + m + 1, n, e));
-    RC(dev::coset_interp_device(ctx, d_interp.p, d_partial.p, d_agg.p, e));
+    RC(dev::coset_interp_device(ctx, v_interp, d_partial.p, d_agg.p, e));
     // the four sums (eip7594.c:926, :530, :807 and the commitment to the aggregated interpolation polynomial over the
-    // first l monomial setup points, :758) in one launch of ladders
+    // first l monomial setup points, :758) in one launch
     G1Jac lc[4];
-    LincombJob jobs[4] = {{d_pts.p, nullptr, (const RawScalar *)d_vec_rp, n},
-                          {d_pts.p + n, nullptr, (const RawScalar *)d_vec_w, nc},
-                          {d_pts.p, nullptr, (const RawScalar *)d_vec_wrp, n},
-                          {ctx->d_mono, nullptr, (const RawScalar *)d_interp.p, l}};
-    RC(gpu_lincomb_multi(ctx, lc, jobs, 4));
-    RC(flags_ok());   // an invalid point or value makes the sums above meaningless, not unsafe: discarded
-    tr.mark("scalars, aggregation, interpolation, four lincombs");
+    if (use_table) {
+        OKB(hipStreamWaitEvent(ctx->stream, ctx->table_ev, 0) == hipSuccess);   // the table is complete
+        RC(dev::table_sums_enqueue(ctx->stream, tbl, d_sums.p, d_sc.p, 4, d_sums_scr.p));
+        G1XYZZ hs[4];
+        OKB(d_sums.down(hs, 4));
+        for (int j = 0; j < 4; j++) lc[j] = jac_from_xyzz(hs[j]);
+    } else {
+        LincombJob jobs[4] = {{d_pts.p, nullptr, (const RawScalar *)v_rp, n},
+                              {d_pts.p + n, nullptr, (const RawScalar *)v_w, nc},
+                              {d_pts.p, nullptr, (const RawScalar *)v_wrp, n},
+                              {ctx->d_mono, nullptr, (const RawScalar *)v_interp, l}};
+        RC(gpu_lincomb_multi(ctx, lc, jobs, 4));
+        RC(flags_ok());   // an invalid point or value makes the sums above meaningless, not unsafe: discarded
+    }
+    tr.mark("aggregation + IFFTs + four lincombs");
     const G1Jac &proof_lc = lc[0], &csum = lc[1], &wsum = lc[2], &interp_commit = lc[3];
     G1Jac final_sum = jac_add(jac_add(csum, jac_neg(interp_commit)), wsum);
     // e(final_sum, [1]_2) == e(proof_lc, [s^l]_2)
@@ -2394,6 +2200,44 @@ static C_KZG_RET verify_cosets_on(dev::DeviceCtx *ctx, bool *ok, const Bytes48 *
                                  prepared_s_pow2(prepared_of(ctx), e, s));
     tr.mark("pairing check");
     return C_KZG_OK;
+}
+
+// The check over n items on the settings' devices: contiguous shards of at least COSET_VERIFY_MIN_SHARD items, each
+// with its own challenge and pairing check, AND-ed
+static C_KZG_RET verify_cosets_sharded(bool *ok, const Bytes48 *commitments_bytes, const uint64_t *coset_indices,
+                                       const Bytes32 *evals, const Bytes48 *proofs_bytes, uint64_t n, int e, const KZGSettings *s) {
+    std::atomic<int> all_ok(1);
+    C_KZG_RET ret = for_each_device_shard(s, n, COSET_VERIFY_MIN_SHARD, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+        bool res = false;
+        C_KZG_RET r = verify_cosets_on(ctx, &res, commitments_bytes + lo, coset_indices + lo, evals + (lo << e), proofs_bytes + lo,
+                                       hi - lo, e, s);
+        if (r == C_KZG_OK && !res) all_ok.store(0);
+        return r;
+    });
+    if (ret == C_KZG_OK) *ok = all_ok.load() != 0;
+    return ret;
+}
+
+// a Cell as its 64 values
+static const Bytes32 *cell_values(const Cell *cells) { return reinterpret_cast<const Bytes32 *>(cells); }
+
+extern "C" C_KZG_RET verify_cell_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes,
+                                                 const uint64_t *cell_indices, const Cell *cells,
+                                                 const Bytes48 *proofs_bytes, uint64_t num_cells,
+                                                 const KZGSettings *s) {
+    // eip7594.c:825-974
+    return guarded([&]() -> C_KZG_RET {
+        *ok = false;
+        if (num_cells == 0) {
+            *ok = true;
+            return C_KZG_OK;
+        }
+        for (size_t i = 0; i < num_cells; i++) {
+            if (cell_indices[i] >= CELLS_PER_EXT_BLOB) return C_KZG_BADARGS;
+        }
+        if (!settings_of(s)) return C_KZG_ERROR;
+        return verify_cosets_sharded(ok, commitments_bytes, cell_indices, cell_values(cells), proofs_bytes, num_cells, CELL_LOG, s);
+    });
 }
 
 extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes,
@@ -2414,17 +2258,7 @@ extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes
             if (coset_indices[i] >= coset_verify_cosets(e)) return C_KZG_BADARGS;
         }
         if (!settings_of(s)) return C_KZG_ERROR;
-        // several devices: contiguous shards of items, each with its own challenge and pairing check, AND-ed
-        std::atomic<int> all_ok(1);
-        C_KZG_RET ret = for_each_device_shard(s, num_cosets, COSET_VERIFY_MIN_SHARD, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
-            bool res = false;
-            C_KZG_RET r = verify_cosets_on(ctx, &res, commitments_bytes + lo, coset_indices + lo, evals + (lo << e),
-                                           proofs_bytes + lo, hi - lo, e, s);
-            if (r == C_KZG_OK && !res) all_ok.store(0);
-            return r;
-        });
-        if (ret == C_KZG_OK) *ok = all_ok.load() != 0;
-        return ret;
+        return verify_cosets_sharded(ok, commitments_bytes, coset_indices, evals, proofs_bytes, num_cosets, e, s);
     });
 }
 
@@ -2804,7 +2638,8 @@ extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8
                 for (uint64_t i = 0; i < n; i++) {
                     if (cell_indices[a + i] >= CELLS_PER_EXT_BLOB) return C_KZG_BADARGS;
                 }
-                return verify_cells_on(ctx, res, commitments_bytes + a, cell_indices + a, cells + a, proofs_bytes + a, n, s);
+                return verify_cosets_on(ctx, res, commitments_bytes + a, cell_indices + a, cell_values(cells + a), proofs_bytes + a, n,
+                                        CELL_LOG, s);
             });
         },
         [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, const uint64_t *start, size_t G) {
@@ -2908,7 +2743,7 @@ static C_KZG_RET verify_blob_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8
 
 // One group of n blobs through the single-batch path (a chunk of one group: a call of one group, or a group larger
 // than a chunk): the cells are made in sub-batches of at most CKZG_HIP_BLOB_CELL_GROUPS_CHUNK_BLOBS blobs, their bytes
-// staged in page-locked memory (256 KB per blob), and verify_cells_on runs on them with the implied commitments and
+// staged in page-locked memory (256 KB per blob), and verify_cosets_on runs on them with the implied commitments and
 // indices.
 static C_KZG_RET verify_blob_cells_staged_on(dev::DeviceCtx *ctx, bool *res, const Blob *blobs, const Bytes48 *cb, const Bytes48 *pb,
                                              uint64_t n, const KZGSettings *s) {
@@ -2945,7 +2780,7 @@ static C_KZG_RET verify_blob_cells_staged_on(dev::DeviceCtx *ctx, bool *res, con
         cm[i] = cb[i / CELLS_PER_EXT_BLOB];
         idx[i] = i % CELLS_PER_EXT_BLOB;
     }
-    return verify_cells_on(ctx, res, cm.data(), idx.data(), reinterpret_cast<const Cell *>(h_cells), pb, cm.size(), s);
+    return verify_cosets_on(ctx, res, cm.data(), idx.data(), reinterpret_cast<const Bytes32 *>(h_cells), pb, cm.size(), CELL_LOG, s);
 }
 
 extern "C" C_KZG_RET ckzg_hip_verify_blob_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Blob *blobs,
@@ -2962,7 +2797,7 @@ extern "C" C_KZG_RET ckzg_hip_verify_blob_cell_kzg_proof_batch_groups(bool *ok, 
             // A chunk of one group (a pool validating one transaction on arrival) could take the chunk path with G = 1 as
             // well as the staged route.  Measured side by side (tools/bench_blob_cell_groups.py --ab-lib, rows new_chunk
             // and new_staged of profiles/blob_cell_groups_bench.json): the staged route is the faster one at 1 x 1
-            // (2.65 against 2.69 ms) and at 1 x 6 (2.94 against 3.31 ms) -- its sums are table sums (verify_cells_on: the
+            // (2.65 against 2.69 ms) and at 1 x 6 (2.94 against 3.31 ms) -- its sums are table sums (verify_cosets_on: the
             // call-time table) -- so every chunk of one group takes it.
             const bool staged = dev::ab_knob("CKZG_HIP_BLOB_CELL_ONE_STAGED", 1) != 0;
             if (n <= CKZG_HIP_BLOB_CELL_GROUPS_CHUNK_BLOBS && !staged) {

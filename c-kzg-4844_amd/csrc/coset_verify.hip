@@ -1,5 +1,6 @@
-// coset_verify.hip -- the device stages of ckzg_hip_verify_coset_kzg_proof_batch: the reference's cell check
-// (eip7594.c:825-974) at every coset size l = 2^e, e = 0 .. 6, of the 8192-point extended domain.  One path for the seven
+// coset_verify.hip -- the device stages of verify_cell_kzg_proof_batch and ckzg_hip_verify_coset_kzg_proof_batch: the
+// reference's cell check (eip7594.c:825-974) at every coset size l = 2^e, e = 0 .. 6 (a cell: e = 6), of the 8192-point
+// extended domain.  One path for the seven
 // sizes: whatever e is, the aggregate has 8192 slots (m = 8192 >> e columns of l), and every kernel maps its lanes over
 // the slots, never over the columns, so that a wave is full at e = 0 (8192 columns of one value) as at e = 6 (128
 // columns of 64).  The index arithmetic is coset_verify_plan.hpp's; DESIGN.md section 3i.

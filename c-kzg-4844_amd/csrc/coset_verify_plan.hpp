@@ -1,5 +1,5 @@
-// coset_verify_plan.hpp -- the index arithmetic and the launch decisions of ckzg_hip_verify_coset_kzg_proof_batch
-// (coset_verify.hip), once, for the host and for the kernels (HD), and through libhost_shim.so
+// coset_verify_plan.hpp -- the index arithmetic and the launch decisions of ckzg_hip_verify_coset_kzg_proof_batch and,
+// at e = 6, of verify_cell_kzg_proof_batch (coset_verify.hip), once, for the host and for the kernels (HD), and through libhost_shim.so
 // for the CPU tests (tests/test_coset_verify_cpu.py; the model is tests/coset_verify_expect.py).
 //
 // Coset size l = 2^e, e <= COSET_MAX_LOG; m = 8192 >> e cosets.  With w = roots_of_unity[1] of the 8192-point domain,
@@ -44,7 +44,8 @@ HD uint32_t coset_verify_twiddle_root(uint32_t pos, int s) {
 // Aggregation: one lane per slot and part.  A column with many items is split over `parts` lanes per slot, each taking
 // every parts-th item of the column's list, and the parts are folded in LDS.  parts is a power of two, grows while an
 // average column would give a lane more than COSET_AGG_ITEMS_PER_LANE items, and stops at COSET_AGG_MAX_PARTS (1024
-// threads, 32 KB of LDS).  At e = 6 these are the numbers of k_cell_aggregate.
+// threads, 32 KB of LDS).  At e = 6 these are the numbers of k_cell_aggregate
+// (verify.hip: the aggregation by groups).
 constexpr uint32_t COSET_AGG_ITEMS_PER_LANE = 4;
 constexpr uint32_t COSET_AGG_MAX_PARTS = 16;
 constexpr uint32_t COSET_AGG_SLOTS_PER_BLOCK = 64;
@@ -95,7 +96,7 @@ void coset_verify_digest(uint8_t digest[32], const uint8_t *commitments48, uint6
 constexpr uint64_t COSET_VERIFY_HASH_ON_POOL_FROM = 256;
 
 // Several devices: no shard below this many items, whatever e is -- an item's cost is its proof's (decompression,
-// subgroup test, two ladders), as a cell's is in verify_cell_kzg_proof_batch, which has the same floor
+// subgroup test, two ladders or table sums); verify_cell_kzg_proof_batch is this check at e = 6
 constexpr uint64_t COSET_VERIFY_MIN_SHARD = 2048;
 
 }  // namespace ckzg

@@ -1280,7 +1280,7 @@ int msm_commit_table_raw_device(DeviceCtx *ctx, uint8_t *d_out48, const uint32_t
 // 6 bits) is built on a side stream under the copy / the transcript hash, and once r exists the sums are digit vectors
 // over that table: 0.45 ms instead of 1.0-2.45 ms after the last byte.  The table is in accumulator form (below): its
 // build is ~1 ms of latency plus 0.15 us per point, short enough to pay from 8 blobs / 128 cells upwards
-// (ckzg_api2.hip: verify_blobs_core, verify_cells_on decide; a table that does not fit the arena is simply not built).
+// (ckzg_api2.hip: verify_blobs_core, verify_cosets_on decide; a table that does not fit the arena is simply not built).
 // ------------------------------------------------------------------------------------------
 
 // Same as k_raw_digits for vectors of any length: scalars[vec][i][8] (canonical, little-endian words), i < npoints

@@ -788,28 +788,8 @@ __global__ void k_scatter_cells(uint4 *image, const uint4 *cells, const uint32_t
     image[(b * 128 + idx[j]) * U4 + w] = cells[g];
 }
 
-// interp[k] = sum_c col[c][k] * (h_c^-1)^k with h_c^-1 = w^(8192 - brp7(c))  (eip7594.c:549-566,
-// 713-752).  One workgroup per coefficient k, one thread per column: a product each and a seven-level fold in LDS --
-// the one-thread-per-coefficient form was 128 dependent multiply-adds (225 us of every cell verification).
-__global__ __launch_bounds__(128) void k_interp_sum(Fr *interp, const Fr *cols, const Fr *roots) {
-    __shared__ Fr sh[128];
-    const uint32_t k = blockIdx.x, c = threadIdx.x;
-    const uint32_t rb = __brev(c) >> 25;
-    const uint32_t idx = ((8192u - rb) * k) & 8191u;
-    sh[c] = mul(vld_fr(cols + c * 64 + k), vld_fr(roots + idx));
-    __syncthreads();
-    for (uint32_t s2 = 64; s2 >= 1; s2 >>= 1) {
-        if (c < s2) sh[c] = add(sh[c], sh[c + s2]);
-        __syncthreads();
-    }
-    if (c == 0) {
-        uint32_t raw[8];
-        to_raw<FrParams>(raw, sh[0]);  // canonical limbs: this vector is used as MSM scalars
-        for (int i = 0; i < 8; i++) reinterpret_cast<uint32_t *>(interp + k)[i] = raw[i];
-    }
-}
-
-// agg[c][j] = sum over the cells i of column c of r^i * cell_i[j]  (eip7594.c:661-683).
+// agg[c][j] = sum over the cells i of row c of r^i * cell_i[j]  (eip7594.c:661-683), a row being a (group, column)
+// pair of a chunk of groups (group_cell_aggregate_device; the single check aggregates in k_coset_aggregate).
 // order[col_start[c] .. col_start[c+1]) lists the cells of column c.  One workgroup per column, thread (j, p): position
 // j over every parts-th cell of the list, then a fold over the parts in LDS (a large batch has 64+ cells per column:
 // that many dependent multiply-adds per thread in the one-part form).
@@ -844,81 +824,9 @@ int scatter_cells_device(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *d_cell
     return 0;
 }
 
-// The scalars of a cell batch's sums over its call-time table, made from the batch challenge where their digits are
-// needed (eip7594.c:926 sum r^i proof_i, :784-812 sum r^i h_k^64 proof_i): lane i raises r to its index, leaves it in
-// Montgomery form for k_cell_aggregate and in canonical limbs -- plain and times the coset factor of its cell's
-// column -- in the two scalar vectors.  Only r (a kernel argument) crosses PCIe after the transcript.
-__global__ void k_cell_rlc_scalars(Fr *rp, uint32_t *vec_rp, uint32_t *vec_wrp, const uint32_t *cell_idx, const Fr *roots,
-                                   RPow2 rp2, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fr pw = rpow_at(rp2, i);
-    rp[i] = pw;
-    const uint32_t rb = __brev(cell_idx[i]) >> 25;   // 7-bit reversal of the column index (128 columns)
-    uint32_t a[8], c[8];
-    to_raw<FrParams>(a, pw);
-    to_raw<FrParams>(c, mul(pw, roots[(size_t)rb * N_CELL]));
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        vec_rp[(size_t)i * 8 + k] = a[k];
-        vec_wrp[(size_t)i * 8 + k] = c[k];
-    }
-}
-
-// Weight of each distinct commitment (eip7594.c:494-539): the sum of r^i over the cells that name it.  One 64-lane
-// workgroup per commitment over the member list the host grouped while the transcript was being hashed.
-__global__ __launch_bounds__(64) void k_commit_weights(uint32_t *vec_w, const Fr *rp, const uint32_t *grp_start,
-                                                      const uint32_t *members) {
-    __shared__ Fr sh[64];
-    const uint32_t j = blockIdx.x, tid = threadIdx.x;
-    Fr acc = Fr::zero();
-    for (uint32_t m = grp_start[j] + tid; m < grp_start[j + 1]; m += 64) acc = add(acc, rp[members[m]]);
-    sh[tid] = acc;
-    __syncthreads();
-    for (uint32_t s2 = 32; s2 >= 1; s2 >>= 1) {
-        if (tid < s2) sh[tid] = add(sh[tid], sh[tid + s2]);
-        __syncthreads();
-    }
-    if (tid == 0) {
-        uint32_t a[8];
-        to_raw<FrParams>(a, sh[0]);
-#pragma unroll
-        for (int k = 0; k < 8; k++) vec_w[(size_t)j * 8 + k] = a[k];
-    }
-}
-
-int cell_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_vec_rp, uint32_t *d_vec_wrp, uint32_t *d_vec_w,
-                             const uint32_t *d_cell_idx, const uint32_t *d_grp_start, const uint32_t *d_members,
-                             const Fr &r, size_t n, size_t nc) {
-    if (!n) return 0;
-    if (n >= ((size_t)1 << 24)) return 2;
-    hipLaunchKernelGGL(k_cell_rlc_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_rp, d_vec_rp, d_vec_wrp,
-                       d_cell_idx, ctx->d_roots, rpow2_of(r), (uint32_t)n);
-    hipLaunchKernelGGL(k_commit_weights, dim3((unsigned)nc), dim3(64), 0, ctx->stream, d_vec_w, d_rp, d_grp_start, d_members);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int cell_aggregate_device(DeviceCtx *ctx, Fr *d_agg, const Fr *d_cell_fr, const Fr *d_rp, const uint32_t *d_col_start,
-                          const uint32_t *d_order, size_t n_cells) {
-    // parts: a power of two, ~4 cells per thread, at most 16 (1024 threads, 32 KB of LDS)
-    uint32_t parts = 1;
-    while (parts < 16 && (size_t)parts * 128 * 4 < n_cells) parts <<= 1;
-    hipLaunchKernelGGL(k_cell_aggregate, dim3(128), dim3(64 * parts), parts > 1 ? parts * 64 * sizeof(Fr) : 0, ctx->stream, d_agg,
-                       d_cell_fr, d_rp, d_col_start, d_order, parts);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int interp_sum_device(DeviceCtx *ctx, Fr *d_interp, const Fr *d_cols) {
-    hipLaunchKernelGGL(k_interp_sum, dim3(64), dim3(128), 0, ctx->stream, d_interp, d_cols, ctx->d_roots);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------
-// cell verification by groups (ckzg_hip_verify_cell_kzg_proof_batch_groups): the kernels above once per chunk,
-// segmented by group.  The index maps are the host's (cell_groups_plan.hpp); gd is its group table
+// cell verification by groups (ckzg_hip_verify_cell_kzg_proof_batch_groups): the stages of the single
+// check (coset_verify.hip, at cosets of 64) once per chunk, segmented by group.  The index maps are the host's (cell_groups_plan.hpp); gd is its group table
 // start[G + 1] | first term of A_g [G] | distinct commitments of g [G] | first term of B_g [G], and sc the scalar
 // vector of all jobs (canonical limbs, 8 words per term, zero where a term is padding).
 // ------------------------------------------------------------------------------------------
@@ -973,8 +881,8 @@ __global__ __launch_bounds__(64) void k_group_commit_weights(uint32_t *sc, const
     }
 }
 
-// -interp_g[k] = -sum over the rows of group g of row[k] * (h_c^-1)^k, c the row's column (k_interp_sum with a
-// row -> column map and the group's rows instead of rows 0..127 = columns), in canonical limbs onto the k-th setup
+// -interp_g[k] = -sum over the rows of group g of row[k] * (h_c^-1)^k, c the row's column (the fold of
+// k_coset_interp_fold with a row -> column map and the group's rows instead of the 128 columns), in canonical limbs onto the k-th setup
 // point of A_g: the interpolation commitment is subtracted by its scalars, not by a negated point table.  One
 // workgroup per group, thread (k, p): coefficient k over every fourth row, then a fold over the four parts.
 __global__ __launch_bounds__(256) void k_group_interp_sum(uint32_t *sc, const Fr *rows, const uint32_t *grp_rows,

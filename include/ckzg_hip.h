@@ -520,26 +520,27 @@ C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proofs, void *d
  * reduced mod r (at e = 6 the input of compute_verify_cell_kzg_proof_batch_challenge, byte for byte), four sums on the
  * GPU and e(sum_j w_j C_j - [sum_i r^i I_i(s)]_1 + sum_i [r^i x_c^l] proof_i, [1]_2) = e(sum_i [r^i] proof_i, [s^l]_2)
  * on the host, x_c = brp_roots_of_unity[c l], I_i the interpolation polynomial of item i.  *ok is the AND over all items.
- * At e = 6 the verdicts and return values are those of verify_cell_kzg_proof_batch, at e = 0 an item is true exactly
- * when verify_kzg_proof(C, z = brp_roots_of_unity[c], y, proof) is; both run through this call's own kernels
- * (coset_verify.hip), which map their lanes over the 8192 slots of the aggregate and not over its columns.
+ * At e = 6 the call IS verify_cell_kzg_proof_batch -- one pipeline serves both, that call with a Cell read as its 64
+ * values -- and at e = 0 an item is true exactly when verify_kzg_proof(C, z = brp_roots_of_unity[c], y, proof) is.  The
+ * kernels (coset_verify.hip) map their lanes over the 8192 slots of the aggregate and not over its columns.
  * num_cosets == 0 gives *ok = true and C_KZG_OK.  C_KZG_BADARGS with *ok = false: log2_coset > 6, a coset index >= m,
  * a value that is not canonical, a commitment or proof that is not a valid G1 point, a NULL pointer with work to do.
  * C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  With several devices each takes a contiguous shard of at least
  * 2048 items with its own challenge and check, and the verdicts are AND-ed.  The line table of [s^l]_2 for 2 <= l <= 32
  * is built by the first call of that size on the settings; load time does not change.
- * NOT here: per-item verdicts, groups, device pointers, and the call-time table of verify_cell_kzg_proof_batch -- the
- * four sums are ladders at every size.
- * Measured (profiles/coset_verify_bench.json): medians of 20 and minima of the wall time, default tables, a fresh
- * process, 128 / 1,024 / 8,192 items, all true; with one false item the same within 0.1 ms unless noted.
+ * The four sums: at e = 6 from 128 items on, table sums over a fixed-base table of the batch's points built while the
+ * transcript is hashed (as verify_cell_kzg_proof_batch always had; a device too full for the table falls back); ladders
+ * below 128 items and at every e < 6, where a table's break-even has not been measured.
+ * NOT here: per-item verdicts, groups, device pointers.
+ * Measured (profiles/coset_verify_bench.json; its e = 6 rows predate the shared pipeline): medians of 20 and minima
+ * of the wall time, default tables, a fresh process, 128 / 1,024 / 8,192 items, all true; with one false item the same within 0.1 ms unless noted.
  *   e = 0  2.33 (min 2.22) / 2.56 (2.41) / 4.49 (4.25) ms (one false at 8,192: 5.00, min 4.18), against 14.2 (min 14.1) /
  *          14.8 (14.8) / 16.8 (16.7) ms for ckzg_hip_verify_kzg_proof_batch_locate with everything true in the same
  *          process: this call's median is below the alternative's minimum at all three (6.1x, 5.8x, 3.7x).  That call
  *          also gives one verdict per item; this one gives one for the batch.
- *   e = 6  2.43 (2.23) / 3.05 (2.96) / 11.73 (11.63) ms against 2.29 (2.19) / 2.59 (2.41) / 9.95 (9.89) ms for
- *          verify_cell_kzg_proof_batch over the same items: this call is NOT faster at any size (6 % / 18 % / 18 %
- *          slower): that call sums over a call-time table.  verify_cell_kzg_proof_batch wins at e = 6; use it for
- *          cells of 64.
+ *   e = 6  the same code as verify_cell_kzg_proof_batch over the same items, and the same time: 2.28 / 2.70 / 9.91 ms
+ *          (profiles/verify_merge_ab.json: medians over eight fresh processes; before the two calls shared their
+ *          pipeline this one took 2.42 / 3.00 / 11.69 ms, by ladders).  Either call serves cells of 64.
  *   e = 1 .. 5 have no alternative in the library: 2.27 / 2.26 / 2.30 / 2.33 / 2.34 ms for 128 items, 2.57 / 2.62 /
  *          2.62 / 2.64 / 2.71 ms for 1,024 and 4.20 / 4.34 / 4.77 / 5.82 / 7.85 ms for 8,192. */
 C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes, const uint64_t *coset_indices,

@@ -1,9 +1,11 @@
 // poly_shim.hip -- the stages that move and combine vectors of Fr, behind a C ABI (tests/test_gpu_poly_stages.py):
 //   ntt.hip     fr_ntt_batch, bytes_to_fr_batch, fr_to_bytes_batch, zero_extend_batch
 //   verify.hip  eval_blob_bytes_batch_device (k_eval_tree), eval_quotient_batch_device (k_eval_barycentric<true>,
-//               k_quotient_in_domain), cell_aggregate_device, group_cell_aggregate_device (k_cell_aggregate),
-//               interp_sum_device, group_interp_sum_device, fr_mul_inplace_device, fr_div_inplace_device,
+//               k_quotient_in_domain), group_cell_aggregate_device (k_cell_aggregate),
+//               group_interp_sum_device, fr_mul_inplace_device, fr_div_inplace_device,
 //               recover_set_factors_enqueue, fr_mul_cell_factor_enqueue, scatter_cells_device, scatter_cells_rows_enqueue
+//   coset_verify.hip  coset_aggregate_device, coset_interp_device at cosets of 64: the aggregation and interpolation of a
+//               single cell batch
 // They sit between the arithmetic that tests/test_gpu_fields.py pins and the entry points that are compared with the
 // oracle, and the entry points reach them with a handful of shapes and with inputs nobody chooses (a hashed z, a
 // divisor that is never zero).  Here each one runs on chosen inputs and its whole output comes back.
@@ -25,12 +27,14 @@
 #include <cstring>
 #include "dev_shim_common.hpp"
 #include "device.hpp"
+#include "coset_verify_plan.hpp"
 
 using namespace ckzg;
 using namespace ckzg::dev;
 
 namespace {
 
+constexpr int CELL_LOG = 6;   // a cell is a coset of 64 values
 constexpr size_t PS_MAX_ELEMS = (size_t)1 << 22;   // field elements of one buffer: no call of a test comes near
 constexpr size_t BLOB_BYTES = (size_t)N_BLOB * 32, CELL_BYTES = (size_t)N_CELL * 32;
 
@@ -318,7 +322,8 @@ int ps_scatter_cells_rows(uint8_t *image, size_t image_rows, const uint8_t *cell
 }
 
 // rows [nrows + 1][64][8] go up as the caller filled them; cell_fr [n][64][8]; rp [n][8]; row_start [nrows + 1]; order [n].
-// grouped = 0: cell_aggregate_device (nrows must be 128: its columns), else group_cell_aggregate_device
+// grouped = 0: the aggregation of a single cell batch, coset_aggregate_device at cosets of 64 (nrows must be 128: its
+// columns), else group_cell_aggregate_device
 int ps_cell_aggregate(uint32_t *rows, const uint32_t *cell_fr, const uint32_t *rp, const uint32_t *row_start, const uint32_t *order,
                       size_t n, size_t nrows, int grouped, int *rc) {
     if (!n || n * 64 > PS_MAX_ELEMS || !nrows || nrows > 4096 || (!grouped && nrows != 128)) return DS_BAD_ARG;
@@ -337,8 +342,8 @@ int ps_cell_aggregate(uint32_t *rows, const uint32_t *cell_fr, const uint32_t *r
             *rc = group_cell_aggregate_device(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const Fr *)args[2].dev,
                                               (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, n, nrows);
         else
-            *rc = cell_aggregate_device(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const Fr *)args[2].dev,
-                                        (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, n);
+            *rc = coset_aggregate_device(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const Fr *)args[2].dev,
+                                         (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, n, CELL_LOG);
     });
     if (run) return run;
     fr_out(rows, out);
@@ -346,16 +351,30 @@ int ps_cell_aggregate(uint32_t *rows, const uint32_t *cell_fr, const uint32_t *r
 }
 
 // interp [128][8] (canonical, as the stage writes them: 64 values and a guard of 64) goes up as the caller filled it;
-// cols [128][64][8]
+// cols [128][64][8]: the coefficients of each column's interpolation polynomial.  The stage of a single cell batch,
+// coset_interp_device at cosets of 64, takes a column's VALUES (bit-reversed order) and makes the coefficients itself,
+// so the shim evaluates each column first, on the host: value j = sum_k cols[c][k] w_64^(brp_6(j) k), w_64 = w^128.
+// (The stage on values, with its coefficients and partial rows read back: coset_verify_shim.hip.)
 int ps_interp_sum(uint32_t *interp, const uint32_t *cols, const uint32_t *roots, int *rc) {
     const Tables tb(roots);
     const std::vector<Fr> cv = fr_in(cols, 128 * 64);
-    std::vector<Arg> args = {{interp, interp, 128 * 32, nullptr}, {cv.data(), nullptr, cv.size() * 32, nullptr}};
+    std::vector<Fr> values(128 * 64);
+    for (uint32_t c = 0; c < 128; c++) {
+        for (uint32_t j = 0; j < 64; j++) {
+            const uint32_t t = brp13(j) >> 7;   // brp_6(j)
+            Fr acc = Fr::zero();
+            for (uint32_t k = 0; k < 64; k++) acc = add(acc, mul(cv[c * 64 + k], tb.roots[(128 * t * k) & (N_EXT - 1)]));
+            values[c * 64 + j] = acc;
+        }
+    }
+    std::vector<Arg> args = {{interp, interp, 128 * 32, nullptr},
+                             {values.data(), nullptr, values.size() * 32, nullptr},
+                             {nullptr, nullptr, (size_t)COSET_INTERP_BLOCKS * 64 * sizeof(Fr), nullptr}};
     const size_t at = tb.push(args);
     return run_bounded(args, [&](hipStream_t st) {
         DeviceCtx ctx;
         *rc = stage_ctx(ctx, st, args, at);
-        if (*rc == 0) *rc = interp_sum_device(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev);
+        if (*rc == 0) *rc = coset_interp_device(&ctx, (uint32_t *)args[0].dev, (Fr *)args[2].dev, (Fr *)args[1].dev, CELL_LOG);
     });
 }
 

@@ -1,6 +1,6 @@
 // stage_shim.hip -- the stages that turn a batch challenge into scalars, and the items into the bytes that are hashed,
-// behind a C ABI (tests/test_gpu_rlc_stages.py): rlc_scalars_enqueue, cell_rlc_scalars_enqueue,
-// group_rlc_scalars_enqueue, blob_group_scalars_enqueue, locate_scale_enqueue, batch_transcript_rows_device and
+// behind a C ABI (tests/test_gpu_rlc_stages.py): rlc_scalars_enqueue, coset_rlc_scalars_enqueue at
+// cosets of 64 (the scalars of a cell batch), group_rlc_scalars_enqueue, blob_group_scalars_enqueue, locate_scale_enqueue, batch_transcript_rows_device and
 // rpow2.hpp's rpow_at.  A weight of a batch check is the one value no verdict can check -- any consistent weights pass an
 // honest batch and fail a spoilt one -- so these values are read here and compared with integers.
 //
@@ -26,6 +26,7 @@ using namespace ckzg::dev;
 
 namespace {
 
+constexpr int CELL_LOG = 6;   // a cell is a coset of 64 values
 constexpr size_t SS_MAX_ITEMS = (size_t)1 << 20;   // no call of a test comes near; keeps every buffer small
 
 std::vector<Fr> fr_in(const uint32_t *raw, size_t n) {
@@ -96,7 +97,9 @@ int ss_rlc_scalars(uint32_t *sc, const uint32_t *z, const uint32_t *r, size_t n)
     return run ? run : rc;
 }
 
-// rp [n][8] (canonical), vec_rp [n][8], vec_wrp [n][8], vec_w [nc][8]; roots: w^i, 8193 of them
+// The scalars of a cell batch: coset_rlc_scalars_enqueue at cosets of 64 (the stage at every coset size, with guards
+// around its buffers: coset_verify_shim.hip).  rp [n][8] (canonical), vec_rp [n][8], vec_wrp [n][8], vec_w [nc][8];
+// cell_idx [n] < 128; roots: w^i, 8193 of them
 int ss_cell_rlc_scalars(uint32_t *rp, uint32_t *vec_rp, uint32_t *vec_wrp, uint32_t *vec_w, const uint32_t *cell_idx,
                         const uint32_t *grp_start, const uint32_t *members, const uint32_t *r, const uint32_t *roots, size_t n,
                         size_t nc) {
@@ -105,7 +108,7 @@ int ss_cell_rlc_scalars(uint32_t *rp, uint32_t *vec_rp, uint32_t *vec_wrp, uint3
     for (size_t j = 0; j < nc; j++)
         if (grp_start[j] > grp_start[j + 1]) return DS_BAD_ARG;
     for (size_t m = 0; m < n; m++)
-        if (members[m] >= n) return DS_BAD_ARG;
+        if (members[m] >= n || cell_idx[m] >= 128) return DS_BAD_ARG;
     const std::vector<Fr> rootsf = fr_in(roots, 8193);
     const Fr rf = from_raw<FrParams>(r);
     std::vector<Fr> rpf(n);
@@ -117,9 +120,9 @@ int ss_cell_rlc_scalars(uint32_t *rp, uint32_t *vec_rp, uint32_t *vec_wrp, uint3
     const int run = run_bounded(args, [&](hipStream_t st) {
         DeviceCtx ctx;
         stage_ctx(ctx, st, (Fr *)args[7].dev);
-        rc = cell_rlc_scalars_enqueue(&ctx, (Fr *)args[0].dev, (uint32_t *)args[1].dev, (uint32_t *)args[2].dev,
-                                      (uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, (const uint32_t *)args[5].dev,
-                                      (const uint32_t *)args[6].dev, rf, n, nc);
+        rc = coset_rlc_scalars_enqueue(&ctx, (Fr *)args[0].dev, (uint32_t *)args[1].dev, (uint32_t *)args[2].dev,
+                                       (uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, (const uint32_t *)args[5].dev,
+                                       (const uint32_t *)args[6].dev, rf, n, nc, CELL_LOG);
     });
     if (run || rc) return run ? run : rc;
     fr_out(rp, rpf);

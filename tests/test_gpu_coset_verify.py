@@ -1,7 +1,8 @@
 """ckzg_hip_verify_coset_kzg_proof_batch: the verdicts, at every coset size 2^e, e = 0 .. 6 (c-kzg-4844_amd/csrc/
 coset_verify.hip; the model is tests/coset_verify_expect.py).  The proofs and values come from
 ckzg_hip_compute_coset_kzg_proofs_batch, which tests/test_gpu_coset_openings.py pins at every size.  The reference is
-never the call under test: e = 6 hangs on verify_cell_kzg_proof_batch (library and oracle), e = 0 on verify_kzg_proof,
+never the call under test: e = 6 hangs on the oracle's verify_cell_kzg_proof_batch (the library's is the same pipeline at
+e = 6, and must agree with both), e = 0 on verify_kzg_proof,
 e = 1 .. 5 on a single-item check by definition in the oracle's group arithmetic on the setup file's points."""
 import ctypes as C
 import random
@@ -305,6 +306,26 @@ def test_aggregate_in_parts(hip, mat, constants, e):
         items = _repeat(mat, e, n)
         assert call(hip, items, e) == (OK, True)
         assert call(hip, items[:n // 2] + [_bump(items[n // 2])] + items[n // 2 + 1:], e) == (OK, False)
+
+
+CALL_TABLE_FROM = 128   # ckzg_api2.hip: verify_cosets_wants_table (CKZG_HIP_VERIFY_CELL_TABLE_MIN), at e = 6 only
+
+
+@pytest.mark.parametrize("e,n", [(6, CALL_TABLE_FROM - 1), (6, CALL_TABLE_FROM), (5, CALL_TABLE_FROM)])
+def test_call_time_table_threshold(hip, oracle, mat, setup, e, n):
+    """cosets of 64 take their four sums from a call-time table from 128 items on (what verify_cell_kzg_proof_batch runs),
+    from ladders below; smaller cosets from ladders at every size.  The verdicts are the CPU oracle's: its
+    verify_cell_kzg_proof_batch at e = 6, the check of each item by definition at e = 5"""
+    items = _repeat(mat, e, n)
+    at = n - 2
+    forged = items[:at] + [_bump(items[at], 1)] + items[at + 1:]
+    if e == 6:
+        for batch, want in ((items, True), (forged, False)):
+            assert oracle.verify_cell_kzg_proof_batch(*[[it[k] for it in batch] for k in range(4)]) is want
+    else:
+        assert all(setup.holds(it, e) for it in items) and not setup.holds(forged[at], e)
+    assert call(hip, items, e) == (OK, True)
+    assert call(hip, forged, e) == (OK, False)
 
 
 def test_every_point_of_the_domain_in_one_call(hip, mat):

@@ -62,3 +62,17 @@ def test_forged_value_pairs(hip, mat, e):
         forged = list(items)
         forged[i], forged[j] = _bump(items[i], pos, delta), _bump(items[i], pos, R - delta)
         assert call(hip, forged, e) == (OK, False), (i, j)
+
+
+@pytest.mark.parametrize("i,j", [(0, 1), (63, 129), (1, 65)])
+def test_forged_proof_pairs_over_the_call_time_table(hip, oracle, mat, i, j):
+    """e = 6, 130 items: the scalars are rows of the table's matrix (from 128 items on), as verify_cell_kzg_proof_batch
+    lays them out; both verdicts are the CPU oracle's"""
+    items = _batch(mat, 6, i, j, 7000 + i + j)[:130]
+    cm, c, ev, pf = items[i]
+    plus, minus = _forged(pf)
+    forged = list(items)
+    forged[i], forged[j] = (cm, c, ev, plus), (cm, c, ev, minus)
+    for batch, want in ((items, True), (forged, False)):
+        assert oracle.verify_cell_kzg_proof_batch(*[[it[k] for it in batch] for k in range(4)]) is want
+        assert call(hip, batch, 6) == (OK, want), (i, j)

@@ -11,8 +11,8 @@ kernels are the product's binary code) runs each stage on chosen inputs and retu
     eval_quotient_batch_device                        k_eval_barycentric<true>, k_quotient_in_domain
     fr_div_inplace_device, fr_mul_inplace_device      k_fr_div_inplace (zero divisors), k_fr_mul_inplace
     recover_set_factors_enqueue, fr_mul_cell_factor_enqueue, scatter_cells_device, scatter_cells_rows_enqueue
-    cell_aggregate_device, group_cell_aggregate_device     k_cell_aggregate, parts = 1 .. 16
-    interp_sum_device, group_interp_sum_device
+    coset_aggregate_device at cosets of 64, group_cell_aggregate_device     parts = 1 .. 16
+    coset_interp_device at cosets of 64 (on the values of given coefficients), group_interp_sum_device
 
 Every comparison is exact and over the whole buffer, a guard region behind the data included: Python integers
 (tests/poly_expect.py, each reference checked by a second route in tests/test_poly_expect_cpu.py) and bytes.

@@ -29,7 +29,7 @@ from test_gpu_round3 import _device, rt  # noqa: F401  (rt: the HIP runtime fixt
 
 pytestmark = pytest.mark.gpu
 VERIFY_CHUNK = 256      # ckzg_api2.hip: piped_form, CH
-CELL_TABLE_MIN = 128    # ckzg_api2.hip: verify_cells_on, cell_table_min
+CELL_TABLE_MIN = 128    # ckzg_api2.hip: verify_cosets_wants_table, table_min
 
 
 def _forged(proof48):
@@ -138,7 +138,8 @@ def _cell_items(mat, n, i, j):
 @pytest.mark.parametrize("n,i,j", [(2, 0, 1), (CELL_TABLE_MIN - 1, 1, 64), (CELL_TABLE_MIN, 1, 64), (130, 0, 1), (130, 63, 129),
                                    (260, 2, 258)])
 def test_cell_batch_rejects_a_cancelling_pair(hip, oracle, mat, n, i, j):
-    """below 128 cells the scalars are made on the host (ladder sums), from 128 on by k_cell_rlc_scalars"""
+    """the scalars are k_coset_rlc_scalars' at every size: below 128 cells as the vectors of the ladder sums, from 128 on
+    as rows of the call-time table's matrix"""
     cms, cols, cells, honest, forged = _cell_items(mat, n, i, j)
     assert oracle.verify_cell_kzg_proof_batch(cms, cols, cells, honest) is True
     assert oracle.verify_cell_kzg_proof_batch(cms, cols, cells, forged) is False

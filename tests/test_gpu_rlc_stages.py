@@ -7,7 +7,7 @@ stage on chosen inputs and returns its whole output buffer:
 
     rpow_at (rpow2.hpp)                               every table entry: indices 2^k - 1, 2^k, 2^k + 1, k < 24
     rlc_scalars_enqueue                               k_rlc_scalars
-    cell_rlc_scalars_enqueue                          k_cell_rlc_scalars, k_commit_weights
+    coset_rlc_scalars_enqueue at cosets of 64         k_coset_rlc_scalars, k_coset_commit_weights (a cell batch's)
     group_rlc_scalars_enqueue                         k_group_rlc_scalars, k_group_commit_weights
     blob_group_scalars_enqueue                        k_blob_group_scalars, k_blob_group_ysum
     locate_scale_enqueue                              k_locate_scale
@@ -140,7 +140,7 @@ def test_rlc_scalars(shim, n):
             pytest.fail("r = %x, n = %d: scalar %d of vector %d is %x, expected %x" % (r, n, at % (2 * n), at // (2 * n), got[at], want[at]))
 
 
-# ---- 3. cell_rlc_scalars_enqueue ----
+# ---- 3. the scalars of a cell batch: coset_rlc_scalars_enqueue at cosets of 64 ----
 
 def _member_lists(rnd, n):
     """the cells dealt to commitments with member lists of 1, 63, 64, 65 and 107 cells (n = 300; whatever fits

@@ -2,7 +2,7 @@
 every e = 0 .. 6 at 128 / 1,024 / 8,192 items, all true and with one false item, default tables, a fresh process.  At
 the two ends what a client had before it, in the same process on the same settings:
 
-    e = 6   verify_cell_kzg_proof_batch over the same items (true and one false)
+    e = 6   verify_cell_kzg_proof_batch over the same items (true and one false): the same pipeline, so the two tie
     e = 0   ckzg_hip_verify_kzg_proof_batch_locate with everything true: the cheapest public route to "are all of these
             right" for single points
     e = 1 .. 5   nothing: the library had no verifier for these sizes
@@ -68,7 +68,8 @@ def main():
     f = hip._fn("ckzg_hip_verify_coset_kzg_proof_batch")
     g_cell = hip._fn("verify_cell_kzg_proof_batch")
     g_locate = hip._fn("ckzg_hip_verify_kzg_proof_batch_locate")
-    res = {"tool": "bench_coset_verify", "reps": a.reps, "unit": "ms", "tables": "default", "sums": "ladders"}
+    res = {"tool": "bench_coset_verify", "reps": a.reps, "unit": "ms", "tables": "default",
+           "sums": "ladders; at e = 6 table sums from 128 items on (the pipeline of verify_cell_kzg_proof_batch)"}
     rows = []
     for e in range(7):
         l, m = 1 << e, 8192 >> e
