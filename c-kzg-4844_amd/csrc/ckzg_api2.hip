@@ -17,7 +17,6 @@
 #include "coset_verify_plan.hpp"
 #include "g1_fft_plan.hpp"
 #include "locate_plan.hpp"
-#include "recover_rows_plan.hpp"
 #include "coset_recover_plan.hpp"
 #include "slice_starts.hpp"
 
@@ -1473,8 +1472,8 @@ static void vanishing_poly_from_roots(std::vector<Fr> &poly, const std::vector<F
 // the OutPipe and its drain, the chunk loop with its alternating output buffers, the conversion from and to bytes, the
 // transform sequence, the one wait per chunk, flags and status, the give-back, the proof tail and the timing epilogue.
 // A *source* supplies what differs between the call whose rows all hold the same cells (RecoverSameCells) and the call
-// by rows (RecoverByRows): its chunks, its way of bringing the cells into the zeroed image, its way of making and
-// applying Z, and which caller rows its device rows are.
+// or cosets by rows (RecoverCosetsByRows, behind the cell call and the coset call): its chunks, its way of bringing the
+// cells into the zeroed image, its way of making and applying Z, which caller rows its device rows are, and its proofs.
 //     chunks(), rows(c), all_full(c)       the chunks; all_full: every row holds 128 cells, nothing to recover
 //     max_rows(), in_bytes()               over the chunks: device rows, bytes of cells copied in
 //     extra_bytes(), take(arena)           the source's own device buffers, taken after the common ones
@@ -1493,7 +1492,7 @@ static void vanishing_poly_from_roots(std::vector<Fr> &poly, const std::vector<F
 // unspecified output; the return value is `result` (what the caller found before) or C_KZG_BADARGS if a row is flagged.
 constexpr size_t RECOVER_CHUNK_ROWS = 512;  // 512 rows: 128 MiB of byte image + 128 MiB of Fr + 64 MiB of coefficients
 
-// The proof tail of the two cell sources: FK20 over the fixed-base tables, 128 proofs a row
+// The proof tail of a source whose rows are cells: FK20 over the fixed-base tables, 128 proofs a row
 static C_KZG_RET fk20_proof_tail(dev::DeviceCtx *ctx, size_t k, Fr *d_e, uint8_t *d_proofs, uint8_t *d_tail) {
     const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
     Fr *d_poly = reinterpret_cast<Fr *>(d_tail);
@@ -1693,104 +1692,15 @@ extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_batch(Cell *recovered
     });
 }
 
-// The source of the call by rows: caller rows [lo, hi) of the call on one device.  The plan (recover_rows_plan.hpp)
-// names the valid rows, their distinct sets and every cell's place; per chunk the GPU makes the per-cell values of Z
-// and 1 / Z for each distinct set (recover_set_factors.hpp) and all rows of the chunk, whatever they hold, go through
-// the transforms and one FK20 batch together.  No field arithmetic on the host.
-struct RecoverByRows {
-    const RecoverRowsPlan &plan;
-    const Cell *cells;
-    uint64_t lo;
-    ABuf<Fr> d_zdom, d_zinv;      // 128 factors per set
-    ABuf<uint32_t> d_meta;        // row_set [k] | cell_dst [cells] | set_mask [4 sets]
-    std::vector<uint32_t> meta;
-
-    size_t chunks() const { return plan.chunks.size(); }
-    size_t rows(size_t c) const { return plan.chunks[c].rows(); }
-    bool all_full(size_t c) const { return plan.chunks[c].all_full; }
-    size_t max_rows() const { return plan.max_rows; }
-    size_t in_bytes() const { return plan.max_cells * BYTES_PER_CELL; }
-    // set ids per row; target per cell; mask + 2 x 128 factors per set
-    size_t extra_bytes() const {
-        return plan.max_rows * 4 + plan.max_cells * 4 + plan.max_sets * (16 + 2 * CELLS_PER_EXT_BLOB * sizeof(Fr));
-    }
-    bool take(Arena &ar) {
-        d_zdom = ABuf<Fr>(ar, plan.max_sets * CELLS_PER_EXT_BLOB), d_zinv = ABuf<Fr>(ar, plan.max_sets * CELLS_PER_EXT_BLOB);
-        d_meta = ABuf<uint32_t>(ar, plan.max_rows + plan.max_cells + 4 * plan.max_sets);
-        return d_zdom.p && d_zinv.p && d_meta.p;
-    }
-    C_KZG_RET prepare(dev::DeviceCtx *) { return C_KZG_OK; }
-    C_KZG_RET cells_in(dev::DeviceCtx *ctx, size_t c, uint8_t *d_img, uint8_t *d_in) {
-        const RecoverRowsChunk &ch = plan.chunks[c];
-        const uint32_t *d_cell_dst = d_meta.p + ch.rows(), *d_set_mask = d_cell_dst + ch.cells();
-        meta.clear();
-        meta.insert(meta.end(), ch.row_set.begin(), ch.row_set.end());
-        meta.insert(meta.end(), ch.cell_dst.begin(), ch.cell_dst.end());
-        meta.insert(meta.end(), ch.set_mask.begin(), ch.set_mask.end());
-        // (the stream was waited for in the chunk before, after its last use of d_meta: nothing reads it or `meta` any more)
-        OKB(hipMemcpyAsync(d_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-        for (const RecoverRowsRun &run : ch.runs) {
-            OKB(hipMemcpyAsync(d_in + (size_t)run.dev_cell * BYTES_PER_CELL, cells + run.src_cell,
-                               (size_t)run.cells * BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-        }
-        if (!ch.all_full) RC(dev::recover_set_factors_enqueue(ctx, d_zdom.p, d_zinv.p, d_set_mask, ch.sets()));
-        RC(dev::scatter_cells_rows_enqueue(ctx, d_img, d_in, d_cell_dst, ch.cells()));
-        return C_KZG_OK;
-    }
-    int mul_z(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_cell_factor_enqueue(ctx, d_e, d_zdom.p, d_meta.p, rows(c)); }
-    int mul_zinv(dev::DeviceCtx *ctx, size_t c, Fr *d_e) { return dev::fr_mul_cell_factor_enqueue(ctx, d_e, d_zinv.p, d_meta.p, rows(c)); }
-    template <class F>
-    bool for_each_run(size_t c, F &&f) const {
-        for (const RecoverRowsRun &run : plan.chunks[c].runs) {
-            if (!f((size_t)run.dev_row, (size_t)(lo + run.caller_row), (size_t)run.rows)) return false;
-        }
-        return true;
-    }
-    size_t caller_row(size_t c, size_t i) const { return (size_t)(lo + plan.chunks[c].row_caller[i]); }
-    static constexpr size_t proofs_per_row() { return CELLS_PER_EXT_BLOB; }
-    size_t tail_bytes() const { return max_rows() * FIELD_ELEMENTS_PER_BLOB * sizeof(Fr); }
-    C_KZG_RET proof_tail(dev::DeviceCtx *ctx, size_t c, Fr *d_e, uint8_t *, bool, uint8_t *d_proofs, uint8_t *d_tail) {
-        return fk20_proof_tail(ctx, rows(c), d_e, d_proofs, d_tail);
-    }
-    void tail_times(dev::DeviceCtx *ctx) const { dev::fk20_collect_times(ctx); }
-};
-
-// Structurally invalid rows get C_KZG_BADARGS here and no device row: they are neither copied, computed nor written
-static C_KZG_RET recover_rows_on(dev::DeviceCtx *ctx, Cell *recovered_cells, KZGProof *recovered_proofs, uint8_t *status,
-                                 const uint64_t *cell_indices, const Cell *cells, const uint64_t *row_start, uint64_t lo,
-                                 uint64_t hi) {
-    RecoverRowsPlan plan;
-    build_recover_rows_plan(plan, cell_indices, row_start + lo, hi - lo, RECOVER_CHUNK_ROWS);
-    if (status) {
-        for (uint64_t r = lo; r < hi; r++) status[r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
-    }
-    return recover_chunks(ctx, recovered_cells, recovered_proofs, status, plan.any_invalid ? C_KZG_BADARGS : C_KZG_OK,
-                          RecoverByRows{plan, cells, lo});
-}
-
-extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs,
-                                                                uint8_t *status, const uint64_t *cell_indices,
-                                                                const Cell *cells, const uint64_t *row_start,
-                                                                uint64_t num_rows, const KZGSettings *s) {
-    // eip7594.c:177-304 once per row [row_start[r], row_start[r + 1]) of the flat arrays
-    return guarded([&]() -> C_KZG_RET {
-        if (!settings_of(s)) return C_KZG_ERROR;
-        if (num_rows == 0) return C_KZG_OK;
-        if (recovered_cells == NULL && recovered_proofs == NULL) return C_KZG_BADARGS;
-        if (!slice_starts_ok(row_start, num_rows)) return C_KZG_BADARGS;
-        if (row_start[num_rows] != 0 && (cell_indices == NULL || cells == NULL)) return C_KZG_BADARGS;
-        // whole rows are the unit of splitting: contiguous runs of rows per device, chunks of rows on a device
-        return for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
-            return recover_rows_on(ctx, recovered_cells, recovered_proofs, status, cell_indices, cells, row_start, lo, hi);
-        });
-    });
-}
-
-// The source of the call by rows at coset size l = 2^e, m = 8192 >> e cosets a row: caller rows [lo, hi) of the call on
-// one device.  RecoverByRows with the coset size a parameter (plan: coset_recover_plan.hpp; kernels: coset_recover.hip),
-// and a proof tail of its own: the proofs of a recovered row are the coset openings of its blob, the first 4096 values
-// of the row's byte image, through dev::openings_enqueue in sub-batches of CKZG_HIP_COSET_CHUNK_BLOBS rows.  No
-// fixed-base table, at e = 6 neither.
+// The source of the calls by rows, at coset size l = 2^e, m = 8192 >> e cosets a row (a cell is a coset of 64: the
+// cell call is e = 6): caller rows [lo, hi) of the call on one device.  The plan (coset_recover_plan.hpp) names the
+// valid rows, their distinct sets and every coset's place; per chunk the GPU makes the per-coset values of Z and 1 / Z
+// for each distinct set (coset_recover.hip, coset_recover_factors.hpp) and all rows of the chunk, whatever they hold, go
+// through the transforms together.  No field arithmetic on the host.  The proof tail has two branches and one
+// predicate, fk20_tail(): at e == 6 the proofs of a row are the 128 cell proofs, FK20 over the fixed-base tables
+// (fk20_proof_tail, from the evaluations d_e); at every other e they are the coset openings of the row's blob, the
+// first 4096 values of the row's byte image, through dev::openings_enqueue in sub-batches of
+// CKZG_HIP_COSET_CHUNK_BLOBS rows.
 struct RecoverCosetsByRows {
     static constexpr size_t n = FIELD_ELEMENTS_PER_EXT_BLOB, SUB = CKZG_HIP_COSET_CHUNK_BLOBS;
     const CosetRecoverPlan &plan;
@@ -1802,6 +1712,7 @@ struct RecoverCosetsByRows {
     std::vector<uint32_t> meta;
 
     int e() const { return plan.e; }
+    bool fk20_tail() const { return plan.e == 6; }
     size_t m() const { return coset_recover_cosets(plan.e); }
     size_t item_bytes() const { return (size_t)32 << plan.e; }
     size_t chunks() const { return plan.chunks.size(); }
@@ -1817,7 +1728,7 @@ struct RecoverCosetsByRows {
         return d_zdom.p && d_zinv.p && d_meta.p;
     }
     C_KZG_RET prepare(dev::DeviceCtx *ctx) {
-        if (want_proofs) RC(dev::openings_xhat_ensure(ctx, e()));
+        if (want_proofs && !fk20_tail()) RC(dev::openings_xhat_ensure(ctx, e()));
         return C_KZG_OK;
     }
     C_KZG_RET cells_in(dev::DeviceCtx *ctx, size_t c, uint8_t *d_img, uint8_t *d_in) {
@@ -1853,13 +1764,16 @@ struct RecoverCosetsByRows {
     size_t caller_row(size_t c, size_t i) const { return (size_t)(lo + plan.chunks[c].row_caller[i]); }
     size_t proofs_per_row() const { return m(); }
     size_t sub_rows() const { return plan.max_rows < SUB ? plan.max_rows : SUB; }
-    // the blobs of a sub-batch, its flags, the scratch of the openings
+    // FK20: the coefficients of the rows; the openings: the blobs of a sub-batch, its flags, their scratch
     size_t tail_bytes() const {
+        if (fk20_tail()) return max_rows() * FIELD_ELEMENTS_PER_BLOB * sizeof(Fr);
         return sub_rows() * (BYTES_PER_BLOB + 4) + dev::openings_scratch_bytes(sub_rows()) + 3 * 256;
     }
     C_KZG_RET proof_tail(dev::DeviceCtx *ctx, size_t c, Fr *d_e, uint8_t *d_img, bool img_final, uint8_t *d_proofs,
                          uint8_t *d_tail) {
-        const size_t k = rows(c), sub = sub_rows();
+        const size_t k = rows(c);
+        if (fk20_tail()) return fk20_proof_tail(ctx, k, d_e, d_proofs, d_tail);
+        const size_t sub = sub_rows();
         uint8_t *d_blobs = d_tail;
         uint32_t *d_flags = reinterpret_cast<uint32_t *>(d_tail + (sub * BYTES_PER_BLOB + 255) / 256 * 256);
         uint8_t *scratch = reinterpret_cast<uint8_t *>(d_flags) + (sub * 4 + 255) / 256 * 256;
@@ -1876,22 +1790,45 @@ struct RecoverCosetsByRows {
         OKB(dev::sync_stream(ctx->stream) == hipSuccess);   // the proofs go back by copies that do not wait for the stream
         return C_KZG_OK;
     }
-    void tail_times(dev::DeviceCtx *) const {}
+    void tail_times(dev::DeviceCtx *ctx) const {
+        if (fk20_tail()) dev::fk20_collect_times(ctx);
+    }
 };
 
 static_assert(CKZG_HIP_COSET_MAX_LOG2 == COSET_RECOVER_MAX_LOG, "the header and coset_recover_plan.hpp name the same largest coset");
+static_assert(sizeof(Cell) == 64 * sizeof(Bytes32), "a cell is a coset of 64 values: the cell call is the coset call at e = 6");
 
 // Structurally invalid rows get C_KZG_BADARGS here and no device row: they are neither copied, computed nor written
 static C_KZG_RET recover_cosets_rows_on(dev::DeviceCtx *ctx, Bytes32 *recovered_evals, KZGProof *recovered_proofs,
                                         uint8_t *status, const uint64_t *coset_indices, const Bytes32 *evals,
-                                        const uint64_t *row_start, uint64_t lo, uint64_t hi, int e) {
+                                        const uint64_t *row_start, uint64_t lo, uint64_t hi, int e, size_t chunk_rows) {
     CosetRecoverPlan plan;
-    build_coset_recover_plan(plan, coset_indices, row_start + lo, hi - lo, e, CKZG_HIP_COSET_RECOVER_CHUNK_ROWS);
+    build_coset_recover_plan(plan, coset_indices, row_start + lo, hi - lo, e, chunk_rows);
     if (status) {
         for (uint64_t r = lo; r < hi; r++) status[r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
     }
     return recover_chunks(ctx, recovered_evals, recovered_proofs, status, plan.any_invalid ? C_KZG_BADARGS : C_KZG_OK,
                           RecoverCosetsByRows{plan, evals, lo, recovered_proofs != NULL});
+}
+
+extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs,
+                                                                uint8_t *status, const uint64_t *cell_indices,
+                                                                const Cell *cells, const uint64_t *row_start,
+                                                                uint64_t num_rows, const KZGSettings *s) {
+    // eip7594.c:177-304 once per row [row_start[r], row_start[r + 1]) of the flat arrays
+    return guarded([&]() -> C_KZG_RET {
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_rows == 0) return C_KZG_OK;
+        if (recovered_cells == NULL && recovered_proofs == NULL) return C_KZG_BADARGS;
+        if (!slice_starts_ok(row_start, num_rows)) return C_KZG_BADARGS;
+        if (row_start[num_rows] != 0 && (cell_indices == NULL || cells == NULL)) return C_KZG_BADARGS;
+        // whole rows are the unit of splitting: contiguous runs of rows per device, chunks of rows on a device
+        return for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+            return recover_cosets_rows_on(ctx, reinterpret_cast<Bytes32 *>(recovered_cells), recovered_proofs, status,
+                                          cell_indices, reinterpret_cast<const Bytes32 *>(cells), row_start, lo, hi, 6,
+                                          RECOVER_CHUNK_ROWS);
+        });
+    });
 }
 
 extern "C" C_KZG_RET ckzg_hip_recover_cosets_and_kzg_proofs_rows(Bytes32 *recovered_evals, KZGProof *recovered_proofs,
@@ -1908,7 +1845,7 @@ extern "C" C_KZG_RET ckzg_hip_recover_cosets_and_kzg_proofs_rows(Bytes32 *recove
         if (row_start[num_rows] != 0 && (coset_indices == NULL || evals == NULL)) return C_KZG_BADARGS;
         return for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
             return recover_cosets_rows_on(ctx, recovered_evals, recovered_proofs, status, coset_indices, evals, row_start,
-                                          lo, hi, (int)log2_coset);
+                                          lo, hi, (int)log2_coset, CKZG_HIP_COSET_RECOVER_CHUNK_ROWS);
         });
     });
 }

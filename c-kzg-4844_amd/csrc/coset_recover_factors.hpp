@@ -1,8 +1,10 @@
 // coset_recover_factors.hpp -- the vanishing polynomial of a set of missing cosets of size l = 2^e, coset by coset.
 //
-// recover_set_factors.hpp with the coset size a parameter.  The data is held in bit-reversed order: position
-// p = l c + k is the natural index brp13(p), whose low 13 - e bits are b(c) = brp_{13-e}(c), and x^l only sees those.
-// With w_m = w^l, Z is constant over each coset:
+// Recovery (recovery.c:200-365) multiplies the extended blob by Z over the domain and divides by Z over the coset
+// 7 w^i, Z being the polynomial that vanishes on the missing cosets: Z(x) = short(x^l), short the product of
+// (y - w_m^b(j)) over the missing cosets j, w_m = w^l (recovery.c:46-134 at l = 64).  The data is held in bit-reversed
+// order: position p = l c + k is the natural index brp13(p), whose low 13 - e bits are b(c) = brp_{13-e}(c), and x^l
+// only sees those.  So Z is constant over each coset:
 //   Z at every position of coset c          = prod over missing j of (      w_m^b(c) - w_m^b(j))
 //   Z on the shifted coset, every pos. of c = prod over missing j of (7^l w_m^b(c) - w_m^b(j))
 // The first is zero exactly for the missing cosets, the second never.  A set has up to m / 2 = 4096 missing cosets at

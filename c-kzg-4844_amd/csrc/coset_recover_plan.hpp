@@ -1,6 +1,7 @@
-// Index maps of ckzg_hip_recover_cosets_and_kzg_proofs_rows: recover_rows_plan.hpp with the coset size a parameter.
-// Plain C++ (no HIP, no field arithmetic): host_shim.cpp exposes the same maps to the CPU tests
-// (tests/test_coset_recover_cpu.py; the model is tests/coset_recover_expect.py).
+// Index maps of recovery by rows (ckzg_hip_recover_cosets_and_kzg_proofs_rows, and ckzg_hip_recover_cells_and_kzg_proofs_rows
+// at e = 6): which rows of the call are valid, which distinct sets of cosets they hold, and where every coset of a chunk
+// lands on the device.  Plain C++ (no HIP, no field arithmetic): host_shim.cpp exposes the same maps to the CPU tests
+// (tests/test_coset_recover_cpu.py, whose model is tests/coset_recover_expect.py; tests/test_recover_rows_cpu.py).
 //
 // Coset size l = 2^e, e <= 6; a row has m = 8192 >> e cosets.  The call is num_rows rows over flat coset_indices[] /
 // evals[]; row r is the slice [row_start[r], row_start[r + 1]).  A row is valid with m/2 .. m cosets, every index < m,
@@ -31,11 +32,14 @@ constexpr int COSET_RECOVER_MAX_LOG = 6;
 
 constexpr uint32_t coset_recover_cosets(int e) { return COSET_RECOVER_EXT >> e; }
 constexpr uint32_t coset_recover_mask_words(int e) { return coset_recover_cosets(e) / 32; }   // m >= 128
-// brp_{13-e}(c), c < m
+// brp_{13-e}(c), c < m: the 32-bit reversal (halves, bytes, nibbles, pairs, bits), shifted down
 constexpr uint32_t coset_recover_brp(uint32_t c, int e) {
-    uint32_t r = 0;
-    for (int b = 0; b < 13 - e; b++) r |= ((c >> b) & 1u) << (12 - e - b);
-    return r;
+    c = (c >> 16) | (c << 16);
+    c = ((c & 0xff00ff00u) >> 8) | ((c & 0x00ff00ffu) << 8);
+    c = ((c & 0xf0f0f0f0u) >> 4) | ((c & 0x0f0f0f0fu) << 4);
+    c = ((c & 0xccccccccu) >> 2) | ((c & 0x33333333u) << 2);
+    c = ((c & 0xaaaaaaaau) >> 1) | ((c & 0x55555555u) << 1);
+    return c >> (19 + e);
 }
 
 // ---- the factor launch: `parts` lanes share the product of one coset (constexpr: the kernel calls these too) ----
@@ -99,10 +103,20 @@ inline uint64_t coset_recover_mask_hash(const uint32_t *w, size_t n) {
     return h;
 }
 
+// the missing list of one set, appended to `miss`: mask as set_mask holds it (m / 32 words)
+inline void coset_recover_missing(std::vector<uint32_t> &miss, const uint32_t *mask, int e) {
+    const size_t at = miss.size();
+    miss.resize(at + coset_recover_cosets(e));   // room for every coset, cut back below: no growth check per entry
+    uint32_t *out = miss.data() + at;
+    for (uint32_t w = 0; w < coset_recover_mask_words(e); w++)
+        for (uint32_t z = ~mask[w]; z; z &= z - 1) *out++ = coset_recover_brp(32 * w + (uint32_t)__builtin_ctz(z), e) << e;
+    miss.resize((size_t)(out - miss.data()));
+}
+
 // row_start must have passed slice_starts_ok; e <= COSET_RECOVER_MAX_LOG
 inline void build_coset_recover_plan(CosetRecoverPlan &p, const uint64_t *coset_indices, const uint64_t *row_start,
                                      uint64_t num_rows, int e, size_t chunk_rows) {
-    const uint32_t m = coset_recover_cosets(e), W = coset_recover_mask_words(e), l = 1u << e;
+    const uint32_t m = coset_recover_cosets(e), W = coset_recover_mask_words(e);
     p.e = e;
     p.valid.assign((size_t)num_rows, 0);
     p.chunks.clear();
@@ -124,9 +138,11 @@ inline void build_coset_recover_plan(CosetRecoverPlan &p, const uint64_t *coset_
     for (uint64_t r = 0; r < num_rows; r++) {
         const uint64_t a = row_start[r], n = row_start[r + 1] - a;
         bool ok = n >= m / 2 && n <= m;
+        mask.assign(W, 0);
         for (uint64_t i = 0; ok && i < n; i++) {
             const uint64_t c = coset_indices[a + i];
             if (c >= m || (i > 0 && c <= coset_indices[a + i - 1])) ok = false;
+            else mask[c >> 5] |= 1u << (c & 31);
         }
         p.valid[(size_t)r] = ok ? 1 : 0;
         if (!ok) {
@@ -134,8 +150,6 @@ inline void build_coset_recover_plan(CosetRecoverPlan &p, const uint64_t *coset_
             prev_valid = false;
             continue;
         }
-        mask.assign(W, 0);
-        for (uint64_t i = 0; i < n; i++) mask[coset_indices[a + i] >> 5] |= 1u << (coset_indices[a + i] & 31);
         if (ch && ch->rows() == chunk_rows) close();
         if (!ch) {
             p.chunks.emplace_back();
@@ -158,8 +172,7 @@ inline void build_coset_recover_plan(CosetRecoverPlan &p, const uint64_t *coset_
             set = (uint32_t)ch->sets();
             ids.emplace(h, set);
             ch->set_mask.insert(ch->set_mask.end(), mask.begin(), mask.end());
-            for (uint32_t j = 0; j < m; j++)
-                if (!((mask[j >> 5] >> (j & 31)) & 1u)) ch->miss.push_back(l * coset_recover_brp(j, e));
+            coset_recover_missing(ch->miss, mask.data(), e);
             ch->miss_start.push_back((uint32_t)ch->miss.size());
         }
         ch->row_caller.push_back(r);

@@ -578,17 +578,9 @@ int blob_group_scalars_enqueue(DeviceCtx *ctx, uint32_t *d_sc, Fr *d_ry, const u
                                const Fr *d_r, const Fr *d_z, const Fr *d_y, size_t n, size_t ngroups);
 int fr_mul_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n, size_t period);
 int fr_div_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n);
-// The rows form of recovery (ckzg_hip_recover_cells_and_kzg_proofs_rows; index maps: recover_rows_plan.hpp).  All
-// enqueue-only, on ctx->stream.
-//   d_z_domain[s][128], d_z_coset_inv[s][128] <- Z over the domain and 1 / Z over the coset of set s, per cell
-int recover_set_factors_enqueue(DeviceCtx *ctx, Fr *d_z_domain, Fr *d_z_coset_inv, const uint32_t *d_set_mask, size_t nsets);
-//   cell i (2048 B) -> image[cell_dst[i]] (cell_dst = device row * 128 + column; zero-filled by the caller)
-int scatter_cells_rows_enqueue(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *d_cells, const uint32_t *d_cell_dst,
-                               size_t ncells);
-//   a[row][p] *= f[row_set[row]][p / 64] over nrows rows of 8192
-int fr_mul_cell_factor_enqueue(DeviceCtx *ctx, Fr *d_a, const Fr *d_f, const uint32_t *d_row_set, size_t nrows);
-// coset_recover.hip: the same three at coset size 2^e, m = 8192 >> e cosets a row (ckzg_hip_recover_cosets_and_kzg_proofs_rows;
-// index maps: coset_recover_plan.hpp).  All enqueue-only, on ctx->stream.
+// coset_recover.hip: recovery by rows at coset size 2^e, m = 8192 >> e cosets a row (ckzg_hip_recover_cosets_and_kzg_proofs_rows,
+// and ckzg_hip_recover_cells_and_kzg_proofs_rows at e = 6; index maps: coset_recover_plan.hpp).  All enqueue-only, on
+// ctx->stream.
 //   d_z_domain[s][m], d_z_coset_inv[s][m] <- Z over the domain and 1 / Z over the shifted coset of set s, per coset;
 //   d_miss[d_miss_start[s] .. d_miss_start[s + 1]): the root indices of the set's missing cosets; parts: lanes per coset
 int coset_recover_factors_enqueue(DeviceCtx *ctx, Fr *d_z_domain, Fr *d_z_coset_inv, const uint32_t *d_miss,

@@ -722,79 +722,21 @@ extern "C" long hs_blob_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_t
     return (long)p.total;
 }
 
-// ---- ckzg_hip_recover_cells_and_kzg_proofs_rows: the index maps the product builds (recover_rows_plan.hpp) laid
-// out per caller row and per caller cell, and the per-cell factor arithmetic of k_recover_set_factors
-// (recover_set_factors.hpp: the very function the kernel calls) replayed for one set, so that both can be checked
-// without a GPU (tests/test_recover_rows_cpu.py).
+// ---- recovery by rows at coset size 2^e: the index maps the product builds (coset_recover_plan.hpp) laid out per
+// caller row and per caller coset, and the per-coset factor arithmetic of k_coset_recover_factors
+// (coset_recover_factors.hpp: the very function the kernel calls) replayed for one set, so that both can be checked
+// without a GPU (tests/test_coset_recover_cpu.py; at e = 6, in the cell call's terms, tests/test_recover_rows_cpu.py).
 // Plan: per caller row valid / chunk / device row / set id inside the chunk / the set's mask as the plan stores it
-// (row_mask [num_rows][4]); per caller cell its position in the chunk's device input (through the copy runs) and the
-// scatter target stored for that position, 0xffffffff for the cells of invalid rows; chunk_info [chunks][4] = rows,
-// cells, sets, all_full.  Returns the number of chunks, -1 for a malformed row_start, -2 beyond cap_chunks. ----
-#include "recover_rows_plan.hpp"
-#include "recover_set_factors.hpp"
-extern "C" long hs_recover_rows_plan(uint8_t *valid, uint32_t *row_chunk, uint32_t *row_dev, uint32_t *row_set,
-                                     uint32_t *row_mask, uint32_t *cell_pos, uint32_t *cell_dst, uint32_t *chunk_info,
-                                     size_t cap_chunks, const uint64_t *cell_indices, const uint64_t *row_start,
-                                     uint64_t num_rows, size_t chunk_rows) {
-    if (!slice_starts_ok(row_start, num_rows)) return -1;
-    RecoverRowsPlan p;
-    build_recover_rows_plan(p, cell_indices, row_start, num_rows, chunk_rows);
-    if (p.chunks.size() > cap_chunks) return -2;
-    for (uint64_t r = 0; r < num_rows; r++) {
-        valid[r] = p.valid[(size_t)r];
-        row_chunk[r] = row_dev[r] = row_set[r] = 0xffffffffu;
-        for (int w = 0; w < 4; w++) row_mask[4 * r + w] = 0;
-    }
-    for (uint64_t i = 0; i < row_start[num_rows]; i++) cell_pos[i] = cell_dst[i] = 0xffffffffu;
-    for (size_t c = 0; c < p.chunks.size(); c++) {
-        const RecoverRowsChunk &ch = p.chunks[c];
-        chunk_info[4 * c] = (uint32_t)ch.rows();
-        chunk_info[4 * c + 1] = (uint32_t)ch.cells();
-        chunk_info[4 * c + 2] = (uint32_t)ch.sets();
-        chunk_info[4 * c + 3] = ch.all_full ? 1 : 0;
-        for (size_t d = 0; d < ch.rows(); d++) {
-            const uint64_t r = ch.row_caller[d];
-            row_chunk[r] = (uint32_t)c;
-            row_dev[r] = (uint32_t)d;
-            row_set[r] = ch.row_set[d];
-            for (int w = 0; w < 4; w++) row_mask[4 * r + w] = ch.set_mask[4 * ch.row_set[d] + w];
-        }
-        for (const RecoverRowsRun &run : ch.runs) {
-            for (uint32_t j = 0; j < run.cells; j++) {
-                cell_pos[run.src_cell + j] = run.dev_cell + j;
-                cell_dst[run.src_cell + j] = ch.cell_dst[run.dev_cell + j];
-            }
-        }
-    }
-    return (long)p.chunks.size();
-}
-
-// Field elements cross as canonical little-endian limbs: roots w^i [8193], seven64 = 7^64; out: Z over the domain
-// [128] and 1 / Z over the coset [128] of the set `mask` (bit c of word c / 32 = cell c is held).
-extern "C" void hs_recover_set_factors(uint32_t *z_domain, uint32_t *z_coset_inv, const uint32_t *mask,
-                                       const uint32_t *roots_raw, const uint32_t *seven64_raw) {
-    std::vector<Fr> roots(8193);
-    for (size_t i = 0; i < roots.size(); i++) roots[i] = from_raw<FrParams>(roots_raw + 8 * i);
-    const Fr seven64 = from_raw<FrParams>(seven64_raw);
-    for (uint32_t c = 0; c < 128; c++) {
-        Fr zd, zc;
-        recover_set_products(zd, zc, mask, c, roots.data(), seven64);
-        to_raw<FrParams>(z_domain + 8 * c, zd);
-        to_raw<FrParams>(z_coset_inv + 8 * c, fr_inv_safegcd(zc));
-    }
-}
-
-// ---- ckzg_hip_recover_cosets_and_kzg_proofs_rows: the same two at coset size 2^e (coset_recover_plan.hpp,
-// coset_recover_factors.hpp; tests/test_coset_recover_cpu.py).
-// Plan: as hs_recover_rows_plan, with row_mask [num_rows][m / 32], the per-coset position and scatter target, and
-// chunk_info [chunks][5] = rows, cosets, sets, all_full, entries of the missing lists.  Returns the number of chunks, -1
+// (row_mask [num_rows][m / 32]); per caller coset its position in the chunk's device input (through the copy runs) and
+// the scatter target stored for that position, 0xffffffff for the cosets of invalid rows; chunk_info [chunks][info] =
+// rows, cosets, sets, all_full and, where info is 5, the entries of the missing lists.  Returns the number of chunks, -1
 // for a malformed row_start or e > 6, -2 beyond cap_chunks. ----
 #include "coset_recover_plan.hpp"
 #include "coset_recover_factors.hpp"
-extern "C" long hs_coset_recover_plan(uint8_t *valid, uint32_t *row_chunk, uint32_t *row_dev, uint32_t *row_set,
-                                      uint32_t *row_mask, uint32_t *coset_pos, uint32_t *coset_dst, uint32_t *chunk_info,
-                                      size_t cap_chunks, const uint64_t *coset_indices, const uint64_t *row_start,
-                                      uint64_t num_rows, int e, size_t chunk_rows) {
+static long coset_recover_plan_out(uint8_t *valid, uint32_t *row_chunk, uint32_t *row_dev, uint32_t *row_set,
+                                   uint32_t *row_mask, uint32_t *coset_pos, uint32_t *coset_dst, uint32_t *chunk_info,
+                                   size_t info, size_t cap_chunks, const uint64_t *coset_indices,
+                                   const uint64_t *row_start, uint64_t num_rows, int e, size_t chunk_rows) {
     if (e < 0 || e > COSET_RECOVER_MAX_LOG || !slice_starts_ok(row_start, num_rows)) return -1;
     const uint32_t W = coset_recover_mask_words(e);
     CosetRecoverPlan p;
@@ -808,11 +750,11 @@ extern "C" long hs_coset_recover_plan(uint8_t *valid, uint32_t *row_chunk, uint3
     for (uint64_t i = 0; i < row_start[num_rows]; i++) coset_pos[i] = coset_dst[i] = 0xffffffffu;
     for (size_t c = 0; c < p.chunks.size(); c++) {
         const CosetRecoverChunk &ch = p.chunks[c];
-        chunk_info[5 * c] = (uint32_t)ch.rows();
-        chunk_info[5 * c + 1] = (uint32_t)ch.cosets();
-        chunk_info[5 * c + 2] = (uint32_t)ch.sets();
-        chunk_info[5 * c + 3] = ch.all_full ? 1 : 0;
-        chunk_info[5 * c + 4] = (uint32_t)ch.miss.size();
+        chunk_info[info * c] = (uint32_t)ch.rows();
+        chunk_info[info * c + 1] = (uint32_t)ch.cosets();
+        chunk_info[info * c + 2] = (uint32_t)ch.sets();
+        chunk_info[info * c + 3] = ch.all_full ? 1 : 0;
+        if (info > 4) chunk_info[info * c + 4] = (uint32_t)ch.miss.size();
         for (size_t d = 0; d < ch.rows(); d++) {
             const uint64_t r = ch.row_caller[d];
             row_chunk[r] = (uint32_t)c;
@@ -828,6 +770,21 @@ extern "C" long hs_coset_recover_plan(uint8_t *valid, uint32_t *row_chunk, uint3
         }
     }
     return (long)p.chunks.size();
+}
+extern "C" long hs_coset_recover_plan(uint8_t *valid, uint32_t *row_chunk, uint32_t *row_dev, uint32_t *row_set,
+                                      uint32_t *row_mask, uint32_t *coset_pos, uint32_t *coset_dst, uint32_t *chunk_info,
+                                      size_t cap_chunks, const uint64_t *coset_indices, const uint64_t *row_start,
+                                      uint64_t num_rows, int e, size_t chunk_rows) {
+    return coset_recover_plan_out(valid, row_chunk, row_dev, row_set, row_mask, coset_pos, coset_dst, chunk_info, 5,
+                                  cap_chunks, coset_indices, row_start, num_rows, e, chunk_rows);
+}
+// the cell call's plan: e = 6, so row_mask [num_rows][4], and chunk_info [chunks][4]
+extern "C" long hs_recover_rows_plan(uint8_t *valid, uint32_t *row_chunk, uint32_t *row_dev, uint32_t *row_set,
+                                     uint32_t *row_mask, uint32_t *cell_pos, uint32_t *cell_dst, uint32_t *chunk_info,
+                                     size_t cap_chunks, const uint64_t *cell_indices, const uint64_t *row_start,
+                                     uint64_t num_rows, size_t chunk_rows) {
+    return coset_recover_plan_out(valid, row_chunk, row_dev, row_set, row_mask, cell_pos, cell_dst, chunk_info, 4,
+                                  cap_chunks, cell_indices, row_start, num_rows, 6, chunk_rows);
 }
 
 // the missing list of set `set` of chunk `chunk` of the same plan, as the device gets it: the number of entries (up to
@@ -890,6 +847,17 @@ extern "C" void hs_coset_recover_factors(uint32_t *z_domain, uint32_t *z_coset_i
         to_raw<FrParams>(z_domain + 8 * i, pd[0]);
         to_raw<FrParams>(z_coset_inv + 8 * i, fr_inv_safegcd(pc[0]));
     }
+}
+
+// The cell call's factors: all 128 cells of the set `mask` (4 words, bit c of word c / 32 = cell c is held) at e = 6,
+// with the parts the product takes for a chunk of one set; seven64 = 7^64.  out: [128] each.
+extern "C" void hs_recover_set_factors(uint32_t *z_domain, uint32_t *z_coset_inv, const uint32_t *mask,
+                                       const uint32_t *roots_raw, const uint32_t *seven64_raw) {
+    std::vector<uint32_t> miss, cells(128);
+    coset_recover_missing(miss, mask, 6);
+    for (uint32_t c = 0; c < 128; c++) cells[c] = c;
+    hs_coset_recover_factors(z_domain, z_coset_inv, miss.data(), (uint32_t)miss.size(), cells.data(), 128, 6,
+                             coset_recover_parts(1, 6), roots_raw, seven64_raw);
 }
 
 // ---- raw-limb entry points: the F28 operations at the bound combinations the group law instantiates

@@ -14,7 +14,6 @@
 #include "g1_quad.hpp"
 #include "fr_inv.hpp"
 #include "fr29.hpp"
-#include "recover_set_factors.hpp"
 
 namespace ckzg {
 namespace dev {
@@ -1282,72 +1281,6 @@ int fr_div_inplace_device(DeviceCtx *ctx, Fr *d_a, const Fr *d_b, size_t n) {
     size_t threads = (n + 15) / 16;
     hipLaunchKernelGGL(k_fr_div_inplace, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, ctx->stream,
                        d_a, d_b, n);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// ckzg_hip_recover_cells_and_kzg_proofs_rows: rows that hold different cells in one pass (index maps:
-// recover_rows_plan.hpp, whose field names the parameters carry; arithmetic: recover_set_factors.hpp)
-// ------------------------------------------------------------------------------------------
-
-// Z over the domain and 1 / Z over the coset for every distinct set of a chunk, one value per cell.  One workgroup of
-// 128 lanes per set, lane = cell: the loop over the missing cells is uniform across the workgroup (no divergence),
-// the two products of a lane are independent chains of at most 64 factors each, and every lane inverts its own coset
-// value.  Lanes run in lockstep, so the 64 inversions of a wave cost the wave one inversion; Montgomery's trick would
-// have to gather a run of values into one lane first, which lengthens that lane's product chain by the run.
-__global__ __launch_bounds__(128) void k_recover_set_factors(Fr *z_domain, Fr *z_coset_inv, const uint32_t *set_mask,
-                                                             const Fr *roots, const Fr *shift) {
-    const uint32_t s = blockIdx.x, c = threadIdx.x;
-    uint32_t mask[4];
-#pragma unroll
-    for (int w = 0; w < 4; w++) mask[w] = set_mask[4 * s + w];
-    Fr zd, zc;
-    recover_set_products(zd, zc, mask, c, roots, vld_fr(shift + 64));
-    vst_fr(z_domain + s * 128 + c, zd);
-    vst_fr(z_coset_inv + s * 128 + c, fr_inv_dev(zc));
-}
-
-// cell i of the chunk's input (2048 B) -> image[cell_dst[i]], cell_dst = device row * 128 + column; the image is zero
-// elsewhere.  16 bytes per lane.
-__global__ void k_scatter_cells_rows(uint4 *image, const uint4 *cells, const uint32_t *cell_dst, size_t total_u4) {
-    size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (g >= total_u4) return;
-    constexpr uint32_t U4 = 2048 / 16;
-    image[(size_t)cell_dst[g / U4] * U4 + (uint32_t)(g % U4)] = cells[g];
-}
-
-// a[g] *= f[row_set[g / 8192]][(g % 8192) / 64]: a wave is one cell, so its 64 lanes read one factor
-__global__ void k_fr_mul_cell_factor(Fr *a, const Fr *f, const uint32_t *row_set, size_t n) {
-    size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    const uint32_t set = row_set[g >> 13], cell = (uint32_t)(g >> 6) & 127u;
-    vst_fr(a + g, mul(vld_fr(a + g), vld_fr(f + (size_t)set * 128 + cell)));
-}
-
-int recover_set_factors_enqueue(DeviceCtx *ctx, Fr *d_z_domain, Fr *d_z_coset_inv, const uint32_t *d_set_mask, size_t nsets) {
-    if (!nsets) return 0;
-    hipLaunchKernelGGL(k_recover_set_factors, dim3((unsigned)nsets), dim3(128), 0, ctx->stream, d_z_domain, d_z_coset_inv,
-                       d_set_mask, ctx->d_roots, ctx->d_shift);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int scatter_cells_rows_enqueue(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *d_cells, const uint32_t *d_cell_dst,
-                               size_t ncells) {
-    const size_t u4 = ncells * (2048 / 16);
-    if (!u4) return 0;
-    hipLaunchKernelGGL(k_scatter_cells_rows, dim3((unsigned)((u4 + 255) / 256)), dim3(256), 0, ctx->stream,
-                       reinterpret_cast<uint4 *>(d_image), reinterpret_cast<const uint4 *>(d_cells), d_cell_dst, u4);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int fr_mul_cell_factor_enqueue(DeviceCtx *ctx, Fr *d_a, const Fr *d_f, const uint32_t *d_row_set, size_t nrows) {
-    const size_t n = nrows * 8192;
-    if (!n) return 0;
-    hipLaunchKernelGGL(k_fr_mul_cell_factor, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_a, d_f,
-                       d_row_set, n);
     HIP_TRY(hipGetLastError());
     return 0;
 }

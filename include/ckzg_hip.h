@@ -566,9 +566,11 @@ C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitm
  * Returns C_KZG_BADARGS if any row is invalid, or -- with nothing written and nothing launched -- for log2_coset > 6, a
  * malformed row_start, both outputs NULL, or NULL inputs with work to do; C_KZG_OK otherwise (also for num_rows == 0);
  * C_KZG_MALLOC / C_KZG_ERROR if the call itself failed.  With several devices, contiguous runs of whole rows go to each.
- * At e = 6 the call is byte for byte ckzg_hip_recover_cells_and_kzg_proofs_rows, status included; it gets there through
- * its own factor kernel and through the coset openings, not through the FK20 tables.
- * How: the transform sequence of recovery does not depend on e and is shared with the two cell calls; what depends on e
+ * At e = 6 the call is ckzg_hip_recover_cells_and_kzg_proofs_rows: the same code (one source of the chunk pipeline, one
+ * plan, one set of kernels), status included, and its proofs are that call's -- FK20 over the fixed-base tables -- so
+ * ckzg_hip_last_kernel_ms entries 1 and 4 are written by this call at e = 6 as they are by that one.  The two entries
+ * differ only in the rows of a chunk (CKZG_HIP_COSET_RECOVER_CHUNK_ROWS here, 512 there).
+ * How: the transform sequence of recovery does not depend on e and is shared with the same-cells batch; what depends on e
  * is the vanishing polynomial of the missing set, constant over a coset: 2 m values per DISTINCT set of a chunk (a hash
  * over the m-bit masks on the host), each a product of up to m / 2 factors, evaluated directly on the GPU
  * (coset_recover.hip: O(m^2) products per distinct set, 67 M at e = 0, split over several lanes per coset where the sets
@@ -577,17 +579,21 @@ C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitm
  * (64 MiB from 9 rows on, two alternating) + 32 MiB of field elements, at most 64 MiB of factors (e = 0, 128 distinct
  * sets: 512 KB a set; 8 KB a set at e = 6) and, with proofs, 2 x 48 MiB of proofs at e = 0 plus the openings' scratch
  * for CKZG_HIP_COSET_CHUNK_BLOBS rows (5.4 MB of HBM a row).
- * NOT here: device pointers, and a fixed-base-table route for the proofs -- they are the coset openings of the recovered
- * blob at every e, one extra transform to bytes and back a row.
+ * NOT here: device pointers, and a fixed-base-table route for the proofs at e < 6 -- there they are the coset openings
+ * of the recovered blob, one extra transform to bytes and back a row.
  * Measured (profiles/coset_recover_bench.json): medians of 20 (of 5 where a call takes more than 0.4 s) and minima of
- * the wall time, default tables, a fresh process, rows of 8 blobs that hold m / 2 + 3 cosets each.
+ * the wall time, default tables, a fresh process, rows of 8 blobs that hold m / 2 + 3 cosets each.  The e = 6 rows were
+ * taken before the two calls were merged, when the cell call had kernels of its own and this call made its proofs at
+ * e = 6 by the openings; they are why the merge kept this call's kernels and that call's proof tail.
  *   e = 6  evaluations only: 0.89 (min 0.88) ms for 16 rows of one set, 3.43 (3.35) / 3.53 (3.43) / 3.72 (3.60) ms for 256
  *          rows of 1 / 16 / 256 distinct sets, against 0.98 (0.94) and 3.96 (3.86) / 3.89 (3.84) / 3.96 (3.88) ms for
  *          ckzg_hip_recover_cells_and_kzg_proofs_rows on the same rows (a build of the parent commit in the same
  *          process): this call's median is below that call's minimum in all five shapes, by 4 to 11 %.  With proofs:
- *          19.9 (19.6) ms for 16 rows and 308.6 (307.0) ms for 256 against 5.07 (4.98) and 24.2 (23.5) ms: this call is
- *          NOT faster, it is 4x and 13x slower -- that call's proofs are FK20 over the fixed-base tables, this call's
- *          are ladders.  Use ckzg_hip_recover_cells_and_kzg_proofs_rows for cells of 64 with proofs.
+ *          19.9 (19.6) ms for 16 rows and 308.6 (307.0) ms for 256 against 5.07 (4.98) and 24.2 (23.5) ms: this call
+ *          was 4x and 13x slower -- that call's proofs are FK20 over the fixed-base tables, this call's were ladders.
+ *          After the merge (profiles/recover_merge_ab.json: fk20_wbits 12, proof_wbits 13, 16 distinct sets):
+ *          4.58 ms for 16 rows and 29.3 ms for 256 through this entry (19.9 and 306.2 ms on the parent commit's build),
+ *          4.60 and 20.0 ms through the cell entry, whose chunks are 512 rows: 256 rows are two chunks here, one there.
  *   e = 0 .. 5 have no alternative in the library.  Evaluations only, 256 rows of 1 / 16 / 256 distinct sets:
  *          e = 0  8.2 / 39.6 / 227.8 ms, e = 1  5.3 / 14.9 / 65.9, e = 2  3.9 / 6.7 / 22.0, e = 3  3.7 / 4.3 / 9.0,
  *          e = 4  3.5 / 3.6 / 5.4, e = 5  3.4 / 3.5 / 4.0; 16 rows of 1 / 16 sets: e = 0  2.4 / 16.9, e = 1  1.26 / 6.25,

@@ -3,7 +3,9 @@
 //   verify.hip  eval_blob_bytes_batch_device (k_eval_tree), eval_quotient_batch_device (k_eval_barycentric<true>,
 //               k_quotient_in_domain), group_cell_aggregate_device (k_cell_aggregate),
 //               group_interp_sum_device, fr_mul_inplace_device, fr_div_inplace_device,
-//               recover_set_factors_enqueue, fr_mul_cell_factor_enqueue, scatter_cells_device, scatter_cells_rows_enqueue
+//               scatter_cells_device
+//   coset_recover.hip  coset_recover_factors_enqueue, fr_mul_coset_factor_enqueue, scatter_cosets_rows_enqueue at cosets
+//               of 64: the factors, the multiplication and the scatter of recovery by rows, in the cell call's terms
 //   coset_verify.hip  coset_aggregate_device, coset_interp_device at cosets of 64: the aggregation and interpolation of a
 //               single cell batch
 // They sit between the arithmetic that tests/test_gpu_fields.py pins and the entry points that are compared with the
@@ -27,6 +29,7 @@
 #include <cstring>
 #include "dev_shim_common.hpp"
 #include "device.hpp"
+#include "coset_recover_plan.hpp"
 #include "coset_verify_plan.hpp"
 
 using namespace ckzg;
@@ -260,12 +263,21 @@ int ps_recover_set_factors(uint32_t *z_domain, uint32_t *z_coset_inv, const uint
     const Tables tb(roots);
     const size_t ne = (nsets + 1) * 128;
     std::vector<Fr> zd = fr_in(z_domain, ne), zi = fr_in(z_coset_inv, ne);
-    std::vector<Arg> args = {{zd.data(), zd.data(), ne * 32, nullptr}, {zi.data(), zi.data(), ne * 32, nullptr}, {masks, nullptr, nsets * 16, nullptr}};
+    std::vector<uint32_t> miss, miss_start = {0};   // the stage takes the sets as the plan hands them over
+    for (size_t s = 0; s < nsets; s++) {
+        coset_recover_missing(miss, masks + 4 * s, CELL_LOG);
+        miss_start.push_back((uint32_t)miss.size());
+    }
+    miss.push_back(0);   // no empty upload where every set is full; no set owns this entry
+    std::vector<Arg> args = {{zd.data(), zd.data(), ne * 32, nullptr}, {zi.data(), zi.data(), ne * 32, nullptr},
+                             {miss.data(), nullptr, miss.size() * 4, nullptr}, {miss_start.data(), nullptr, miss_start.size() * 4, nullptr}};
     const size_t at = tb.push(args);
     const int run = run_bounded(args, [&](hipStream_t st) {
         DeviceCtx ctx;
         *rc = stage_ctx(ctx, st, args, at);
-        if (*rc == 0) *rc = recover_set_factors_enqueue(&ctx, (Fr *)args[0].dev, (Fr *)args[1].dev, (const uint32_t *)args[2].dev, nsets);
+        if (*rc == 0)
+            *rc = coset_recover_factors_enqueue(&ctx, (Fr *)args[0].dev, (Fr *)args[1].dev, (const uint32_t *)args[2].dev,
+                                                (const uint32_t *)args[3].dev, nsets, CELL_LOG, coset_recover_parts(nsets, CELL_LOG));
     });
     if (run) return run;
     fr_out(z_domain, zd);
@@ -284,7 +296,7 @@ int ps_fr_mul_cell_factor(uint32_t *a, const uint32_t *f, size_t nsets, const ui
     const int run = run_bounded(args, [&](hipStream_t st) {
         DeviceCtx ctx;
         ctx.stream = st;
-        *rc = fr_mul_cell_factor_enqueue(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const uint32_t *)args[2].dev, nrows);
+        *rc = fr_mul_coset_factor_enqueue(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const uint32_t *)args[2].dev, nrows, CELL_LOG);
     });
     if (run) return run;
     fr_out(a, av);
@@ -317,7 +329,7 @@ int ps_scatter_cells_rows(uint8_t *image, size_t image_rows, const uint8_t *cell
     return run_bounded(args, [&](hipStream_t st) {
         DeviceCtx ctx;
         ctx.stream = st;
-        *rc = scatter_cells_rows_enqueue(&ctx, (uint8_t *)args[0].dev, (const uint8_t *)args[1].dev, (const uint32_t *)args[2].dev, ncells);
+        *rc = scatter_cosets_rows_enqueue(&ctx, (uint8_t *)args[0].dev, (const uint8_t *)args[1].dev, (const uint32_t *)args[2].dev, ncells, CELL_LOG);
     });
 }
 

@@ -1,7 +1,7 @@
 """What the stages that move and combine vectors of Fr must produce, as Python integers: the transforms of ntt.hip,
 evaluation in evaluation form and the opening quotient (verify.hip: k_eval_tree, k_eval_barycentric,
-k_quotient_in_domain), the two products of recover_set_factors.hpp, and the aggregate and interpolation sums as the
-kernels' comments write them.  Nothing here reads the library under test.  Shared by tests/test_gpu_poly_stages.py (the
+k_quotient_in_domain), the two products of coset_recover_factors.hpp at cosets of 64, and the aggregate and
+interpolation sums as the kernels' comments write them.  Nothing here reads the library under test.  Shared by tests/test_gpu_poly_stages.py (the
 device stages) and tests/test_poly_expect_cpu.py, which checks each reference by a second route."""
 from rlc_expect import R, brev7
 
@@ -143,7 +143,7 @@ def quotient(poly, z, dom, index=None):
     return y, m, q
 
 
-# ---- recovery: recover_set_factors.hpp ----
+# ---- recovery: coset_recover_factors.hpp at cosets of 64 ----
 
 SEVEN64 = pow(7, 64, R)
 

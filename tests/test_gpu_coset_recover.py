@@ -161,6 +161,8 @@ def test_invalid_rows_keep_the_sentinel_and_their_neighbours_are_recovered(hip, 
 
 
 def test_at_e6_the_call_is_the_cell_call_by_rows_and_the_oracle(hip, oracle, full):
+    """The two entries run one code path at e = 6 (they differ in the rows of a chunk), so their equality is an identity
+    check of the entries' argument handling; what pins the bytes is the oracle."""
     e = 6
     rows, blobs = _mixed_with_invalid(full, e)
     ret, ev, pr, st = raw_call(hip, rows, e)
@@ -271,3 +273,76 @@ def test_recovered_cosets_verify(hip, full):
     wrong = list(args[2])
     wrong[3] = wrong[4]
     assert hip.verify_coset_kzg_proof_batch(args[0], args[1], wrong, args[3], e) is False
+
+
+# ---- e = 6 through the coset entry: the cell call's code, FK20 proof tail included ----
+
+E6_ROWS = [(0, "random_half"), (1, "first_half_missing"), None, (0, "held_70"), (1, "all")]
+
+
+@pytest.fixture(scope="module")
+def e6(oracle, full):
+    """(blob, set name) -> (indices, held bytes, the oracle's recovered row, the oracle's 128 proofs) for the valid rows of
+    E6_ROWS: two distinct half-sets, a row of 70 cosets and a full row.  The oracle runs once per row."""
+    sets = dict(held_sets(6), held_70=sorted(random.Random(46).sample(range(128), 70)))
+    assert len(sets["random_half"]) == len(sets["first_half_missing"]) == 64 and sets["random_half"] != sets["first_half_missing"]
+    out = {}
+    for key in E6_ROWS:
+        if key is None:
+            continue
+        b, name = key
+        idx = sets[name]
+        data = cut(full[b]["ext"], idx, 6)
+        ec, ep = oracle.recover_cells_and_kzg_proofs(idx, [data[2048 * i:2048 * (i + 1)] for i in range(len(idx))])
+        out[key] = (idx, data, b"".join(ec), b"".join(ep))
+    return out
+
+
+def _e6_rows(e6, keys):
+    """rows for raw_call; None is the invalid row: 63 cosets"""
+    return [(e6[k][0], e6[k][1]) if k is not None else (list(range(63)), bytes(63 * 2048)) for k in keys]
+
+
+def test_e6_proofs_only_with_an_invalid_row_in_the_middle(hip, e6):
+    """recovered_evals NULL: the FK20 tail on an image that is never made final"""
+    ret, none_e, pr, st = raw_call(hip, _e6_rows(e6, E6_ROWS), 6, False, True)
+    assert ret == 1 and none_e is None
+    assert st == [0, 0, 1, 0, 0]
+    for r, k in enumerate(E6_ROWS):
+        want = e6[k][3] if k is not None else b"\xa5" * (128 * 48)
+        assert pr[r * 128 * 48:(r + 1) * 128 * 48] == want, "proofs of row %d" % r
+
+
+def test_e6_both_outputs_are_the_same_bytes_through_both_entries(hip, e6):
+    """one code path behind both entries: their equality checks the entries, the oracle pins the bytes"""
+    rows = _e6_rows(e6, E6_ROWS)
+    ret, ev, pr, st = raw_call(hip, rows, 6)
+    nr = len(rows)
+    idx = [i for ix, _ in rows for i in ix]
+    start = [0]
+    for ix, _ in rows:
+        start.append(start[-1] + len(ix))
+    f = hip.lib.ckzg_hip_recover_cells_and_kzg_proofs_rows
+    f.restype = C.c_int
+    fill = lambda n: (C.c_char * n).from_buffer(bytearray([0xa5]) * n)
+    rc2, rp2, st2 = fill(nr * EVALS), fill(nr * 128 * 48), (C.c_uint8 * nr)(*([0xa5] * nr))
+    ret2 = f(rc2, rp2, st2, (C.c_uint64 * len(idx))(*idx), b"".join(b for _, b in rows), (C.c_uint64 * (nr + 1))(*start),
+             C.c_uint64(nr), hip.sp)
+    assert ret == ret2 == 1 and st == list(st2) == [0, 0, 1, 0, 0]
+    assert ev == rc2.raw and pr == rp2.raw
+    for r, k in enumerate(E6_ROWS):
+        want_e, want_p = (e6[k][2], e6[k][3]) if k is not None else (b"\xa5" * EVALS, b"\xa5" * (128 * 48))
+        assert ev[r * EVALS:(r + 1) * EVALS] == want_e, "evaluations of row %d" % r
+        assert pr[r * 128 * 48:(r + 1) * 128 * 48] == want_p, "proofs of row %d" % r
+
+
+def test_e6_nine_rows_piped_on_the_other_proof_path(hip_fk20, e6):
+    """nine rows: the first size whose outputs go back through the pipe; with the low-latency proof path disabled, so
+    that the coset entry reaches both FK20 proof paths as the cell entry does"""
+    valid = [k for k in E6_ROWS if k is not None]
+    keys = [valid[(r + r // 4) % 4] for r in range(9)]
+    ret, ev, pr, st = raw_call(hip_fk20, _e6_rows(e6, keys), 6)
+    assert ret == 0 and st == [0] * 9
+    for r, k in enumerate(keys):
+        assert ev[r * EVALS:(r + 1) * EVALS] == e6[k][2], "evaluations of row %d" % r
+        assert pr[r * 128 * 48:(r + 1) * 128 * 48] == e6[k][3], "proofs of row %d" % r

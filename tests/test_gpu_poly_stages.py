@@ -10,7 +10,7 @@ kernels are the product's binary code) runs each stage on chosen inputs and retu
     eval_blob_bytes_batch_device                      the three launch forms of k_eval_tree
     eval_quotient_batch_device                        k_eval_barycentric<true>, k_quotient_in_domain
     fr_div_inplace_device, fr_mul_inplace_device      k_fr_div_inplace (zero divisors), k_fr_mul_inplace
-    recover_set_factors_enqueue, fr_mul_cell_factor_enqueue, scatter_cells_device, scatter_cells_rows_enqueue
+    coset_recover_factors_enqueue, fr_mul_coset_factor_enqueue, scatter_cosets_rows_enqueue at cosets of 64; scatter_cells_device
     coset_aggregate_device at cosets of 64, group_cell_aggregate_device     parts = 1 .. 16
     coset_interp_device at cosets of 64 (on the values of given coefficients), group_interp_sum_device
 

@@ -2,7 +2,7 @@
 
 The references of tests/poly_expect.py, each by a second route: the opening quotient by interpolation and synthetic
 division (which checks the transform reference on the way), evaluation against the Horner value of the coefficients,
-the set factors against the host replay of recover_set_factors.hpp, and evaluation against the host replays of the
+the set factors against the host replay of coset_recover_factors.hpp, and evaluation against the host replays of the
 two evaluation kernels on items of the GPU module.
 
 The shim (tests/native/poly_shim.hip), as tests/test_stage_shim_cpu.py checks its shim: libpoly_shim.so cross-compiles

@@ -1,7 +1,7 @@
 """ckzg_hip_recover_cells_and_kzg_proofs_rows without a GPU: the symbol is declared and exported, a settings struct
 without GPU state gives C_KZG_ERROR (no CPU fallback), the binding checks its arguments, the index maps the product
-builds (csrc/recover_rows_plan.hpp, through libhost_shim.so) put every cell at (its row, its column) and give equal
-set ids exactly to equal sets, and the per-cell factors of csrc/recover_set_factors.hpp -- the function the kernel
+builds (csrc/coset_recover_plan.hpp at e = 6, through libhost_shim.so) put every cell at (its row, its column) and give equal
+set ids exactly to equal sets, and the per-cell factors of csrc/coset_recover_factors.hpp -- the function the kernel
 calls, replayed on the host -- are the vanishing polynomial of the missing cells: equal to the two products computed
 with Python integers, and equal to Z evaluated from the coefficients that the existing route's recurrence
 (vanishing_poly_from_roots, recovery.c:46-75) gives."""

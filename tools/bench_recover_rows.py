@@ -34,7 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as ge  # noqa: E402
 
 CELLS, PROOFS = 128 * 2048, 128 * 48
-KERNELS = ("k_recover_set_factors", "k_scatter_cells_rows", "k_fr_mul_cell_factor", "k_fr_mul_inplace", "k_fr_div_inplace",
+KERNELS = ("k_coset_recover_factors", "k_scatter_cosets_rows", "k_fr_mul_coset_factor", "k_fr_mul_inplace", "k_fr_div_inplace",
            "k_scatter_cells", "k_ntt_tile", "k_ntt8192_outer", "k_bytes_to_fr", "k_fr_to_bytes")
 
 
