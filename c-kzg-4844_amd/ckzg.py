@@ -484,6 +484,29 @@ class Kzg:
                    b"".join(proofs), C.c_uint64(n), C.c_uint32(log2_coset), self.sp)
         return ok.value
 
+    def verify_coset_kzg_proof_batch_locate(self, commitments, coset_indices, evals, proofs, log2_coset):
+        """ckzg_hip_verify_coset_kzg_proof_batch_locate: one verify_coset_kzg_proof_batch verdict per item at the cost of
+        one batch check when everything verifies; the arguments are that call's.  Returns (ok, status, stats) as
+        verify_cell_kzg_proof_batch_locate does; raises KzgError for log2_coset > 6."""
+        n = len(evals)
+        _check(len(commitments) == n and len(coset_indices) == n and len(proofs) == n, "list lengths")
+        _check(0 <= log2_coset < 1 << 32, "log2_coset")
+        for v in evals:
+            _check(len(v) == 32 << min(log2_coset, 6), "evals")
+        for c in list(commitments) + list(proofs):
+            _check(len(c) == 48, "commitment/proof")
+        for i in coset_indices:
+            _check(0 <= i < 1 << 64, "coset index")
+        ok = (C.c_bool * max(n, 1))()
+        st = (C.c_uint8 * max(n, 1))()
+        stats = (C.c_uint64 * 3)()
+        ret = self._fn("ckzg_hip_verify_coset_kzg_proof_batch_locate")(
+            ok, st, stats, b"".join(commitments), (C.c_uint64 * max(n, 1))(*coset_indices), b"".join(evals), b"".join(proofs),
+            C.c_uint64(n), C.c_uint32(log2_coset), self.sp)
+        if ret not in (0, 1) or log2_coset > 6:
+            raise KzgError("ckzg_hip_verify_coset_kzg_proof_batch_locate -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:n]], [int(v) for v in st[:n]], [int(v) for v in stats]
+
     def verify_cell_kzg_proof_batch_groups(self, groups):
         """ckzg_hip_verify_cell_kzg_proof_batch_groups: one verify_cell_kzg_proof_batch per group, in one call.  groups
         is a list of (commitments, cell_indices, cells, proofs) tuples.  Returns (ok, status): ok[g] is the group's

@@ -17,6 +17,7 @@
 #include "coset_verify_plan.hpp"
 #include "g1_fft_plan.hpp"
 #include "locate_plan.hpp"
+#include "coset_locate_plan.hpp"
 #include "coset_recover_plan.hpp"
 #include "slice_starts.hpp"
 
@@ -3247,6 +3248,99 @@ C_KZG_RET locate_cells_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64
     return ret;
 }
 
+// The coset form: the cell form at every coset size l = 2^e, e <= 6 (m = 8192 >> e cosets).  Per item
+// P1_i = C_i - [I_i(s)]_1 + [x_c^l] proof_i against [s^l]_2 (the check of ckzg_hip_verify_coset_kzg_proof_batch on a batch of
+// one).  [I_i(s)]_1 is an l-term fixed-base sum over g1_values_monomial[0 .. l - 1]: k_msm_small reads table entry
+// tw * npoints + voff + i with i < ppv, so with one vector per group (voff = 0) a vector of ppv = l digits per window
+// reads a prefix of the slot's 64-point cell_interp table, and that one table serves the seven sizes.  Which
+// k_msm_small<LPV> form runs at which (e, items): coset_locate_plan.hpp.
+C_KZG_RET locate_cosets_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t *stats, const Bytes48 *cb,
+                           const uint64_t *coset_indices, const Bytes32 *evals, const Bytes48 *pb, uint64_t n, int e,
+                           const KZGSettings *s) {
+    for (uint64_t i = 0; i < n; i++) ok[i] = false;
+    if (n == 0) return C_KZG_OK;
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    static const int table_wbits = (int)dev::ab_knob("CKZG_HIP_CELL_LOCATE_WBITS", 10);
+    static const int forced_lpv = (int)dev::ab_knob("CKZG_HIP_COSET_LOCATE_LPV", 0);
+    if (!ctx->cell_interp.d_table) {
+        // (a failed build leaves d_table null and nothing allocated: the next call builds it)
+        RC(dev::build_fixed_base_table(ctx, &ctx->cell_interp, ctx->d_mono, (int)FIELD_ELEMENTS_PER_CELL, table_wbits));
+    }
+    const dev::FixedBaseTable &t = ctx->cell_interp;
+    const host::G2Prepared &q2 = prepared_s_pow2(pg, e, s);
+    const size_t l = (size_t)1 << e;
+    const uint32_t ncosets = coset_verify_cosets(e);
+    const uint64_t CH = coset_locate_chunk_items(e);
+    const uint64_t m = n < CH ? n : CH;
+    const size_t digits_per_item = (size_t)t.nwin * l;
+    Arena &ar = ctx->api_arena;
+    OKM(ar.begin(LocateBufs::bytes(m) + m * l * 32 + m * l * sizeof(Fr) + 3 * m * 4 + m * digits_per_item * 2 + m * sizeof(G1XYZZ) +
+                 8 * 256));
+    ArenaTrim trim(ar);
+    LocateBufs b;
+    OKM(b.take(ar, m));
+    ABuf<uint8_t> d_ev(ar, m * l * 32);
+    ABuf<Fr> d_fr(ar, m * l);
+    ABuf<uint32_t> d_meta(ar, 2 * m), d_vbad(ar, m);   // coset [k] | commitment [k]
+    ABuf<int16_t> d_digits(ar, m * digits_per_item);
+    ABuf<G1XYZZ> d_interp(ar, m);
+    OKM(d_ev.p && d_fr.p && d_meta.p && d_vbad.p && d_digits.p && d_interp.p);
+    std::vector<uint32_t> meta(2 * m);
+    std::vector<uint8_t> leaves(32 * m);
+    std::vector<Bytes48> uniq;
+    StreamDrain drain{ctx->stream};   // nothing enqueued may outlive the arena's reuse
+    C_KZG_RET ret = C_KZG_OK;
+    for (uint64_t off = 0; off < n; off += CH) {
+        const uint64_t k = n - off < CH ? n - off : CH;
+        const Bytes32 *ev = evals + off * l;
+        // the chunk's distinct commitments: decompressed and subgroup-tested once each
+        uniq.clear();
+        {
+            std::unordered_map<std::string_view, uint32_t> ids;
+            ids.reserve(256);
+            for (uint64_t i = 0; i < k; i++) {
+                auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(cb[off + i].bytes), 48), (uint32_t)uniq.size());
+                if (it.second) uniq.push_back(cb[off + i]);
+                meta[k + i] = it.first->second;
+                meta[i] = coset_indices[off + i] < ncosets ? (uint32_t)coset_indices[off + i] : ncosets;
+            }
+        }
+        const size_t nc = uniq.size();
+        uint8_t digest[32];
+        {
+            // the leaves of the chunk's challenge on the host pool (locate_plan.hpp), underneath the copies and kernels
+            BackgroundFor hashes;
+            hashes.what = "coset locate leaf hash jobs";
+            hashes.n = k;
+            hashes.fn = [&](size_t i) {
+                locate_coset_leaf<Sha256>(&leaves[32 * i], cb[off + i].bytes, coset_indices[off + i], ev[i * l].bytes, pb[off + i].bytes, e);
+            };
+            hashes.start();
+            // (all copies from pageable memory first: such a copy returns only when it is done)
+            OKB(hipMemcpyAsync(b.d_in48.p, pb + off, k * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            OKB(hipMemcpyAsync(b.d_in48.p + k * 48, uniq.data(), nc * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            OKB(hipMemcpyAsync(d_meta.p, meta.data(), 2 * k * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            OKB(hipMemcpyAsync(d_ev.p, ev, k * l * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+            // proofs [0, k), distinct commitments [k, k + nc): flags in d_st[0, k + nc) and d_st[2k, 2k + k + nc)
+            RC(dev::decompress_g1_batch_device(ctx, b.d_pts.p, b.d_st.p, b.d_in48.p, k + nc));
+            RC(dev::subgroup_g1_batch_device(ctx, b.d_st.p + 2 * k, b.d_pts.p, k + nc));
+            OKB(hipMemsetAsync(d_vbad.p, 0, k * 4, ctx->stream) == hipSuccess);
+            RC(dev::bytes_to_fr_batch(ctx, d_fr.p, d_vbad.p, d_ev.p, k * l, (uint32_t)l));
+            RC(dev::coset_item_interp_digits_enqueue(ctx, d_digits.p, d_fr.p, d_meta.p, k, e, t.wbits, t.twin));
+            RC(dev::msm_small_vectors_lpv_device(ctx, t, d_interp.p, d_digits.p, k, (uint32_t)l, 1,
+                                                 forced_lpv ? forced_lpv : coset_locate_sum_lpv(e, k)));
+            RC(dev::coset_item_lhs_enqueue(ctx, b.d_xyzz.p, b.d_negp.p, b.d_bad.p, b.d_pts.p, b.d_st.p, b.d_st.p + 2 * k, d_interp.p,
+                                           d_meta.p, d_meta.p + k, d_vbad.p, k, e));
+            hashes.finish();
+            locate_coset_root<Sha256>(digest, leaves.data(), k, e);
+        }
+        ret = worse(ret, locate_chunk_from_lhs(ctx, ok + off, status ? status + off : nullptr, stats, b, fr_from_bytes_reduce(digest), k, pg, q2));
+        if (ret != C_KZG_OK && ret != C_KZG_BADARGS) return ret;
+    }
+    return ret;
+}
+
 // the shards' stats summed into the caller's three entries
 template <class Body>
 C_KZG_RET locate_entry(uint64_t *stats, uint64_t n, uint64_t min_shard, const KZGSettings *s, Body &&body) {
@@ -3304,6 +3398,26 @@ extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_locate(bool *ok, uint8
         return locate_entry(stats, num_cells, 64, s, [&](dev::DeviceCtx *ctx, uint64_t *st, uint64_t lo, uint64_t hi) {
             return locate_cells_on(ctx, ok + lo, status ? status + lo : nullptr, st, commitments_bytes + lo, cell_indices + lo,
                                    cells + lo, proofs_bytes + lo, hi - lo);
+        });
+    });
+}
+
+static_assert(CKZG_HIP_COSET_LOCATE_CHUNK_SLOTS == COSET_LOCATE_CHUNK_SLOTS && CKZG_HIP_LOCATE_CHUNK_ITEMS == COSET_LOCATE_CHUNK_ITEMS_MAX,
+              "the header and coset_locate_plan.hpp name the same chunk");
+
+extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats,
+                                                                 const Bytes48 *commitments_bytes, const uint64_t *coset_indices,
+                                                                 const Bytes32 *evals, const Bytes48 *proofs_bytes,
+                                                                 uint64_t num_cosets, uint32_t log2_coset, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (log2_coset > CKZG_HIP_COSET_MAX_LOG2) return C_KZG_BADARGS;
+        if (!settings_of(s)) return C_KZG_ERROR;
+        if (num_cosets == 0) return C_KZG_OK;
+        if (!ok || !commitments_bytes || !coset_indices || !evals || !proofs_bytes) return C_KZG_BADARGS;
+        const int e = (int)log2_coset;
+        return locate_entry(stats, num_cosets, COSET_LOCATE_MIN_SHARD, s, [&](dev::DeviceCtx *ctx, uint64_t *st, uint64_t lo, uint64_t hi) {
+            return locate_cosets_on(ctx, ok + lo, status ? status + lo : nullptr, st, commitments_bytes + lo, coset_indices + lo,
+                                    evals + (lo << e), proofs_bytes + lo, hi - lo, e, s);
         });
     });
 }

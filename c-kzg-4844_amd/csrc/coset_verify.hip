@@ -136,6 +136,49 @@ __global__ void k_coset_interp_final(uint32_t *interp, const Fr *partial, int e)
     store_raw(interp + (size_t)k * 8, acc);
 }
 
+// The per-item form (ckzg_hip_verify_coset_kzg_proof_batch_locate): what k_cell_interp_digits does
+// for 64, at every e.  A 64-lane workgroup takes 64 consecutive slots of the flat value array item_fr[n << e], that is
+// 64 >> e whole items: lane t is value t & (l - 1) of item t >> e, and ends with minus coefficient t & (l - 1) of that
+// item's interpolation polynomial over its coset, as the signed digits digits[item][w][k] of the fixed-base sum over
+// g1_values_monomial[0 .. l - 1].  The e butterfly stages are k_coset_interp_fold's, inside the wave (a lane's partner
+// tid ^ half is a value of the same item: half < l); then one product by 1 / l and one by x_c^-k.  e = 0: a lane is an
+// item and the coefficient is -y.  Lanes past the last item repeat it and write nothing; an index >= m is clamped for
+// the table look-up (k_coset_item_lhs flags the item).  Nothing goes through global memory between values and digits.
+__global__ __launch_bounds__(64) void k_coset_item_interp_digits(int16_t *digits, const Fr *item_fr, const uint32_t *coset_idx,
+                                                                 const Fr *roots, Fr inv_l, uint32_t n, int e, int wbits, int twin) {
+    __shared__ uint32_t sh[8 * 64];
+    const uint32_t tid = threadIdx.x, l = 1u << e, k = tid & (l - 1u);
+    uint32_t item = blockIdx.x * (64u >> e) + (tid >> e);
+    const bool live = item < n;
+    if (!live) item = n - 1;
+    Fr v = item_fr[((size_t)item << e) + k];
+    for (int s = 1; s <= e; s++) {
+        const uint32_t half = 1u << (s - 1);
+        lds_st<64>(sh, tid, v);
+        __syncthreads();
+        const Fr other = lds_ld<64>(sh, tid ^ half);
+        const Fr tw = roots[coset_verify_twiddle_root(k, s)];
+        v = (k & half) ? sub(other, mul(v, tw)) : add(v, mul(other, tw));
+        __syncthreads();
+    }
+    const uint32_t m = coset_verify_cosets(e), c = coset_idx[item] < m ? coset_idx[item] : m - 1u;
+    v = neg(mul(mul(v, inv_l), roots[coset_verify_unshift_root(c, e, k)]));
+    uint32_t raw[8];
+    to_raw<FrParams>(raw, v);
+    if (live) glv_digits(digits + ((size_t)item * (size_t)(2 * twin) << e) + k, l, raw, wbits, twin);
+}
+
+int coset_item_interp_digits_enqueue(DeviceCtx *ctx, int16_t *d_digits, const Fr *d_item_fr, const uint32_t *d_coset_idx, size_t n,
+                                     int e, int wbits, int twin) {
+    if (!n) return 0;
+    if (e < 0 || e > COSET_MAX_LOG || n > ((size_t)1 << 24)) return 2;
+    const size_t per_block = 64u >> e;
+    hipLaunchKernelGGL(k_coset_item_interp_digits, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(64), 0, ctx->stream,
+                       d_digits, d_item_fr, d_coset_idx, ctx->d_roots, fr_inv_pow2(e), (uint32_t)n, e, wbits, twin);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int coset_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_vec_rp, uint32_t *d_vec_wrp, uint32_t *d_vec_w,
                               const uint32_t *d_coset_idx, const uint32_t *d_grp_start, const uint32_t *d_members, const Fr &r,
                               size_t n, size_t nc, int e) {

@@ -449,6 +449,10 @@ int msm_from_digits_device(DeviceCtx *ctx, const FixedBaseTable &t, uint8_t *d_o
 int msm_small_vectors_device(DeviceCtx *ctx, const FixedBaseTable &t, G1XYZZ *d_out,
                              const int16_t *d_digits, size_t nvec, uint32_t ppv,
                              uint32_t vecs_per_group);
+// the same with the launch form chosen by the caller: lanes per vector lpv in {4, 8, 16, 64} (k_msm_small<lpv>; 2 for any
+// other value).  ckzg_hip_verify_coset_kzg_proof_batch_locate picks it per coset size and item count (coset_locate_plan.hpp).
+int msm_small_vectors_lpv_device(DeviceCtx *ctx, const FixedBaseTable &t, G1XYZZ *d_out, const int16_t *d_digits, size_t nvec,
+                                 uint32_t ppv, uint32_t vecs_per_group, int lpv);
 
 // ntt.hip
 int fr_ntt_batch(DeviceCtx *ctx, Fr *d_data, size_t count, int logn, bool dif, bool inverse,
@@ -621,6 +625,15 @@ int cell_interp_digits_enqueue(DeviceCtx *ctx, int16_t *d_digits, Fr *d_cell_fr,
 int cell_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8_t *d_bad, const G1Affine *d_pts,
                      const uint8_t *d_st_dec, const uint8_t *d_st_sub, const G1XYZZ *d_minus_interp, const uint32_t *d_col,
                      const uint32_t *d_commit, const uint32_t *d_cell_bad, size_t n);
+// The coset form (ckzg_api2.hip: locate_cosets_on), items of l = 2^e values, e <= 6.  coset_verify.hip:
+// d_digits[n][2 twin][l] <- the signed digits (table geometry wbits, twin) of minus the interpolation coefficients of item i
+// over coset d_coset_idx[i] (clamped to m - 1 = (8192 >> e) - 1 for the look-up), from d_item_fr[n][l] (Montgomery).
+int coset_item_interp_digits_enqueue(DeviceCtx *ctx, int16_t *d_digits, const Fr *d_item_fr, const uint32_t *d_coset_idx, size_t n,
+                                     int e, int wbits, int twin);
+// locate.hip: cell_lhs_enqueue with the coset size a parameter; an index >= m makes the item invalid.
+int coset_item_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8_t *d_bad, const G1Affine *d_pts,
+                           const uint8_t *d_st_dec, const uint8_t *d_st_sub, const G1XYZZ *d_minus_interp, const uint32_t *d_idx,
+                           const uint32_t *d_commit, const uint32_t *d_val_bad, size_t n, int e);
 // d_data[s][i] <- d_data[s][0] + ... + d_data[s][i] for nseg arrays of n points each, in place, with the complete
 // addition; d_scratch: g1_prefix_scan_scratch_points(n, nseg) points
 size_t g1_prefix_scan_scratch_points(size_t n, size_t nseg);

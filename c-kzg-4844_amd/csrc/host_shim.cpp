@@ -1115,6 +1115,136 @@ extern "C" int hs_locate_cells_host(uint8_t *ok, uint8_t *status, uint64_t *stat
     return 0;
 }
 
+// ---- ckzg_hip_verify_coset_kzg_proof_batch_locate: the cell form's two functions at every coset size l = 2^e, e <= 6
+// (tests/test_coset_locate_cpu.py), and the launch plan of the call (coset_locate_plan.hpp). ----
+#include "coset_locate_plan.hpp"
+extern "C" void hs_locate_coset_digest(uint8_t *digest32, const uint8_t *c48, const uint64_t *coset_indices, const uint8_t *evals,
+                                       const uint8_t *p48, uint64_t n, int e) {
+    locate_coset_digest<Sha256>(digest32, c48, coset_indices, evals, p48, n, e);
+}
+extern "C" uint64_t hs_coset_locate_chunk_items(int e) { return coset_locate_chunk_items(e); }
+extern "C" int hs_coset_locate_sum_lpv(int e, uint64_t items) { return coset_locate_sum_lpv(e, items); }
+// what[0 .. 6] = COSET_LOCATE_SUM_WAVE_BELOW, what[7 .. 13] = COSET_LOCATE_SUM_LPV, what[14] = smallest shard
+extern "C" void hs_coset_locate_constants(uint64_t *what) {
+    for (int e = 0; e <= COSET_MAX_LOG; e++) {
+        what[e] = COSET_LOCATE_SUM_WAVE_BELOW[e];
+        what[7 + e] = (uint64_t)COSET_LOCATE_SUM_LPV[e];
+    }
+    what[14] = COSET_LOCATE_MIN_SHARD;
+}
+
+// Per item: validation (index < m = 8192 >> e, l canonical values, both points in G1), the interpolation polynomial of
+// the item's values over its coset by the definition of the inverse transform (l x l products, no butterflies: a route
+// of its own) -- a_k = x_c^-k (1/l) sum_j y_j w_l^(-brp_e(j) k), x_c = w^brp_{13-e}(c) -- then
+// P1_i = C_i - sum_k a_k mono[k] + [x_c^l] proof_i and, as hs_locate_cells_host, r from locate_coset_digest,
+// A_i = [r^i] P1_i, B_i = [r^i] proof_i, prefix sums and the bisection over
+// e(PA[b] - PA[a], [1]_2) * e(-(PB[b] - PB[a]), [s^l]_2) == 1.  mono48: g1_values_monomial[0 .. l - 1] as the setup file
+// has them, sl_g2: [s^l]_2 = g2_values_monomial[l].  Out as hs_locate_cells_host.  Returns 0, 1 if a setup point does
+// not decompress, 2 for e out of range.
+extern "C" int hs_locate_cosets_host(uint8_t *ok, uint8_t *status, uint64_t *stats, uint8_t *r32, const uint8_t *c48,
+                                     const uint64_t *coset_indices, const uint8_t *evals, const uint8_t *p48, uint64_t n, int e,
+                                     const uint8_t *mono48, const G2Jac *sl_g2, int64_t max_checks) {
+    if (e < 0 || e > COSET_MAX_LOG) return 2;
+    const uint32_t l = 1u << e, m = 8192u >> e;
+    G2Prepared q1, q2;
+    g2_prepare(q1, g2_to_affine(g2_generator()));
+    g2_prepare(q2, g2_to_affine(*sl_g2));
+    G1Jac mono[64];
+    for (uint32_t k = 0; k < l; k++) {
+        G1Affine a;
+        if (g1_uncompress(a, mono48 + 48 * k) != 0) return 1;
+        mono[k] = jac_from_affine(a);
+    }
+    // w = 7^((r - 1) / 8192), the 8192-th root of unity the setup uses; roots[i] = w^i
+    std::vector<Fr> roots(8192);
+    {
+        uint32_t ex[8], seven[8] = {7, 0, 0, 0, 0, 0, 0, 0};
+        mod_limbs<FrParams>(ex);
+        ex[0] -= 1;   // (r is odd)
+        for (int i = 0; i < 8; i++) ex[i] = (ex[i] >> 13) | (i < 7 ? ex[i + 1] << 19 : 0u);
+        Fr w = Fr::one(), base = from_raw<FrParams>(seven);
+        for (int i = 0; i < 256; i++, base = mul(base, base))
+            if ((ex[i >> 5] >> (i & 31)) & 1u) w = mul(w, base);
+        roots[0] = Fr::one();
+        for (int i = 1; i < 8192; i++) roots[i] = mul(roots[i - 1], w);
+    }
+    uint32_t lraw[8] = {l, 0, 0, 0, 0, 0, 0, 0};
+    const Fr inv_l = fr_inv_safegcd(from_raw<FrParams>(lraw));
+    auto brp = [](uint32_t v, int bits) {
+        uint32_t o = 0;
+        for (int b = 0; b < bits; b++) o |= ((v >> b) & 1u) << (bits - 1 - b);
+        return o;
+    };
+    locate_coset_digest<Sha256>(r32, c48, coset_indices, evals, p48, n, e);
+    uint32_t rraw[8];
+    for (int i = 0; i < 8; i++) {
+        const uint8_t *p = r32 + 4 * (7 - i);
+        rraw[i] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+    }
+    const Fr r = from_raw<FrParams>(rraw);   // (reduces)
+    std::vector<uint8_t> invalid(n ? n : 1), okb(n ? n : 1);
+    std::vector<G1Jac> pa(n + 1), pb(n + 1);   // PA[0] = PB[0] = infinity
+    pa[0] = pb[0] = G1Jac::inf();
+    Fr rp = Fr::one();
+    for (uint64_t i = 0; i < n; i++, rp = mul(rp, r)) {
+        G1Affine c, pr;
+        bool bad = g1_uncompress(c, c48 + 48 * i) != 0 || g1_uncompress(pr, p48 + 48 * i) != 0;
+        bad = bad || !g1_in_subgroup_host(c) || !g1_in_subgroup_host(pr);
+        bad = bad || coset_indices[i] >= m;
+        Fr ev[64];
+        for (uint32_t j = 0; j < l && !bad; j++) {
+            uint32_t raw[8], md[8];
+            for (int w = 0; w < 8; w++) {
+                const uint8_t *p = evals + 32 * ((size_t)i * l + j) + 4 * (7 - w);
+                raw[w] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+            }
+            mod_limbs<FrParams>(md);
+            bad = limbs_geq<8>(raw, md);
+            ev[j] = from_raw<FrParams>(raw);
+        }
+        invalid[i] = bad ? 1 : 0;
+        G1Jac a = G1Jac::inf(), b = G1Jac::inf();
+        if (!bad) {
+            const uint32_t rb = brp((uint32_t)coset_indices[i], 13 - e);   // x_c = w^rb
+            G1Jac sum = G1Jac::inf();
+            for (uint32_t k = 0; k < l; k++) {
+                // value j sits at x_c w_l^brp_e(j), w_l = w^(8192 / l)
+                Fr ck = Fr::zero();
+                for (uint32_t j = 0; j < l; j++) ck = add(ck, mul(ev[j], roots[(8192u - m * ((brp(j, e) * k) & (l - 1u))) & 8191u]));
+                ck = mul(mul(ck, inv_l), roots[((8192u - rb) * k) & 8191u]);
+                uint32_t kraw[8];
+                to_raw<FrParams>(kraw, ck);
+                sum = jac_add(sum, g1_mul_glv_host(mono[k], kraw));
+            }
+            uint32_t xl[8], k[8];
+            to_raw<FrParams>(xl, roots[(rb << e) & 8191u]);
+            const G1Jac proof = jac_from_affine(pr);
+            const G1Jac p1 = jac_add(jac_add(jac_from_affine(c), jac_neg(sum)), g1_mul_glv_host(proof, xl));
+            to_raw<FrParams>(k, rp);
+            a = g1_mul_glv_host(p1, k);
+            b = g1_mul_glv_host(proof, k);
+        }
+        pa[i + 1] = jac_add(pa[i], a);
+        pb[i + 1] = jac_add(pb[i], b);
+    }
+    auto range_ok = [&](size_t lo, size_t hi) {
+        const G1Jac da = jac_add(pa[hi], jac_neg(pa[lo])), db = jac_add(pb[hi], jac_neg(pb[lo]));
+        return pairing_product_is_one(jac_to_affine(da), q1, jac_to_affine(jac_neg(db)), q2);
+    };
+    auto serial = [](size_t cnt, auto &&fn) {
+        for (size_t i = 0; i < cnt; i++) fn(i);
+    };
+    const LocateOutcome res = locate_bisect(reinterpret_cast<bool *>(okb.data()), invalid.data(), (size_t)n,
+                                            max_checks < 0 ? UINT64_MAX : (uint64_t)max_checks, range_ok, serial);
+    for (uint64_t i = 0; i < n; i++) {
+        ok[i] = okb[i];
+        status[i] = invalid[i];
+    }
+    stats[0] = res.checks;
+    stats[1] = res.open.size();
+    return 0;
+}
+
 // ---- g1_fft_plan.hpp: the index maps, the form picker and the chunk split of the general G1 transform and of the
 // ---- openings at every domain point (tests/test_domain_openings_cpu.py) ----
 #include "g1_fft_plan.hpp"

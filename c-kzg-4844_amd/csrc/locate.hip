@@ -10,10 +10,13 @@
 //     fixed-base sum over g1_values_monomial[0..63] reads (k_cell_interp_scale / k_cell_raw_digits: the same in three
 //     passes around fr_ntt_batch, the A/B partner)
 //   * k_cell_lhs: P1_i = C_i - [I_i(s)]_1 + [h_i^64] proof_i, -proof_i and the item's flag.
+// The coset form (ckzg_hip_verify_coset_kzg_proof_batch_locate) is the cell form at every coset
+// size: k_coset_item_interp_digits (coset_verify.hip) and k_coset_item_lhs here.
 #include "device.hpp"
 #include "dev_inline.hpp"
 #include "g1_glv_dev.hpp"
 #include "rpow2.hpp"
+#include "coset_verify_plan.hpp"
 
 namespace ckzg {
 namespace dev {
@@ -167,6 +170,52 @@ int cell_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8
     if (!n) return 0;
     hipLaunchKernelGGL(k_cell_lhs, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_lhs, d_neg_proof, d_bad, d_pts,
                        d_st_dec, d_st_sub, d_minus_interp, d_col, d_commit, d_cell_bad, ctx->d_roots, n);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the coset form: k_cell_lhs with the coset size a parameter (ckzg_hip_verify_coset_kzg_proof_batch_locate) ----
+
+// As k_cell_lhs, for cosets of l = 2^e values: item g names coset idx[g] of the m = 8192 >> e; val_bad[g] != 0 marks an
+// item with a value >= r.  P1_g = C_g + (-[I_g(s)]_1) + [x_c^l] proof_g, x_c^l = roots[coset_verify_shift_root(c, e)].
+// An index >= m makes the item invalid; it is clamped for the look-up only.
+__global__ __launch_bounds__(64) void k_coset_item_lhs(G1XYZZ *lhs, G1Affine *neg_proof, uint8_t *bad_out, const G1Affine *pts,
+                                                       const uint8_t *st_dec, const uint8_t *st_sub, const G1XYZZ *minus_interp,
+                                                       const uint32_t *idx, const uint32_t *commit, const uint32_t *val_bad,
+                                                       const Fr *roots, size_t n, int e) {
+    size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const bool live = g < n;
+    if (!live) g = n - 1;   // lanes past the end repeat the last item and write nothing
+    const size_t cg = n + commit[g];
+    const uint32_t m = coset_verify_cosets(e), ci = idx[g];
+    const bool bad = ci >= m || val_bad[g] != 0 || (st_dec[g] | st_sub[g] | st_dec[cg] | st_sub[cg]) != 0;
+    G1Affine c = pts[cg], pr = pts[g];
+    G1XYZZ mi = minus_interp[g];
+    if (bad) {
+        c = G1Affine::inf();
+        pr = G1Affine::inf();
+        mi = G1XYZZ::inf();
+    }
+    uint32_t h[8], hg[8];
+    to_raw<FrParams>(h, roots[coset_verify_shift_root(ci < m ? ci : m - 1u, e)]);
+    glv_split(h, hg, hg + 4);
+    G1XYZZ acc = xyzz_add_ni(xyzz_from_affine(c), mi);
+    acc = xyzz_add_ni(acc, glv_half_mul(pr, hg, false));   // [x_c^l]proof = [h1]proof + [h2]phi(proof)
+    acc = xyzz_add_ni(acc, glv_half_mul(pr, hg + 4, true));
+    if (live) {
+        lhs[g] = acc;
+        neg_proof[g] = affine_neg(pr);   // (infinity stays (0, 0))
+        bad_out[g] = bad ? 1 : 0;
+    }
+}
+
+int coset_item_lhs_enqueue(DeviceCtx *ctx, G1XYZZ *d_lhs, G1Affine *d_neg_proof, uint8_t *d_bad, const G1Affine *d_pts,
+                           const uint8_t *d_st_dec, const uint8_t *d_st_sub, const G1XYZZ *d_minus_interp, const uint32_t *d_idx,
+                           const uint32_t *d_commit, const uint32_t *d_val_bad, size_t n, int e) {
+    if (!n) return 0;
+    if (e < 0 || e > COSET_MAX_LOG) return 2;
+    hipLaunchKernelGGL(k_coset_item_lhs, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_lhs, d_neg_proof, d_bad,
+                       d_pts, d_st_dec, d_st_sub, d_minus_interp, d_idx, d_commit, d_val_bad, ctx->d_roots, n, e);
     HIP_TRY(hipGetLastError());
     return 0;
 }

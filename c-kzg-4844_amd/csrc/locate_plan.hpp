@@ -2,7 +2,8 @@
 // ranges (ckzg_hip_verify_kzg_proof_batch_locate / ckzg_hip_verify_blob_kzg_proof_batch_locate /
 // ckzg_hip_verify_cell_kzg_proof_batch_locate; DESIGN.md sections 3f, 3g), and the chunk challenges of the point and cell
 // forms.  Pure host code, shared by the product (ckzg_api2.hip: the predicate is one two-pairing check over differences
-// of prefix sums) and the host test shim (host_shim.cpp: hs_locate_bisect, hs_locate_points_host, hs_locate_cells_host).
+// of prefix sums) and the host test shim (host_shim.cpp: hs_locate_bisect, hs_locate_points_host, hs_locate_cells_host,
+// hs_locate_cosets_host).
 //
 // The rules are fixed, so that the number of checks is a property and not an observation:
 //   * invalid items are inert (they contribute infinity to every range) and are settled from their flag: ok = false;
@@ -142,6 +143,50 @@ void locate_cell_digest(uint8_t digest[32], const uint8_t *c48, const uint64_t *
     std::vector<uint8_t> leaves(32 * (k ? k : 1));
     for (uint64_t i = 0; i < k; i++) locate_cell_leaf<Sha>(&leaves[32 * i], c48 + 48 * i, cell_indices[i], cells + 2048 * i, p48 + 48 * i);
     locate_cell_root<Sha>(digest, leaves.data(), k);
+}
+
+// The challenge of a chunk of the coset form (ckzg_hip_verify_coset_kzg_proof_batch_locate), items of l = 2^e values:
+// the same two levels, with the coset size in every leaf and in the root.
+//   leaf_i = SHA-256("CKZGHIPCOSETLEAF" | C_i (48) | u64be l | u64be coset_index_i | its l values (32 l) | proof_i (48))
+//   root   = SHA-256("CKZGHIPCOSETROOT" | u64be 4096 | u64be l | u64be k | leaf_0 | ... | leaf_{k-1})
+template <class Sha>
+void locate_coset_leaf(uint8_t leaf[32], const uint8_t *c48, uint64_t coset_index, const uint8_t *values, const uint8_t *p48, int e) {
+    const uint64_t l = (uint64_t)1 << e;
+    Sha h;
+    uint8_t head[16] = {'C', 'K', 'Z', 'G', 'H', 'I', 'P', 'C', 'O', 'S', 'E', 'T', 'L', 'E', 'A', 'F'};
+    h.update(head, 16);
+    h.update(c48, 48);
+    for (int i = 0; i < 8; i++) {
+        head[i] = (uint8_t)(l >> (8 * (7 - i)));
+        head[8 + i] = (uint8_t)(coset_index >> (8 * (7 - i)));
+    }
+    h.update(head, 16);
+    h.update(values, 32 * l);
+    h.update(p48, 48);
+    h.finish(leaf);
+}
+template <class Sha>
+void locate_coset_root(uint8_t digest[32], const uint8_t *leaves, uint64_t k, int e) {
+    const uint64_t l = (uint64_t)1 << e;
+    Sha h;
+    uint8_t head[40] = {'C', 'K', 'Z', 'G', 'H', 'I', 'P', 'C', 'O', 'S', 'E', 'T', 'R', 'O', 'O', 'T'};
+    for (int i = 0; i < 8; i++) {
+        head[16 + i] = (uint8_t)((uint64_t)4096 >> (8 * (7 - i)));
+        head[24 + i] = (uint8_t)(l >> (8 * (7 - i)));
+        head[32 + i] = (uint8_t)(k >> (8 * (7 - i)));
+    }
+    h.update(head, 40);
+    h.update(leaves, 32 * k);
+    h.finish(digest);
+}
+// both levels on one thread (the host test shim; the product hashes the leaves on its pool)
+template <class Sha>
+void locate_coset_digest(uint8_t digest[32], const uint8_t *c48, const uint64_t *coset_indices, const uint8_t *evals, const uint8_t *p48,
+                         uint64_t k, int e) {
+    std::vector<uint8_t> leaves(32 * (k ? k : 1));
+    for (uint64_t i = 0; i < k; i++)
+        locate_coset_leaf<Sha>(&leaves[32 * i], c48 + 48 * i, coset_indices[i], evals + ((size_t)(32 * i) << e), p48 + 48 * i, e);
+    locate_coset_root<Sha>(digest, leaves.data(), k, e);
 }
 
 }  // namespace ckzg

@@ -1016,6 +1016,32 @@ int msm_small_vectors_device(DeviceCtx *ctx, const FixedBaseTable &t, G1XYZZ *d_
     return 0;
 }
 
+// The same kernels, the form named by the caller: lpv lanes per vector, 64 / lpv vectors per workgroup.
+template <int LPV>
+static void msm_small_launch(DeviceCtx *ctx, const FixedBaseTable &t, G1XYZZ *d_out, const int16_t *d_digits, size_t nvec,
+                             uint32_t ppv, uint32_t vecs_per_group) {
+    constexpr size_t GROUPS = 64 / LPV;
+    hipLaunchKernelGGL(k_msm_small<LPV>, dim3((unsigned)((nvec + GROUPS - 1) / GROUPS)), dim3(64), 0, ctx->stream, d_out, t.d_table,
+                       d_digits, (uint32_t)nvec, (uint32_t)t.nwin * ppv, t.wbits - 1, ppv, (uint32_t)t.npoints, vecs_per_group,
+                       small_prio_bit());
+}
+int msm_small_vectors_lpv_device(DeviceCtx *ctx, const FixedBaseTable &t, G1XYZZ *d_out, const int16_t *d_digits, size_t nvec,
+                                 uint32_t ppv, uint32_t vecs_per_group, int lpv) {
+    if (nvec == 0) return 0;
+    if (nvec > 0x7fffffffu || ppv == 0 || ppv > (uint32_t)t.npoints) return 2;
+    HIP_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
+    switch (lpv) {
+    case 4: msm_small_launch<4>(ctx, t, d_out, d_digits, nvec, ppv, vecs_per_group); break;
+    case 8: msm_small_launch<8>(ctx, t, d_out, d_digits, nvec, ppv, vecs_per_group); break;
+    case 16: msm_small_launch<16>(ctx, t, d_out, d_digits, nvec, ppv, vecs_per_group); break;
+    case 64: msm_small_launch<64>(ctx, t, d_out, d_digits, nvec, ppv, vecs_per_group); break;
+    default: return 2;
+    }
+    HIP_TRY(hipEventRecord(ctx->ev[6], ctx->stream));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // Full-size MSMs (ppv == npoints) for nvec digit vectors already in HBM; writes nvec compressed
 // points.  d_partials must hold msm_partials_needed() XYZZ points.
 size_t msm_partials_needed(const FixedBaseTable &t, size_t nvec) {

@@ -531,7 +531,7 @@ C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proofs, void *d
  * The four sums: at e = 6 from 128 items on, table sums over a fixed-base table of the batch's points built while the
  * transcript is hashed (as verify_cell_kzg_proof_batch always had; a device too full for the table falls back); ladders
  * below 128 items and at every e < 6, where a table's break-even has not been measured.
- * NOT here: per-item verdicts, groups, device pointers.
+ * NOT here: groups, device pointers.  Per-item verdicts: ckzg_hip_verify_coset_kzg_proof_batch_locate, below.
  * Measured (profiles/coset_verify_bench.json; its e = 6 rows predate the shared pipeline): medians of 20 and minima
  * of the wall time, default tables, a fresh process, 128 / 1,024 / 8,192 items, all true; with one false item the same within 0.1 ms unless noted.
  *   e = 0  2.33 (min 2.22) / 2.56 (2.41) / 4.49 (4.25) ms (one false at 8,192: 5.00, min 4.18), against 14.2 (min 14.1) /
@@ -546,6 +546,59 @@ C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proofs, void *d
 C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes, const uint64_t *coset_indices,
                                                 const Bytes32 *evals, const Bytes48 *proofs_bytes, uint64_t num_cosets,
                                                 uint32_t log2_coset, const KZGSettings *s);
+
+/* Per-coset verdicts at batch cost, at every coset size: the fourth *_locate call.  The inputs are those of
+ * ckzg_hip_verify_coset_kzg_proof_batch (item i carries l = 2^e values evals[i l .. i l + l - 1], m = 8192 >> e), and for
+ * every i, (status[i], ok[i]) is exactly (return value, *ok) of that call on item i alone -- for a node that takes cosets
+ * from untrusted peers and must know which one to throw away and ask for again.  A call in which every item verifies
+ * costs ONE two-pairing check.  The contract is ckzg_hip_verify_cell_kzg_proof_batch_locate's with 128 replaced by m and
+ * 64 by l: per item the left-hand point P1_i = C_i - [I_i(s)]_1 + [x_c^l] proof_i, I_i the interpolation polynomial of the
+ * item's values over its coset and x_c = brp_roots_of_unity[c l]; with A_i = [r^i] P1_i and B_i = [r^i] proof_i a range
+ * [a, b) is true iff e(sum A, [1]_2) * e(-sum B, [s^l]_2) == 1, and from the prefix sums on it is the point form:
+ * bisection on the host pool, ok[i] = false always exact, the hand-over under the option "locate_max_checks", stats
+ * ([0] host range checks, [1] items settled by the per-lane check, [2] chunks).
+ * Every item has its own inverse transform -- 64 >> e whole items per wave, a lane per value, so a wave is as full at
+ * e = 0 as at e = 6 -- and its own l-term fixed-base sum over g1_values_monomial[0 .. l - 1]: a prefix of the 64-point
+ * table the cell form builds on a slot's first call (41 MB per device slot, kept until free_trusted_setup) serves all seven
+ * sizes, so load time and ckzg_hip_table_bytes are as they were.
+ * An item is invalid when its coset index is >= m, when a value is not canonical, or when its commitment or proof is not
+ * a valid G1 point: status[i] = 1, ok[i] = false, inert in every range, settled from its flag alone; the other items are
+ * still decided.  Returns C_KZG_BADARGS if any item is invalid, C_KZG_OK otherwise (also for num_cosets == 0, which
+ * writes nothing); C_KZG_BADARGS with nothing written and nothing launched for log2_coset > 6, or for NULL ok or inputs
+ * with work to do; C_KZG_MALLOC / C_KZG_ERROR if the call itself failed; C_KZG_ERROR on settings without GPU state (there
+ * is no CPU fallback).  status and stats may be NULL.  Host pointers; several devices take contiguous runs of at least 64
+ * items; on a device the items go in chunks of min(CKZG_HIP_LOCATE_CHUNK_ITEMS, CKZG_HIP_COSET_LOCATE_CHUNK_SLOTS >> e)
+ * items, each with its own challenge and bisection; a chunk's distinct commitments are decompressed and subgroup-tested
+ * once each.  The challenge is NOT the transcript of ckzg_hip_verify_coset_kzg_proof_batch: a per-item verdict does not
+ * depend on r, so the chunk's items, as given, are hashed in two levels --
+ *   leaf_i = SHA-256("CKZGHIPCOSETLEAF" | C_i | u64be l | u64be coset_index_i | its l values | proof_i) on the host pool
+ *   underneath the copies and kernels, root = SHA-256("CKZGHIPCOSETROOT" | u64be 4096 | u64be l | u64be k | leaf_0 | ... |
+ *   leaf_{k-1}), r = root reduced mod r.
+ * The existing ckzg_hip_verify_cell_kzg_proof_batch_locate keeps its own kernels; at e = 6 the two calls give the same
+ * verdicts.
+ * Measured (profiles/coset_locate_bench.json; medians of 20 and minima, a fresh process, default tables, a 256-thread
+ * host; the alternatives on a build of the parent commit in the same process; 128 / 1,024 / 8,192 items).  Everything
+ * true: e = 0  11.4 / 12.0 / 13.6 ms against 14.1 (min 14.1) / 14.7 (14.6) / 16.3 (16.3) ms for
+ * ckzg_hip_verify_kzg_proof_batch_locate on the same items: faster at all three, by 2.7 ms (one ladder less per item).
+ * e = 1 .. 5  11.4-11.6 / 12.0-12.2 / 13.6-14.9 ms against a loop of single-item ckzg_hip_verify_coset_kzg_proof_batch
+ * calls: 282-291 ms (min 280) for 128 calls, 2.2 ms each; 2.2-2.3 s and 17.8-18.6 s for 1,024 and 8,192, extrapolated
+ * from 256-call loops: faster at all three, 25x / 185x / 1,300x.  e = 6  11.7 / 12.4 / 16.3 ms against 11.7 (min 11.6) /
+ * 12.4 (12.3) / 16.1 (16.0) ms for ckzg_hip_verify_cell_kzg_proof_batch_locate: NOT faster, the same within 0.13 ms.
+ * One false item 18.7-19.2 / 23.8-24.3 / 28.2-31.2 ms (11 / 17 / 21 host range checks), eight 23.6-24.7 / 29.0-30.7 /
+ * 36.9-41.8 ms, everything false 28.4-32.1 / 110.8-115.3 / 112.6-117.4 ms (the bisection up to the hand-over, then the
+ * per-lane pass), at every e; still below the loop's minimum at every measured shape of e = 1 .. 5.
+ * NOT faster: at e = 6, where the cell form is the same speed; and, by the figures above and not measured as a shape,
+ * below about five items at e = 1 .. 5 -- the two ladder kernels of a *_locate call cost ~11 ms whatever the size, a
+ * single-item call 2.2 ms -- or about eight when a false item is expected (18.7 ms).  A caller who needs ONE verdict for
+ * the batch keeps ckzg_hip_verify_coset_kzg_proof_batch (2.3-7.9 ms at these sizes).
+ * The l-term sums run one wave per item below 2,048 (e <= 1), 4,096 (e = 2, 3, 6) or 8,192 (e = 4, 5) items and with
+ * 4 (e = 0), 8 (e = 1 .. 5) or 16 (e = 6) lanes per item from there on, chosen from the kernel's own times at every (e,
+ * items, form) in the same record ("sum_forms"; csrc/coset_locate_plan.hpp). */
+#define CKZG_HIP_COSET_LOCATE_CHUNK_SLOTS 1048576
+C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_locate(bool *ok, uint8_t *status, uint64_t *stats,
+                                                       const Bytes48 *commitments_bytes, const uint64_t *coset_indices,
+                                                       const Bytes32 *evals, const Bytes48 *proofs_bytes, uint64_t num_cosets,
+                                                       uint32_t log2_coset, const KZGSettings *s);
 
 /* Recovery by rows at any coset size l = 2^e, e = log2_coset <= CKZG_HIP_COSET_MAX_LOG2: a node that holds at least half
  * of a row's cosets gets the row back, with its multiproofs -- the third leg next to
