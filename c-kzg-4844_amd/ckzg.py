@@ -538,6 +538,39 @@ class Kzg:
             raise KzgError("ckzg_hip_verify_cell_kzg_proof_batch_groups -> C_KZG_RET %d" % ret)
         return [bool(v) for v in ok[:g]], [int(v) for v in st[:g]]
 
+    def verify_coset_kzg_proof_batch_groups(self, groups, log2_coset):
+        """ckzg_hip_verify_coset_kzg_proof_batch_groups: one verify_coset_kzg_proof_batch per group, in one call.  groups
+        is a list of (commitments, coset_indices, evals, proofs) tuples, evals[i] the l = 2^log2_coset values of item i
+        (l * 32 bytes).  Returns (ok, status): ok[g] is the group's verdict and status[g] its C_KZG_RET (1 =
+        C_KZG_BADARGS: invalid index, point or value); raises KzgError for log2_coset > 6."""
+        g = len(groups)
+        _check(0 <= log2_coset < 1 << 32, "log2_coset")
+        start = [0]
+        flat = ([], [], [], [])
+        for grp in groups:
+            _check(len(grp) == 4, "a group is (commitments, coset_indices, evals, proofs)")
+            commitments, coset_indices, evals, proofs = grp
+            n = len(evals)
+            _check(len(commitments) == n and len(coset_indices) == n and len(proofs) == n, "list lengths")
+            for v in evals:
+                _check(len(v) == 32 << min(log2_coset, 6), "evals")
+            for c in list(commitments) + list(proofs):
+                _check(len(c) == 48, "commitment/proof")
+            for i in coset_indices:
+                _check(0 <= i < 1 << 64, "coset index")
+            for dst, src in zip(flat, grp):
+                dst.extend(src)
+            start.append(start[-1] + n)
+        total = start[-1]
+        ok = (C.c_bool * max(g, 1))()
+        st = (C.c_uint8 * max(g, 1))()
+        ret = self._fn("ckzg_hip_verify_coset_kzg_proof_batch_groups")(
+            ok, st, b"".join(flat[0]), (C.c_uint64 * max(total, 1))(*flat[1]), b"".join(flat[2]), b"".join(flat[3]),
+            (C.c_uint64 * (g + 1))(*start), C.c_uint64(g), C.c_uint32(log2_coset), self.sp)
+        if ret not in (0, 1) or log2_coset > 6:
+            raise KzgError("ckzg_hip_verify_coset_kzg_proof_batch_groups -> C_KZG_RET %d" % ret)
+        return [bool(v) for v in ok[:g]], [int(v) for v in st[:g]]
+
     def verify_blob_cell_kzg_proof_batch_groups(self, groups):
         """ckzg_hip_verify_blob_cell_kzg_proof_batch_groups: per group, compute_cells of every blob and one
         verify_cell_kzg_proof_batch over all their cells, in one call.  groups is a list of (blobs, commitments,

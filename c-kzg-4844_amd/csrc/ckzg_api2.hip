@@ -13,6 +13,7 @@
 #include <unordered_map>
 #include "blob_groups_plan.hpp"
 #include "cell_groups_plan.hpp"
+#include "coset_groups_plan.hpp"
 #include "combiner.hpp"
 #include "coset_verify_plan.hpp"
 #include "g1_fft_plan.hpp"
@@ -2583,6 +2584,164 @@ extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8
         [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, const uint64_t *start, size_t G) {
             return verify_cell_groups_on(ctx, ok, status, commitments_bytes + a, cell_indices + a, cells + a, proofs_bytes + a,
                                          start, G, s);
+        });
+}
+
+// ------------------------------------------------------------------------------------------
+// ckzg_hip_verify_coset_kzg_proof_batch_groups: many coset batches in one call, one verdict per group, at every coset size
+// ------------------------------------------------------------------------------------------
+
+// G groups over start[G] items (start[0] = 0) of l = 2^e values each on one device, as one chunk: verify_cell_groups_on
+// with the coset size a parameter (index maps and launch pickers: coset_groups_plan.hpp, device stages:
+// coset_groups.hip).  As there, everything that costs latency rather than work is paid once for
+// the chunk -- the points validated in one launch each with the commitments deduplicated across the chunk, the values
+// converted in one, the groups' transcripts (coset_verify_digest on each slice) hashed on the host pool underneath -- and
+// then the four segmented stages make every group's scalars, aggregate its rows, interpolate them and add them up, and
+// final_g = sum w_j C_j + sum r^i x_c^l proof_i - sum interp_g[k] [s^k]_1 and proof_lc_g = sum r^i proof_i of every
+// group run in ONE pass of the ladder kernels.  Every valid group gets its own two-pairing check against [s^l]_2.
+static C_KZG_RET verify_coset_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                        const uint64_t *coset_indices, const Bytes32 *evals, const Bytes48 *proofs_bytes,
+                                        const uint64_t *start, size_t G, int e, const KZGSettings *s) {
+    static const size_t quad_max = (size_t)dev::ab_knob("CKZG_HIP_QUAD_MAX", 8192);
+    const size_t N = (size_t)start[G], l = (size_t)1 << e, m = coset_verify_cosets(e);
+    for (size_t g = 0; g < G; g++) {
+        ok[g] = false;
+        status[g] = (uint8_t)C_KZG_OK;
+    }
+    if (N == 0) {
+        for (size_t g = 0; g < G; g++) ok[g] = true;
+        return C_KZG_OK;
+    }
+    const PreparedG2 *pg = prepared_of(ctx);
+    if (!pg) return C_KZG_ERROR;
+    const host::G2Prepared &q2 = prepared_s_pow2(pg, e, s);
+    StagedTrace tr("verify_coset_groups", ctx->stream);
+    std::vector<uint8_t> invalid(G, 0);
+    // the chunk's distinct commitments: validated once, however many groups repeat them
+    std::vector<uint32_t> item_commit(N);
+    std::vector<Bytes48> uniq;
+    {
+        std::unordered_map<std::string_view, uint32_t> ids;
+        ids.reserve(256);
+        for (size_t i = 0; i < N; i++) {
+            auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(commitments_bytes[i].bytes), 48), (uint32_t)uniq.size());
+            if (it.second) uniq.push_back(commitments_bytes[i]);
+            item_commit[i] = it.first->second;
+        }
+    }
+    for (size_t i = 0, g = 0; i < N; i++) {
+        while (i >= start[g + 1]) g++;
+        if (coset_indices[i] >= m) invalid[g] = 1;
+    }
+    const size_t ncu = uniq.size();
+    CosetGroupsPlan plan;
+    build_coset_groups_plan(plan, start, G, item_commit.data(), ncu, coset_indices, e, quad_max);
+    const size_t P = plan.P, R = plan.R, total = plan.total, npool = N + ncu + l, nparts = total / plan.per();
+    std::vector<Bytes48> pair_bytes(P);   // the commitments of every group in the order of its transcript
+    for (size_t j = 0; j < P; j++) pair_bytes[j] = uniq[plan.pair_commit[j]];
+    std::vector<Fr> r(G, Fr::zero());
+    // One SHA-256 stream per group, from the caller's bytes, on the host pool, underneath the copies and the validation
+    // below.  (declared after everything its jobs touch: an early return waits for them first)
+    BackgroundFor hashes;
+    hashes.what = "coset group transcript hash jobs";
+    hashes.n = G;
+    hashes.fn = [&plan, &pair_bytes, &r, start, coset_indices, evals, proofs_bytes, e](size_t g) {
+        const size_t a = (size_t)start[g], n = (size_t)(start[g + 1] - start[g]);
+        if (n == 0) return;
+        uint8_t digest[32];
+        coset_verify_digest<Sha256>(digest, pair_bytes[plan.pair_off[g]].bytes, plan.pair_off[g + 1] - plan.pair_off[g],
+                                    plan.item_pair.data() + a, coset_indices + a, evals[a << e].bytes, proofs_bytes[a].bytes, n, e);
+        r[g] = fr_from_bytes_reduce(digest);
+    };
+    hashes.start();
+    IndexMaps maps;
+    maps.words.reserve(4 * N + 4 * G + 2 * P + 2 * R + total + 8);
+    const size_t m_grp = maps.put(plan.item_grp), m_col = maps.put(plan.item_col), m_gd = maps.put(plan.gd),
+                 m_pstart = maps.put(plan.pair_start), m_pmem = maps.put(plan.pair_members), m_pterm = maps.put(plan.pair_term),
+                 m_rstart = maps.put(plan.row_start), m_rorder = maps.put(plan.row_order), m_rcol = maps.put(plan.row_col),
+                 m_grows = maps.put(plan.grp_rows), m_src = maps.put(plan.term_src);
+    Arena &ar = ctx->api_arena;
+    ArenaTrim trim(ar);
+    OKM(ar.begin((N + ncu) * (48 + 2) + npool * sizeof(G1Affine) + (N * l + N + R * l + G) * sizeof(Fr) + maps.words.size() * 4 +
+                 total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) + (2 * G + 1) * 4 +
+                 N * l * 32 + N * 4 + 20 * 256));
+    ABuf<uint8_t> d_ptb(ar, (N + ncu) * 48), d_st(ar, N + ncu), d_st2(ar, N + ncu), d_ev(ar, N * l * 32);
+    ABuf<G1Affine> d_pool(ar, npool), d_jobpts(ar, total), d_out(ar, 2 * G);   // pool: proofs, distinct commitments, g1_values_monomial[0 .. l - 1]
+    ABuf<Fr> d_evfr(ar, N * l), d_rp(ar, N), d_rows(ar, R * l), d_r(ar, G);
+    ABuf<uint32_t> d_maps(ar, maps.words.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1), d_bad(ar, N);
+    ABuf<G1XYZZ> d_part(ar, nparts);
+    OKM(d_ptb.p && d_st.p && d_st2.p && d_ev.p && d_pool.p && d_jobpts.p && d_out.p && d_evfr.p && d_rp.p && d_rows.p && d_r.p &&
+        d_maps.p && d_sc.p && d_off.p && d_bad.p && d_part.p);
+    OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, 2 * (N + ncu) + N * 4));
+    uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[0]), *h_st2 = h_st + (N + ncu);
+    uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
+    OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess &&
+        dev::ensure_event(ctx->flags_ev) == hipSuccess);
+    // whatever path leaves this function, both streams must be idle before the arena is reused
+    StreamDrain drain_main{ctx->stream}, drain{ctx->copy_stream};
+    // (all copies from pageable memory first: such a copy returns only when it is done, so it must not queue behind
+    // the validation kernels)
+    OKB(hipMemcpyAsync(d_ptb.p, proofs_bytes, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_ptb.p + N * 48, uniq.data(), ncu * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(hipMemcpyAsync(d_ev.p, evals, N * l * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    OKB(maps.upload(d_maps.p, ctx->stream));
+    RC(validate_points_two_streams(ctx, d_pool.p, d_st.p, d_st2.p, d_ptb.p, N + ncu, h_st, h_st2));
+    OKB(hipMemsetAsync(d_bad.p, 0, N * 4, ctx->stream) == hipSuccess);
+    RC(dev::bytes_to_fr_batch(ctx, d_evfr.p, d_bad.p, d_ev.p, N * l, (uint32_t)l));   // a flag per item
+    OKB(hipMemcpyAsync(h_bad, d_bad.p, N * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
+    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
+    // what the sums need besides the scalars: the jobs' points, gathered by index, and zeroes where no scalar is written
+    uint32_t *const dm = d_maps.p;
+    OKB(hipMemcpyAsync(d_pool.p + N + ncu, ctx->d_mono, l * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
+    RC(dev::group_gather_points_enqueue(ctx, d_jobpts.p, d_pool.p, dm + m_src, total));
+    OKB(hipMemsetAsync(d_sc.p, 0, total * 32, ctx->stream) == hipSuccess);
+    OKB(tr.stage("copies and validation (underneath the transcript hashes)"));
+    hashes.finish();
+    tr.mark("hashes");
+    OKB(hipMemcpyAsync(d_r.p, r.data(), G * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    RC(dev::coset_group_rlc_scalars_enqueue(ctx, d_rp.p, d_sc.p, dm + m_grp, dm + m_col, dm + m_gd, d_r.p, dm + m_pstart, dm + m_pmem,
+                                            dm + m_pterm, N, G, P, e));
+    OKB(tr.stage("scalars"));
+    RC(dev::coset_group_aggregate_device(ctx, d_rows.p, d_evfr.p, d_rp.p, dm + m_rstart, dm + m_rorder, N, R, e));
+    RC(dev::coset_group_interp_device(ctx, d_rows.p, dm + m_rcol, R, e));
+    RC(dev::coset_group_interp_sum_device(ctx, d_sc.p, d_rows.p, dm + m_grows, dm + m_gd, R, G, e));
+    OKB(tr.stage("aggregation"));
+    std::vector<G1Affine> sums;
+    RC(group_sums(ctx, sums, plan, G, d_out, d_part.p, d_off.p, d_jobpts.p, d_sc.p));
+    tr.mark("sums");
+    // the validation flags, folded into per-group status
+    OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
+    for (size_t i = 0; i < N; i++) {
+        const size_t c = N + item_commit[i];
+        if (h_st[i] || h_st2[i] || h_st[c] || h_st2[c] || h_bad[i]) invalid[plan.item_grp[i]] = 1;
+    }
+    // e(final_g, [1]_2) * e(-proof_lc_g, [s^l]_2) == 1, one check per valid group, on the host pool
+    return settle_groups(ok, status, start, G, invalid, sums, pg, q2, tr);
+}
+
+extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                                                 const uint64_t *coset_indices, const Bytes32 *evals,
+                                                                 const Bytes48 *proofs_bytes, const uint64_t *group_start,
+                                                                 uint64_t num_groups, uint32_t log2_coset, const KZGSettings *s) {
+    if (log2_coset > CKZG_HIP_COSET_MAX_LOG2)
+        return guarded([&]() -> C_KZG_RET { return settings_of(s) ? C_KZG_BADARGS : C_KZG_ERROR; });
+    const int e = (int)log2_coset;
+    // chunks of at most CKZG_HIP_COSET_GROUPS_CHUNK_ITEMS items / _CHUNK_GROUPS groups
+    return verify_groups_entry(
+        ok, status, group_start, num_groups, commitments_bytes && coset_indices && evals && proofs_bytes, s,
+        CKZG_HIP_COSET_GROUPS_CHUNK_GROUPS, CKZG_HIP_COSET_GROUPS_CHUNK_ITEMS,
+        [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, uint64_t n) {
+            // (status, ok) = (return value, *ok) of ckzg_hip_verify_coset_kzg_proof_batch on the group
+            return verify_one_group(ok, status, n, [&](bool *res) {
+                for (uint64_t i = 0; i < n; i++) {
+                    if (coset_indices[a + i] >= coset_verify_cosets(e)) return C_KZG_BADARGS;
+                }
+                return verify_cosets_on(ctx, res, commitments_bytes + a, coset_indices + a, evals + (a << e), proofs_bytes + a, n, e, s);
+            });
+        },
+        [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, const uint64_t *start, size_t G) {
+            return verify_coset_groups_on(ctx, ok, status, commitments_bytes + a, coset_indices + a, evals + (a << e), proofs_bytes + a,
+                                          start, G, e, s);
         });
 }
 

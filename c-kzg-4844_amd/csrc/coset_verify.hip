@@ -7,36 +7,11 @@
 #include "device.hpp"
 #include "rpow2.hpp"
 #include "dev_inline.hpp"
+#include "fr_lds.hpp"
 #include "coset_verify_plan.hpp"
 
 namespace ckzg {
 namespace dev {
-
-namespace {
-
-// An Fr vector in LDS, limb-major: limb k of element i at sh[k * n + i], so that the lanes of a wave that read
-// consecutive elements read consecutive words (element-major, 32 B apart, eight lanes would share a bank).
-template <uint32_t N>
-__device__ __forceinline__ Fr lds_ld(const uint32_t *sh, uint32_t i) {
-    Fr r;
-#pragma unroll
-    for (int k = 0; k < 8; k++) r.l[k] = sh[k * N + i];
-    return r;
-}
-template <uint32_t N>
-__device__ __forceinline__ void lds_st(uint32_t *sh, uint32_t i, const Fr &v) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) sh[k * N + i] = v.l[k];
-}
-
-__device__ __forceinline__ void store_raw(uint32_t *out, const Fr &v) {
-    uint32_t a[8];
-    to_raw<FrParams>(a, v);
-#pragma unroll
-    for (int k = 0; k < 8; k++) out[k] = a[k];
-}
-
-}  // namespace
 
 // Stage 2, per item: r^i in Montgomery form for the aggregation, and in canonical limbs -- plain, and times x_c^l of
 // the item's coset -- as the scalars of sum r^i proof_i and sum r^i x_c^l proof_i (eip7594.c:926, :784-812).

@@ -566,6 +566,9 @@ int coset_interp_device(DeviceCtx *ctx, uint32_t *d_interp, Fr *d_partial, Fr *d
 int group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_cell_grp, const uint32_t *d_cell_col,
                               const uint32_t *d_gd, const Fr *d_r, const uint32_t *d_pair_start, const uint32_t *d_pair_members,
                               const uint32_t *d_pair_term, size_t n, size_t ngroups, size_t npairs);
+//   d_sc <- the per-(group, commitment) weights alone: the sum of d_rp over each pair's members, onto the pair's term
+int group_commit_weights_enqueue(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rp, const uint32_t *d_pair_start,
+                                 const uint32_t *d_pair_members, const uint32_t *d_pair_term, size_t npairs);
 //   rows[t][j] = sum over the cells i of row t (CSR: row_start[nrows + 1], row_order[n]) of rp[i] * cell_fr[i][j]
 int group_cell_aggregate_device(DeviceCtx *ctx, Fr *d_rows, const Fr *d_cell_fr, const Fr *d_rp, const uint32_t *d_row_start,
                                 const uint32_t *d_row_order, size_t n_cells, size_t nrows);
@@ -574,6 +577,24 @@ int group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, co
                             const uint32_t *d_gd, size_t ngroups);
 //   d_out[t] <- d_pool[term_src[t]], infinity for a padding term
 int group_gather_points_enqueue(DeviceCtx *ctx, G1Affine *d_out, const G1Affine *d_pool, const uint32_t *d_term_src, size_t total);
+// coset_groups.hip: the same steps segmented by group at every coset size l = 2^e, e <= 6
+// (ckzg_hip_verify_coset_kzg_proof_batch_groups; index maps and launch pickers: coset_groups_plan.hpp, whose field names
+// the parameters carry).  All enqueue-only, on ctx->stream; d_sc and d_r as above.  A row is a distinct (group, coset)
+// pair of l values; the jobs' points are gathered by group_gather_points_enqueue.
+//   d_rp[n] <- r_g^(i - start_g); d_sc <- the same on each item's proof in B_g, times x_c^l of its coset in A_g, and the
+//   per-(group, commitment) weights on the pairs' terms
+int coset_group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_item_grp, const uint32_t *d_item_col,
+                                    const uint32_t *d_gd, const Fr *d_r, const uint32_t *d_pair_start, const uint32_t *d_pair_members,
+                                    const uint32_t *d_pair_term, size_t n, size_t ngroups, size_t npairs, int e);
+//   rows[t l + j] = sum over the items i of row t (CSR: row_start[nrows + 1], row_order[n]) of rp[i] * item_fr[i l + j]
+int coset_group_aggregate_device(DeviceCtx *ctx, Fr *d_rows, const Fr *d_item_fr, const Fr *d_rp, const uint32_t *d_row_start,
+                                 const uint32_t *d_row_order, size_t n_items, size_t nrows, int e);
+//   rows[t l + k] <- coefficient k of row t's interpolation polynomial over the l-th roots of unity, times x_c^-k of the
+//   row's coset c = row_col[t]; in place
+int coset_group_interp_device(DeviceCtx *ctx, Fr *d_rows, const uint32_t *d_row_col, size_t nrows, int e);
+//   d_sc <- minus the sum of each group's rows (grp_rows[ngroups + 1]), onto the l setup terms of A_g
+int coset_group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, const uint32_t *d_grp_rows, const uint32_t *d_gd,
+                                  size_t nrows, size_t ngroups, int e);
 // Blob verification by groups (ckzg_hip_verify_blob_kzg_proof_batch_groups; index maps: blob_groups_plan.hpp, over the
 // same job layout).  Enqueue-only, on ctx->stream: k_blob_group_scalars, then k_blob_group_ysum.
 //   d_sc <- r_g^(i - start_g) on blob i's commitment in A_g and on its proof in B_g, times z_i on its proof in A_g, and

@@ -665,6 +665,94 @@ extern "C" long hs_cell_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_t
     return (long)p.total;
 }
 
+// ---- ckzg_hip_verify_coset_kzg_proof_batch_groups: hs_cell_groups_replay with the coset size 2^e a parameter -- the
+// kernels of coset_groups.hip (k_coset_group_rlc_scalars, k_group_commit_weights, k_coset_group_aggregate,
+// k_coset_group_interp with its butterfly stages, k_coset_group_interp_sum) replayed slot by slot over the index maps
+// the product builds (coset_groups_plan.hpp), so that the maps can be checked without a GPU
+// (tests/test_coset_groups_cpu.py).  Field elements cross as canonical little-endian limbs: evals [N][l], r [G], roots
+// w^i [8193].  Out: info = (total, quad, pairs, rows, parts of the aggregation, parts of the per-group sum), term_src
+// [total], part_off [2 G + 1] and the jobs' scalars sc [total][8].  Returns the number of terms, -1 if it exceeds
+// cap_terms, -2 for e out of range. ----
+#include "coset_groups_plan.hpp"
+extern "C" long hs_coset_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_t *part_off, uint32_t *info, size_t cap_terms,
+                                       const uint64_t *start, size_t G, const uint32_t *item_commit, size_t num_commits,
+                                       const uint64_t *coset_indices, const uint32_t *evals_raw, const uint32_t *r_raw,
+                                       const uint32_t *roots_raw, int e, size_t quad_max_terms) {
+    if (e < 0 || e > COSET_MAX_LOG) return -2;
+    CosetGroupsPlan p;
+    build_coset_groups_plan(p, start, G, item_commit, num_commits, coset_indices, e, quad_max_terms);
+    if (p.total > cap_terms) return -1;
+    const size_t N = p.N, l = (size_t)1 << e;
+    info[0] = (uint32_t)p.total;
+    info[1] = p.quad ? 1 : 0;
+    info[2] = (uint32_t)p.P;
+    info[3] = (uint32_t)p.R;
+    info[4] = coset_groups_agg_parts(N, p.R);
+    info[5] = coset_groups_sum_parts(p.R, G);
+    for (size_t t = 0; t < p.total; t++) term_src[t] = p.term_src[t];
+    for (size_t j = 0; j <= 2 * G; j++) part_off[j] = p.part_off[j];
+    for (size_t t = 0; t < p.total * 8; t++) sc[t] = 0;
+    auto fr_at = [](const uint32_t *raw, size_t i) { return from_raw<FrParams>(raw + i * 8); };
+    const uint32_t *gd = p.gd.data();
+    // k_coset_group_rlc_scalars
+    std::vector<Fr> rp(N);
+    for (size_t i = 0; i < N; i++) {
+        const uint32_t g = p.item_grp[i], off = (uint32_t)i - gd[g];
+        Fr base = fr_at(r_raw, g), pw = Fr::one();
+        for (uint32_t x = off; x; x >>= 1) {
+            if (x & 1u) pw = mul(pw, base);
+            base = mul(base, base);
+        }
+        rp[i] = pw;
+        const size_t ta = (size_t)gd[G + 1 + g] + gd[2 * G + 1 + g] + off, tb = (size_t)gd[3 * G + 1 + g] + off;
+        to_raw<FrParams>(sc + ta * 8, mul(pw, fr_at(roots_raw, coset_verify_shift_root(p.item_col[i], e))));
+        to_raw<FrParams>(sc + tb * 8, pw);
+    }
+    // k_group_commit_weights
+    for (size_t j = 0; j < p.P; j++) {
+        Fr acc = Fr::zero();
+        for (uint32_t q = p.pair_start[j]; q < p.pair_start[j + 1]; q++) acc = add(acc, rp[p.pair_members[q]]);
+        to_raw<FrParams>(sc + (size_t)p.pair_term[j] * 8, acc);
+    }
+    // k_coset_group_aggregate, then k_coset_group_interp over the R l slots
+    std::vector<Fr> rows(p.R * l), next(p.R * l);
+    for (size_t slot = 0; slot < p.R * l; slot++) {
+        const size_t t = slot >> e, j = slot & (l - 1);
+        Fr acc = Fr::zero();
+        for (uint32_t q = p.row_start[t]; q < p.row_start[t + 1]; q++) {
+            const uint32_t i = p.row_order[q];
+            acc = add(acc, mul(fr_at(evals_raw, ((size_t)i << e) + j), rp[i]));
+        }
+        rows[slot] = acc;
+    }
+    for (int s = 1; s <= e; s++) {
+        const uint32_t half = 1u << (s - 1);
+        for (size_t slot = 0; slot < p.R * l; slot++) {
+            const uint32_t k = (uint32_t)(slot & (l - 1));
+            const Fr v = rows[slot], other = rows[slot ^ half], tw = fr_at(roots_raw, coset_verify_twiddle_root(k, s));
+            next[slot] = (k & half) ? sub(other, mul(v, tw)) : add(v, mul(other, tw));
+        }
+        rows.swap(next);
+    }
+    const uint32_t l_raw[8] = {(uint32_t)l, 0, 0, 0, 0, 0, 0, 0};
+    const Fr inv_l = fr_inv(from_raw<FrParams>(l_raw));
+    for (size_t slot = 0; slot < p.R * l; slot++) {
+        const uint32_t k = (uint32_t)(slot & (l - 1));
+        rows[slot] = mul(mul(rows[slot], inv_l), fr_at(roots_raw, coset_verify_unshift_root(p.row_col[slot >> e], e, k)));
+    }
+    // k_coset_group_interp_sum
+    for (size_t g = 0; g < G; g++) {
+        const uint32_t n = gd[g + 1] - gd[g];
+        if (!n) continue;
+        for (uint32_t k = 0; k < l; k++) {
+            Fr acc = Fr::zero();
+            for (uint32_t t = p.grp_rows[g]; t < p.grp_rows[g + 1]; t++) acc = add(acc, rows[((size_t)t << e) + k]);
+            to_raw<FrParams>(sc + ((size_t)gd[G + 1 + g] + gd[2 * G + 1 + g] + n + k) * 8, neg(acc));
+        }
+    }
+    return (long)p.total;
+}
+
 // ---- ckzg_hip_verify_blob_kzg_proof_batch_groups: the segmented scalar arithmetic of verify.hip
 // (k_blob_group_scalars, k_blob_group_ysum) replayed element by element over the index maps the product builds
 // (blob_groups_plan.hpp), so that the maps can be checked without a GPU (tests/test_blob_groups_cpu.py).  Field

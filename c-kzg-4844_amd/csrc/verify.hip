@@ -920,6 +920,15 @@ __global__ void k_group_gather_points(uint4 *out, const uint4 *pool, const uint3
     out[q] = src == 0xffffffffu ? make_uint4(0, 0, 0, 0) : pool[(size_t)src * U4 + q % U4];
 }
 
+int group_commit_weights_enqueue(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rp, const uint32_t *d_pair_start,
+                                 const uint32_t *d_pair_members, const uint32_t *d_pair_term, size_t npairs) {
+    if (!npairs) return 0;
+    hipLaunchKernelGGL(k_group_commit_weights, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, d_sc, d_rp, d_pair_start,
+                       d_pair_members, d_pair_term);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 int group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_cell_grp, const uint32_t *d_cell_col,
                               const uint32_t *d_gd, const Fr *d_r, const uint32_t *d_pair_start, const uint32_t *d_pair_members,
                               const uint32_t *d_pair_term, size_t n, size_t ngroups, size_t npairs) {
@@ -927,10 +936,8 @@ int group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const ui
     if (n >= ((size_t)1 << 31)) return 2;
     hipLaunchKernelGGL(k_group_rlc_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_rp, d_sc, d_cell_grp,
                        d_cell_col, d_gd, d_r, ctx->d_roots, (uint32_t)n, (uint32_t)ngroups);
-    hipLaunchKernelGGL(k_group_commit_weights, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, d_sc, d_rp, d_pair_start,
-                       d_pair_members, d_pair_term);
     HIP_TRY(hipGetLastError());
-    return 0;
+    return group_commit_weights_enqueue(ctx, d_sc, d_rp, d_pair_start, d_pair_members, d_pair_term, npairs);
 }
 
 // k_cell_aggregate over the rows of a chunk (one workgroup per distinct (group, column) pair instead of per column)

@@ -531,7 +531,8 @@ C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proofs, void *d
  * The four sums: at e = 6 from 128 items on, table sums over a fixed-base table of the batch's points built while the
  * transcript is hashed (as verify_cell_kzg_proof_batch always had; a device too full for the table falls back); ladders
  * below 128 items and at every e < 6, where a table's break-even has not been measured.
- * NOT here: groups, device pointers.  Per-item verdicts: ckzg_hip_verify_coset_kzg_proof_batch_locate, below.
+ * NOT here: device pointers.  One verdict per group of many batches: ckzg_hip_verify_coset_kzg_proof_batch_groups,
+ * below; per-item verdicts: ckzg_hip_verify_coset_kzg_proof_batch_locate, below.
  * Measured (profiles/coset_verify_bench.json; its e = 6 rows predate the shared pipeline): medians of 20 and minima
  * of the wall time, default tables, a fresh process, 128 / 1,024 / 8,192 items, all true; with one false item the same within 0.1 ms unless noted.
  *   e = 0  2.33 (min 2.22) / 2.56 (2.41) / 4.49 (4.25) ms (one false at 8,192: 5.00, min 4.18), against 14.2 (min 14.1) /
@@ -546,6 +547,52 @@ C_KZG_RET ckzg_hip_compute_coset_kzg_proofs_batch_device(void *d_proofs, void *d
 C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch(bool *ok, const Bytes48 *commitments_bytes, const uint64_t *coset_indices,
                                                 const Bytes32 *evals, const Bytes48 *proofs_bytes, uint64_t num_cosets,
                                                 uint32_t log2_coset, const KZGSettings *s);
+
+/* ckzg_hip_verify_coset_kzg_proof_batch over num_groups independent batches in one call, one verdict per group, at every
+ * coset size l = 2^e, e = log2_coset <= CKZG_HIP_COSET_MAX_LOG2: ckzg_hip_verify_cell_kzg_proof_batch_groups with the cell
+ * size a parameter.  The four input arrays are flat as for the single call (item i owns evals[i l .. i l + l - 1]),
+ * group_start[num_groups] items long; group g is the slice [group_start[g], group_start[g + 1]).  group_start has
+ * num_groups + 1 entries, starts at 0 and does not decrease.  For every g, (status[g], ok[g]) is exactly (return value,
+ * *ok) of
+ *   ckzg_hip_verify_coset_kzg_proof_batch(&ok, commitments + a, coset_indices + a, evals + a l, proofs + a, b - a, e, s)
+ * with a = group_start[g], b = group_start[g + 1]: an empty group is true with status 0; a coset index >= 8192 >> e, a
+ * value that is not canonical, or a commitment or proof that is not a valid G1 point gives that group status 1
+ * (C_KZG_BADARGS) and ok = false and says nothing about the other groups, whose verdicts are still computed and
+ * written.  Every group has the single call's challenge for its slice (its own transcript, commitments deduplicated
+ * within the group in order of first appearance) and every valid group its own two-pairing check against [s^l]_2; no
+ * randomness is shared between groups.
+ * Returns C_KZG_BADARGS if any group is invalid; C_KZG_BADARGS with nothing written for a malformed group_start (first
+ * entry not 0, or decreasing), for log2_coset > 6, or for NULL ok or inputs with work to do; C_KZG_OK otherwise (also
+ * for num_groups == 0, which writes nothing); C_KZG_MALLOC / C_KZG_ERROR if the call itself failed; C_KZG_ERROR on
+ * settings without GPU state.  status may be NULL.  Host pointers only.
+ * Whole groups are the unit of work: several devices take contiguous runs of groups, and on a device the groups are
+ * processed in chunks of at most CKZG_HIP_COSET_GROUPS_CHUNK_ITEMS items and CKZG_HIP_COSET_GROUPS_CHUNK_GROUPS groups;
+ * a group is never cut.  A group larger than a chunk, and a call of one group, go through the single-batch path.
+ * The kernels (coset_groups.hip) map their lanes over items, over the slots of the chunk's distinct (group, coset) rows
+ * and over the G l outputs, never over rows or groups: a wave is as full at e = 0 as at e = 6.
+ * ckzg_hip_verify_cell_kzg_proof_batch_groups keeps its own kernels; at e = 6 the two calls give the same verdicts.
+ * Measured (profiles/coset_groups_bench.json: tools/bench_coset_groups.py, medians of 20 and minima of the wall time, a fresh
+ * process, default tables, a 256-thread host, valid data; the alternatives on a build of the parent commit in the same process;
+ * groups x items per group).  Against a loop of one ckzg_hip_verify_coset_kzg_proof_batch per group, e = 0 .. 5:
+ *   128 x 8    5.8-6.8 ms (min 5.1-6.2)    against 284-292 ms (min 284-290)
+ *   128 x 64   7.5-8.0 ms (min 7.4-7.8)    against 309-316 ms (min 305-313); ONE call over the 8,192 items, one verdict for
+ *              all, takes 4.5 ms (e = 0) to 7.9 ms (e = 5)
+ *   8 x 64     2.7-2.8 ms (min 2.4-2.5)    against 19.2-19.9 ms (min 19.1-19.6)
+ *   512 x 1    16.1-18.3 ms (min 15.1-17.2) against 1,122-1,159 ms (min 1,108-1,150); 12-14 ms of it are the 512 pairing checks
+ *              on the host pool
+ * and at e = 6 8.5 / 9.1 / 3.0 / 23.3 ms against 296 / 318 / 19.9 / 1,170 ms: faster than the loop at every measured shape and
+ * size (the median below the loop's minimum), about 7x at 8 groups and 40-70x at 128 and 512.
+ * NOT faster: at e = 6 against ckzg_hip_verify_cell_kzg_proof_batch_groups on the same bytes, 9.3 (min 8.6) / 9.6 (9.0) / 2.95
+ * (2.67) / 23.0 (21.9) ms -- the same speed within the spread of two runs; either call serves cells of 64.  Nothing below 8
+ * groups was measured; a call of one group is the single call.  Kernels (profiles/coset_groups_resources.txt): 54-68 VGPRs, no
+ * scratch, 8 KB of static LDS in the interpolation and at most 32 KB in the folds; the switch point of the per-group sum's parts
+ * (32 rows a lane) is set by reasoning and unmeasured. */
+#define CKZG_HIP_COSET_GROUPS_CHUNK_ITEMS  16384
+#define CKZG_HIP_COSET_GROUPS_CHUNK_GROUPS 8192
+C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
+                                                       const uint64_t *coset_indices, const Bytes32 *evals,
+                                                       const Bytes48 *proofs_bytes, const uint64_t *group_start,
+                                                       uint64_t num_groups, uint32_t log2_coset, const KZGSettings *s);
 
 /* Per-coset verdicts at batch cost, at every coset size: the fourth *_locate call.  The inputs are those of
  * ckzg_hip_verify_coset_kzg_proof_batch (item i carries l = 2^e values evals[i l .. i l + l - 1], m = 8192 >> e), and for
