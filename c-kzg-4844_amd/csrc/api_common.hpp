@@ -685,6 +685,7 @@ inline bool ensure_pinned(void **bufs, size_t &have, size_t want) {
             return false;
         }
         CKZG_TSAN_NEW_MEMORY(bufs[i], want);
+        if (const int b = dev::poison_byte()) memset(bufs[i], b, want);   // option "poison_temporaries": the fresh block
     }
     have = want;
     return true;
@@ -826,7 +827,10 @@ struct PipeDrain {
 
 struct DeviceBuffer {
     void *p = nullptr;
-    bool alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess; }
+    // (a fresh block holds the byte of option "poison_temporaries", if set; `s` is the stream its first user runs on)
+    bool alloc(size_t bytes, hipStream_t s = nullptr) {
+        return hipMalloc(&p, bytes ? bytes : 1) == hipSuccess && dev::poison_fresh(p, bytes ? bytes : 1, s) == hipSuccess;
+    }
     ~DeviceBuffer() {
         if (p) (void)hipFree(p);
     }

@@ -80,6 +80,9 @@ extern "C" C_KZG_RET ckzg_hip_set_option(const char *key, int64_t value) {
     } else if (!strcmp(key, "commit_graph")) {
         if (value < 0 || value > 2) return C_KZG_BADARGS;   // (2: diagnostic -- build the graph anew on every call)
         g_commit_graph.store((int)value);  // read at call time
+    } else if (!strcmp(key, "poison_temporaries")) {
+        if (value < 0 || value > 255) return C_KZG_BADARGS;   // (diagnostic -- 0: off; else the fill byte, device.hpp)
+        dev::g_poison_byte.store((int)value, std::memory_order_relaxed);  // read at call time
     } else if (!strcmp(key, "host_threads")) {
         if (value < 0 || value > 1024) return C_KZG_BADARGS;
         g_host_threads.store((int)value);  // read when the helper pools start and at call time

@@ -195,6 +195,26 @@ inline hipError_t ensure_event(hipEvent_t &e) {
     return r;
 }
 
+// Option "poison_temporaries" (diagnostic, read at call time): 0 = off, 1..255 = the byte that every per-call temporary
+// holds before the call writes it -- the slot's scratch area, its two arenas and its pinned staging at lease time, and
+// every fresh block of them (and of the hipMalloc'd construction temporaries) where it is allocated.  A kernel that
+// reads an element nobody wrote, or a flag nobody cleared, then reads this byte instead of whatever the previous call
+// on the slot -- or a fresh, zeroed hipMalloc block -- happened to leave there.  Off costs one relaxed load per site.
+inline std::atomic<int> g_poison_byte{0};
+inline int poison_byte() { return g_poison_byte.load(std::memory_order_relaxed); }
+// Fill, then WAIT: the staging pipelines write the arena from other streams without ordering on `s`, so a fill that
+// was still running when this returns would race with them.
+inline hipError_t poison_fill(void *p, size_t bytes, hipStream_t s, int byte) {
+    if (!p || !bytes) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(p, byte, bytes, s);
+    return e != hipSuccess ? e : sync_stream(s);
+}
+// a block that has just been allocated inside a call: nothing unless the option is set
+inline hipError_t poison_fresh(void *p, size_t bytes, hipStream_t s) {
+    const int b = poison_byte();
+    return b ? poison_fill(p, bytes, s, b) : hipSuccess;
+}
+
 struct FixedBaseTable {
     G1Affine *d_table = nullptr;
     int npoints = 0;
@@ -276,7 +296,7 @@ struct Arena {
             // a batch of a coalescing operation: room for the largest batch at once (fall back to the need if it fails)
             if (hipMalloc(&base, reserve_scaled(bytes)) == hipSuccess) {
                 cap = reserve_scaled(bytes);
-                return true;
+                return fresh();
             }
             (void)hipGetLastError();
             base = nullptr;
@@ -287,7 +307,7 @@ struct Arena {
         if (twice > ((size_t)3 << 30)) twice = (size_t)3 << 30;   // (never past the size above which ArenaTrim gives the block back)
         if (old_cap && want < twice && speculative_bytes(want, twice) > want && hipMalloc(&base, twice) == hipSuccess) {
             cap = twice;
-            return true;
+            return fresh();
         }
         (void)hipGetLastError();
         base = nullptr;
@@ -300,8 +320,11 @@ struct Arena {
             return false;
         }
         cap = want;
-        return true;
+        return fresh();
     }
+    // a block that begin() has just allocated (never one it found large enough: callers may begin() again while data of
+    // the same call is live): option "poison_temporaries"
+    bool fresh() { return poison_fresh(base, cap, stream) == hipSuccess; }
     template <class T>
     T *get(size_t count) {
         size_t off = (used + 255) & ~(size_t)255, bytes = (count ? count : 1) * sizeof(T);

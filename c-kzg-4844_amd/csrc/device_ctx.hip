@@ -76,6 +76,28 @@ void Lease::take(DevicePool *p) {
         p->cv.notify_one();
         pool = nullptr;
         ctx = nullptr;
+        return;
+    }
+    // Option "poison_temporaries": everything a call takes from the slot holds the byte before the call starts.  Fill,
+    // then wait (dev::poison_fill): the staging pipelines write the arena from copy_stream without ordering on the
+    // compute stream.  A fill that fails gives the slot back: the call fails with C_KZG_ERROR, like any lost lease.
+    if (const int b = dev::poison_byte()) {
+        bool ok = dev::poison_fill(ctx->scratch.ptr, ctx->scratch.cap, ctx->stream, b) == hipSuccess &&
+                  dev::poison_fill(ctx->api_arena.base, ctx->api_arena.cap, ctx->stream, b) == hipSuccess &&
+                  dev::poison_fill(ctx->lc_arena.base, ctx->lc_arena.cap, ctx->stream, b) == hipSuccess;
+        for (int i = 0; i < 2 && ok; i++) {
+            if (ctx->h_stage[i]) memset(ctx->h_stage[i], b, ctx->h_stage_bytes);
+            if (ctx->h_out[i]) memset(ctx->h_out[i], b, ctx->h_out_bytes);
+        }
+        if (!ok) {
+            fprintf(stderr, "[ckzg-hip] poison_temporaries: filling the slot's temporaries failed\n");
+            (void)hipGetLastError();
+            std::lock_guard<std::mutex> relock(p->mu);
+            p->free_slots.push_back(idx);
+            p->cv.notify_one();
+            pool = nullptr;
+            ctx = nullptr;
+        }
     }
 }
 
@@ -393,7 +415,7 @@ static C_KZG_RET build_owner(DevicePool *pool, const KZGSettings *s, const Optio
     // rather than silently giving sums that differ from the reference's.
     {
         DeviceBuffer d_st;
-        if (!d_st.alloc(2 * NUM_G1_POINTS)) return C_KZG_MALLOC;
+        if (!d_st.alloc(2 * NUM_G1_POINTS, ctx->stream)) return C_KZG_MALLOC;
         int rc = dev::subgroup_g1_batch_device(ctx, (uint8_t *)d_st.p, (const G1Affine *)d_bases.p, NUM_G1_POINTS);
         if (!rc) rc = dev::subgroup_g1_batch_device(ctx, (uint8_t *)d_st.p + NUM_G1_POINTS, ctx->d_mono, NUM_G1_POINTS);
         if (rc) return (C_KZG_RET)rc;

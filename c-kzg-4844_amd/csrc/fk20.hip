@@ -865,6 +865,9 @@ int fk20_setup_device(DeviceCtx *ctx, const G1Affine *d_monomial, G1Affine *h_xe
     HIP_TRY(hipMalloc(&xin.p, npts * sizeof(G1XYZZ)));
     HIP_TRY(hipMalloc(&cols.p, npts * sizeof(G1XYZZ)));
     HIP_TRY(hipMalloc(&prefix.p, npts * sizeof(Fp)));
+    HIP_TRY(poison_fresh(xin.p, npts * sizeof(G1XYZZ), ctx->stream));
+    HIP_TRY(poison_fresh(cols.p, npts * sizeof(G1XYZZ), ctx->stream));
+    HIP_TRY(poison_fresh(prefix.p, npts * sizeof(Fp), ctx->stream));
     G1XYZZ *d_xin = static_cast<G1XYZZ *>(xin.p), *d_cols = static_cast<G1XYZZ *>(cols.p);
     Fp *d_prefix = static_cast<Fp *>(prefix.p);
     if (!ctx->d_xext) HIP_TRY(hipMalloc(&ctx->d_xext, npts * sizeof(G1Affine)));

@@ -326,6 +326,10 @@ int openings_xhat_ensure(DeviceCtx *ctx, int e) {
     HIP_TRY(hipMalloc(&tmp.p, g1_fft_tmp_points(logn, l) * sizeof(G1XYZZ)));
     HIP_TRY(hipMalloc(&prefix.p, (size_t)N_EXT * sizeof(Fp)));
     HIP_TRY(hipMalloc(&out.p, (size_t)N_EXT * sizeof(G1Affine)));
+    // (the three temporaries; `out` is the table that stays)
+    HIP_TRY(poison_fresh(xin.p, (size_t)N_EXT * sizeof(G1XYZZ), ctx->stream));
+    HIP_TRY(poison_fresh(tmp.p, g1_fft_tmp_points(logn, l) * sizeof(G1XYZZ), ctx->stream));
+    HIP_TRY(poison_fresh(prefix.p, (size_t)N_EXT * sizeof(Fp), ctx->stream));
     G1XYZZ *d_xin = static_cast<G1XYZZ *>(xin.p);
     hipLaunchKernelGGL(k_coset_xext_gather, dim3(N_EXT / 256), dim3(256), 0, ctx->stream, d_xin, ctx->d_mono, e);
     rc = g1_fft_enqueue(ctx, d_xin, static_cast<G1XYZZ *>(tmp.p), logn, l, (size_t)1 << logn, /*dif=*/true, /*inverse=*/0);

@@ -53,6 +53,7 @@ int scratch_reserve(DeviceCtx *ctx, size_t bytes) {
         HIP_TRY(hipMalloc(&ctx->scratch.ptr, want));
     }
     ctx->scratch.cap = want;
+    HIP_TRY(poison_fresh(ctx->scratch.ptr, want, ctx->stream));   // (the fresh block only: callers reserve again with data live)
     return 0;
 }
 
@@ -384,6 +385,7 @@ int build_fixed_base_table(DeviceCtx *ctx, FixedBaseTable *t, const G1Affine *d_
     HIP_TRY(hipMalloc(&table.p, t->bytes()));
     G1Affine *d_table = static_cast<G1Affine *>(table.p);
     HIP_TRY(hipMalloc(&wb.p, (size_t)t->twin * npoints * sizeof(G1XYZZ)));
+    HIP_TRY(poison_fresh(wb.p, (size_t)t->twin * npoints * sizeof(G1XYZZ), ctx->stream));
     G1XYZZ *d_wb = static_cast<G1XYZZ *>(wb.p);
     const auto t_alloc = std::chrono::steady_clock::now();
     enqueue_window_bases(ctx->stream, d_wb, d_bases, npoints, wbits, t->twin);
@@ -393,6 +395,8 @@ int build_fixed_base_table(DeviceCtx *ctx, FixedBaseTable *t, const G1Affine *d_
         const size_t nchains = (size_t)t->twin * npoints;
         HIP_TRY(hipMalloc(&wba.p, nchains * sizeof(G1Affine)));
         HIP_TRY(hipMalloc(&prefix.p, nchains * sizeof(Fp)));
+        HIP_TRY(poison_fresh(wba.p, nchains * sizeof(G1Affine), ctx->stream));
+        HIP_TRY(poison_fresh(prefix.p, nchains * sizeof(Fp), ctx->stream));
         int rc = enqueue_affine_chain_table(ctx->stream, *t, d_table, d_wb, static_cast<G1Affine *>(wba.p),
                                             static_cast<Fp *>(prefix.p), cancel);
         if (rc) return rc;

@@ -110,6 +110,16 @@ extern "C" {
  *                   0: hand over as soon as the root check fails.  Default 1024: the range checks a 256-thread
  *                   host pool completes (20.7 per ms) in the 74.8 ms the per-lane pass takes on a full chunk, rounded
  *                   down to a power of two (profiles/locate_bench.json).  Takes effect immediately.
+ *   "poison_temporaries"  diagnostic.  0 (default): off.  1..255: a fill byte.  While it is set, every call finds its
+ *                   temporaries holding that byte instead of what the previous call on the stream slot left there (or the
+ *                   zeroes of a fresh allocation): the slot's scratch area, its two arenas and its page-locked staging
+ *                   buffers are filled when the slot is leased, every block of them that is allocated during a call is
+ *                   filled before it is used, and so are the device temporaries of table and transform construction.  Each
+ *                   fill is waited for.  Tables, twiddles and the other data a slot keeps on purpose are not touched.  A
+ *                   kernel that reads an element no earlier kernel of the call wrote, or a flag that was never cleared,
+ *                   then gives a wrong answer under every fill byte instead of a right one by luck (0xFF: flags set, field
+ *                   elements >= r, digits -1; 0x01: flags set, every 32-byte word a canonical field element).  Off costs
+ *                   one relaxed atomic load per lease and per allocation.  Takes effect immediately.
  * A width that does not fit the free HBM is narrowed at load time (ckzg_hip_table_wbits reports the result).
  * Returns C_KZG_BADARGS for an unknown key or out-of-range value. */
 C_KZG_RET ckzg_hip_set_option(const char *key, int64_t value);

@@ -126,3 +126,6 @@ def test_null_arguments_are_rejected_not_dereferenced(lib):
     o.restype = C.c_int
     o.argtypes = [C.c_char_p, C.c_int64]
     assert o(b"commit_graph", 3) == 1 and o(b"commit_graph", -1) == 1 and o(b"commit_graph", 0) == 0 and o(b"commit_graph", 1) == 0
+    # the fill byte of the diagnostic "poison_temporaries": 0 (off, the default) .. 255
+    assert o(b"poison_temporaries", -1) == 1 and o(b"poison_temporaries", 256) == 1 and o(b"poison_temporaries", 1 << 32) == 1
+    assert o(b"poison_temporaries", 1) == 0 and o(b"poison_temporaries", 255) == 0 and o(b"poison_temporaries", 0) == 0
