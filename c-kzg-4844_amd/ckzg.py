@@ -451,6 +451,54 @@ class Kzg:
         out_p = [None if status[r] else bytes(praw[r * ps:(r + 1) * ps]) for r in range(nr)] if want_proofs else None
         return out_e, out_p, status
 
+    def repair_cosets_and_kzg_proofs_rows(self, rows, log2_coset, commitments=None, held_proofs=None, want_evals=True,
+                                          want_proofs=True):
+        """ckzg_hip_repair_cosets_and_kzg_proofs_rows: recover_cosets_and_kzg_proofs_rows on untrusted cosets.  rows as
+        there; commitments: one 48-byte commitment a row, or None; held_proofs: per row the list of its held cosets' proofs,
+        or None (then nothing is repaired).  Both outputs may be switched off (check-only).  Returns (evals_per_row,
+        proofs_per_row, status, verdict, coset_ok, stats): verdict[r] is a CKZG_HIP_ROW_* value (0 OK, 1 INCONSISTENT,
+        2 MISMATCH, 3 REPAIRED, 4 UNRECOVERABLE, 5 INVALID); coset_ok is a list of bools per row (None without held_proofs);
+        stats = [rows sent to repair, cosets through locate, rows of the second pass, host range checks].  The outputs of a
+        row are kept whatever its verdict (None only for an INVALID row): what an INCONSISTENT or MISMATCH row holds is what
+        the unchecked call returns."""
+        _check(isinstance(log2_coset, int) and 0 <= log2_coset <= 6, "log2_coset")
+        _check(held_proofs is None or commitments is not None, "held_proofs need commitments")
+        nr, item = len(rows), 32 << log2_coset
+        _check(commitments is None or len(commitments) == nr, "one commitment a row")
+        _check(held_proofs is None or len(held_proofs) == nr, "one list of proofs a row")
+        start, flat_idx, flat_evals, flat_proofs = [0], [], [], []
+        for r, row in enumerate(rows):
+            _check(len(row) == 2, "a row is (coset_indices, evals)")
+            coset_indices, evals = row
+            _check(len(evals) == len(coset_indices) * item, "evals")
+            flat_idx.extend(coset_indices)
+            flat_evals.append(bytes(evals))
+            start.append(start[-1] + len(coset_indices))
+            if held_proofs is not None:
+                _check(len(held_proofs[r]) == len(coset_indices) and all(len(p) == 48 for p in held_proofs[r]), "held proofs")
+                flat_proofs.extend(held_proofs[r])
+        for c in commitments or []:
+            _check(len(c) == 48, "commitment")
+        es, ps = 32 * 8192, 48 * (8192 >> log2_coset)
+        re = C.create_string_buffer(max(nr, 1) * es) if want_evals else None
+        rp = C.create_string_buffer(max(nr, 1) * ps) if want_proofs else None
+        st, vd = (C.c_uint8 * max(nr, 1))(), (C.c_uint8 * max(nr, 1))()
+        ok = (C.c_bool * max(start[-1], 1))() if held_proofs is not None else None
+        stats = (C.c_uint64 * 4)()
+        ret = self._fn("ckzg_hip_repair_cosets_and_kzg_proofs_rows")(
+            re, rp, st, vd, ok, stats, (C.c_uint64 * max(start[-1], 1))(*flat_idx), b"".join(flat_evals),
+            (C.c_uint64 * (nr + 1))(*start), C.c_uint64(nr), b"".join(commitments) if commitments is not None else None,
+            b"".join(flat_proofs) if held_proofs is not None else None, C.c_uint32(log2_coset), self.sp)
+        if ret not in (0, 1):
+            raise KzgError("ckzg_hip_repair_cosets_and_kzg_proofs_rows -> C_KZG_RET %d" % ret)
+        status, verdict = [int(v) for v in st[:nr]], [int(v) for v in vd[:nr]]
+        eraw = memoryview(re) if want_evals else None
+        praw = memoryview(rp) if want_proofs else None
+        out_e = [None if status[r] else bytes(eraw[r * es:(r + 1) * es]) for r in range(nr)] if want_evals else None
+        out_p = [None if status[r] else bytes(praw[r * ps:(r + 1) * ps]) for r in range(nr)] if want_proofs else None
+        coset_ok = [[bool(v) for v in ok[start[r]:start[r + 1]]] for r in range(nr)] if ok is not None else None
+        return out_e, out_p, status, verdict, coset_ok, [int(v) for v in stats]
+
     def verify_cell_kzg_proof_batch(self, commitments, cell_indices, cells, proofs):
         n = len(cells)
         _check(len(commitments) == n and len(cell_indices) == n and len(proofs) == n, "list lengths")

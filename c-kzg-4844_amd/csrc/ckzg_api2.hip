@@ -20,6 +20,7 @@
 #include "locate_plan.hpp"
 #include "coset_locate_plan.hpp"
 #include "coset_recover_plan.hpp"
+#include "coset_repair_plan.hpp"
 #include "slice_starts.hpp"
 
 using namespace ckzg;
@@ -1507,9 +1508,25 @@ static C_KZG_RET fk20_proof_tail(dev::DeviceCtx *ctx, size_t k, Fr *d_e, uint8_t
     return C_KZG_OK;
 }
 
+// The optional checks of the repair calls (ckzg_hip_repair_cosets_and_kzg_proofs_rows): two flags per caller row, both
+// indexed like status[].  high[r]: the coefficients 4096 .. 8191 of the row are not all zero -- with Q what the algorithm
+// returns and Z the vanishing polynomial of the missing set (deg Z <= 4096), deg Q < 4096 makes QZ the interpolant of
+// E Z, so Q equals the given values on every held coset, and consistent input gives deg Q < 4096: the held cosets lie on
+// one polynomial of degree < 4096 iff the flag is clear.  mismatch[r] (only with commitments): the commitment of the
+// row's first 4096 recovered values -- the blob in the blob's own order, the basis of ctx->commit -- is not the 48 bytes
+// commitments[r]; compressed G1 encodings are canonical, and the given bytes are never decompressed.
+// WITHOUT a RecoverChecks (the three recovery entries: ckzg_hip_recover_cells_and_kzg_proofs_batch,
+// ckzg_hip_recover_cells_and_kzg_proofs_rows, ckzg_hip_recover_cosets_and_kzg_proofs_rows) every `if (checks)` below is
+// skipped: the arena request, the buffers and every launch and copy are what they were before the checks existed
+// (profiles/coset_repair_bench.json lists the kernels of each entry on both builds).
+struct RecoverChecks {
+    const Bytes48 *commitments;   // [caller rows] or null: no mismatch flags
+    uint8_t *high, *mismatch;     // [caller rows]
+};
+
 template <class Source>
 static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, void *recovered_cells, void *recovered_proofs, uint8_t *status,
-                                C_KZG_RET result, Source &&src) {
+                                C_KZG_RET result, Source &&src, const RecoverChecks *checks = nullptr) {
     if (src.chunks() == 0) return result;
     const size_t n = FIELD_ELEMENTS_PER_EXT_BLOB;
     const size_t m = src.max_rows();
@@ -1519,18 +1536,28 @@ static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, void *recovered_cells, void
     // buffers alternate between chunks.  A call with a few rows copies directly (no helper thread).
     const bool piped = m > 8;
     const int nbuf = piped ? 2 : 1;
-    std::vector<uint32_t> bad(m);
+    // with checks the flags of a chunk are three runs of m words -- range, degree, commitment -- that come down together
+    const bool commits = checks && checks->commitments;
+    std::vector<uint32_t> bad(checks ? 3 * m : m);
+    std::vector<uint8_t> given;
     Arena &ar = ctx->api_arena;
-    // image(s) + Fr + flags per row; input; the source's own; proofs
+    // image(s) + Fr + flags per row; input; the source's own; proofs; the checks' flags and commitments (made | given)
     OKM(ar.begin(m * (nbuf * n * 32 + n * sizeof(Fr) + 4) + src.in_bytes() + src.extra_bytes() +
-                 (recovered_proofs ? m * nbuf * pr_row + src.tail_bytes() : 0) + 4096));
+                 (recovered_proofs ? m * nbuf * pr_row + src.tail_bytes() : 0) + 4096 + (checks ? m * (8 + 96) + 512 : 0)));
     ArenaTrim trim(ar);
     ABuf<uint8_t> d_img0(ar, m * n * 32), d_img1(ar, piped ? m * n * 32 : 1), d_in(ar, src.in_bytes());
     ABuf<uint8_t> d_pr0(ar, recovered_proofs ? m * pr_row : 1);
     ABuf<uint8_t> d_pr1(ar, recovered_proofs && piped ? m * pr_row : 1);
     ABuf<Fr> d_e(ar, m * n);
     ABuf<uint8_t> d_tail(ar, recovered_proofs ? src.tail_bytes() : 1);
-    ABuf<uint32_t> d_bad(ar, m);
+    ABuf<uint32_t> d_bad(ar, checks ? 3 * m : m);
+    ABuf<uint8_t> d_c48;
+    if (commits) {
+        d_c48 = ABuf<uint8_t>(ar, 2 * m * 48);
+        OKM(d_c48.p);
+        // the commitment's digits and partial sums live in ctx->scratch, like those of every other commitment
+        OKM(dev::scratch_reserve(ctx, dev::commit_scratch_bytes(ctx, m)) == 0);
+    }
     OKM(d_img0.p && d_img1.p && d_in.p && d_pr0.p && d_pr1.p && d_e.p && d_tail.p && d_bad.p && src.take(ar));
     uint8_t *img_buf[2] = {d_img0.p, piped ? d_img1.p : d_img0.p}, *pr_buf[2] = {d_pr0.p, piped ? d_pr1.p : d_pr0.p};
     // the pipe's page-locked staging, taken here so that running out of it is C_KZG_MALLOC like every other allocation
@@ -1557,6 +1584,19 @@ static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, void *recovered_cells, void
         OKB(hipMemsetAsync(d_bad.p, 0, k * 4, ctx->stream) == hipSuccess);
         RC(src.cells_in(ctx, c, d_img, d_in.p));
         RC(dev::bytes_to_fr_batch(ctx, d_e.p, d_bad.p, d_img, tot, (uint32_t)n));
+        if (commits) {   // the given commitments of the chunk's rows, in device-row order, next to the ones made below
+            given.resize(k * 48);
+            for (size_t i = 0; i < k; i++) memcpy(&given[48 * i], checks->commitments[src.caller_row(c, i)].bytes, 48);
+            // (from pageable memory: the copy has left `given` when this returns)
+            OKB(hipMemcpyAsync(d_c48.p + m * 48, given.data(), k * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+        }
+        if (checks && src.all_full(c)) {
+            // nothing is recovered, but the degree flag needs the rows' coefficients: transform and transform back, in
+            // place (exact arithmetic: d_e is again what it was; no second 64 MiB-per-256-rows buffer for a copy)
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));
+            RC(dev::rows_high_degree_enqueue(ctx, d_bad.p + m, d_e.p, k));
+            RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));
+        }
         if (!src.all_full(c)) {
             RC(src.mul_z(ctx, c, d_e.p));                                        // (E * Z)(w^i)
             RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));         // -> coefficients
@@ -1565,10 +1605,20 @@ static C_KZG_RET recover_chunks(dev::DeviceCtx *ctx, void *recovered_cells, void
             RC(src.mul_zinv(ctx, c, d_e.p));                                     // recovery.c:322-328
             RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, false, true, true));         // coset_ifft ...
             RC(dev::fr_mul_inplace_device(ctx, d_e.p, ctx->d_unshift, tot, n));  // ... unscale by 7^-i
+            if (checks) RC(dev::rows_high_degree_enqueue(ctx, d_bad.p + m, d_e.p, k));   // d_e: coefficients, natural order
             RC(dev::fr_ntt_batch(ctx, d_e.p, k, 13, true, false, false));        // evaluations, cell order
             if (recovered_cells) RC(dev::fr_to_bytes_batch(ctx, d_img, d_e.p, tot));
         }
-        OKB(d_bad.down(bad.data(), k));   // the chunk's one wait for the stream: the flags, and d_img is final
+        if (commits) {   // from d_e (given values on an all_full chunk), no byte image: check-only calls have none
+            RC(dev::fr_rows_commit_enqueue(ctx, d_c48.p, d_e.p, k));
+            RC(dev::commit_compare_enqueue(ctx, d_bad.p + 2 * m, d_c48.p, d_c48.p + m * 48, k));
+        }
+        // the chunk's one wait for the stream: the flags (with checks all three runs in the one copy), and d_img is final
+        OKB(d_bad.down(bad.data(), !checks ? k : commits ? 2 * m + k : m + k));
+        for (size_t i = 0; checks && i < k; i++) {
+            checks->high[src.caller_row(c, i)] = bad[m + i] != 0;
+            checks->mismatch[src.caller_row(c, i)] = commits && bad[2 * m + i] != 0;
+        }
         for (size_t i = 0; i < k; i++) {
             if (!bad[i]) continue;   // a field element >= r: the row's output is unspecified
             if (status) status[src.caller_row(c, i)] = (uint8_t)C_KZG_BADARGS;
@@ -1709,6 +1759,7 @@ struct RecoverCosetsByRows {
     const Bytes32 *evals;
     uint64_t lo;
     bool want_proofs;
+    const uint64_t *out_row;      // null, or (the second pass of a repair call) row r's outputs, status and flags are caller row out_row[r]'s
     ABuf<Fr> d_zdom, d_zinv;      // m factors per set
     ABuf<uint32_t> d_meta;        // row_set [k] | coset_dst [cosets] | miss_start [sets + 1] | miss
     std::vector<uint32_t> meta;
@@ -1759,11 +1810,19 @@ struct RecoverCosetsByRows {
     template <class F>
     bool for_each_run(size_t c, F &&f) const {
         for (const CosetRecoverRun &run : plan.chunks[c].runs) {
-            if (!f((size_t)run.dev_row, (size_t)(lo + run.caller_row), (size_t)run.rows)) return false;
+            if (!out_row) {
+                if (!f((size_t)run.dev_row, (size_t)(lo + run.caller_row), (size_t)run.rows)) return false;
+                continue;
+            }
+            for (uint32_t i = 0; i < run.rows; i++)   // the rows of a repair pass land wherever their caller rows are
+                if (!f((size_t)run.dev_row + i, (size_t)out_row[lo + run.caller_row + i], (size_t)1)) return false;
         }
         return true;
     }
-    size_t caller_row(size_t c, size_t i) const { return (size_t)(lo + plan.chunks[c].row_caller[i]); }
+    size_t caller_row(size_t c, size_t i) const {
+        const size_t r = (size_t)(lo + plan.chunks[c].row_caller[i]);
+        return out_row ? (size_t)out_row[r] : r;
+    }
     size_t proofs_per_row() const { return m(); }
     size_t sub_rows() const { return plan.max_rows < SUB ? plan.max_rows : SUB; }
     // FK20: the coefficients of the rows; the openings: the blobs of a sub-batch, its flags, their scratch
@@ -1803,14 +1862,15 @@ static_assert(sizeof(Cell) == 64 * sizeof(Bytes32), "a cell is a coset of 64 val
 // Structurally invalid rows get C_KZG_BADARGS here and no device row: they are neither copied, computed nor written
 static C_KZG_RET recover_cosets_rows_on(dev::DeviceCtx *ctx, Bytes32 *recovered_evals, KZGProof *recovered_proofs,
                                         uint8_t *status, const uint64_t *coset_indices, const Bytes32 *evals,
-                                        const uint64_t *row_start, uint64_t lo, uint64_t hi, int e, size_t chunk_rows) {
+                                        const uint64_t *row_start, uint64_t lo, uint64_t hi, int e, size_t chunk_rows,
+                                        const RecoverChecks *checks = nullptr, const uint64_t *out_row = nullptr) {
     CosetRecoverPlan plan;
     build_coset_recover_plan(plan, coset_indices, row_start + lo, hi - lo, e, chunk_rows);
     if (status) {
-        for (uint64_t r = lo; r < hi; r++) status[r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
+        for (uint64_t r = lo; r < hi; r++) status[out_row ? out_row[r] : r] = plan.valid[(size_t)(r - lo)] ? 0 : (uint8_t)C_KZG_BADARGS;
     }
     return recover_chunks(ctx, recovered_evals, recovered_proofs, status, plan.any_invalid ? C_KZG_BADARGS : C_KZG_OK,
-                          RecoverCosetsByRows{plan, evals, lo, recovered_proofs != NULL});
+                          RecoverCosetsByRows{plan, evals, lo, recovered_proofs != NULL, out_row}, checks);
 }
 
 extern "C" C_KZG_RET ckzg_hip_recover_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs,
@@ -3578,6 +3638,136 @@ extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_locate(bool *ok, uint
             return locate_cosets_on(ctx, ok + lo, status ? status + lo : nullptr, st, commitments_bytes + lo, coset_indices + lo,
                                     evals + (lo << e), proofs_bytes + lo, hi - lo, e, s);
         });
+    });
+}
+
+// ------------------------------------------------------------------------------------------
+// Recovery from untrusted cosets: check, locate, repair (ckzg_hip_repair_cosets_and_kzg_proofs_rows, and
+// ckzg_hip_repair_cells_and_kzg_proofs_rows at e = 6; coset_repair.hip, coset_repair_plan.hpp)
+// ------------------------------------------------------------------------------------------
+
+static_assert(CKZG_HIP_ROW_OK == COSET_ROW_OK && CKZG_HIP_ROW_INCONSISTENT == COSET_ROW_INCONSISTENT &&
+                  CKZG_HIP_ROW_MISMATCH == COSET_ROW_MISMATCH && CKZG_HIP_ROW_REPAIRED == COSET_ROW_REPAIRED &&
+                  CKZG_HIP_ROW_UNRECOVERABLE == COSET_ROW_UNRECOVERABLE && CKZG_HIP_ROW_INVALID == COSET_ROW_INVALID,
+              "the header and coset_repair_plan.hpp name the same verdicts");
+
+namespace {
+
+// Caller rows [lo, hi) on one device.  First pass: the rows call with the checks switched on -- the same plan, the same
+// chunks, the same outputs.  Then, with proofs of the held cosets: the failing rows' cosets through locate_cosets_on,
+// each with its row's commitment; the rows that keep m / 2 true cosets through the rows call once more (the row source
+// over the filtered rows, its outputs landing at their caller rows), checked again.  high / mismatch: [num_rows] scratch
+// of the call, each shard writes its own rows.  st: rows sent to repair, cosets through locate, rows of the second pass,
+// host range checks of the locate pass.
+C_KZG_RET repair_cosets_rows_on(dev::DeviceCtx *ctx, Bytes32 *recovered_evals, KZGProof *recovered_proofs, uint8_t *status,
+                                uint8_t *verdict, bool *coset_ok, uint64_t *st, uint8_t *high, uint8_t *mismatch,
+                                const uint64_t *coset_indices, const Bytes32 *evals, const uint64_t *row_start, uint64_t lo,
+                                uint64_t hi, const Bytes48 *cb, const Bytes48 *pb, int e, size_t chunk_rows,
+                                const KZGSettings *s) {
+    const RecoverChecks checks{cb, high, mismatch};
+    const C_KZG_RET ret = recover_cosets_rows_on(ctx, recovered_evals, recovered_proofs, status, coset_indices, evals, row_start,
+                                                 lo, hi, e, chunk_rows, &checks);
+    if (ret != C_KZG_OK && ret != C_KZG_BADARGS) return ret;
+    // (an OK row's held cosets are all true: the checks imply it, no pairing is spent; an invalid row's are not judged)
+    coset_repair_first_pass(verdict, coset_ok, status, high, mismatch, row_start, lo, hi);
+    if (!pb) return ret;
+    CosetRepairLocate lp;
+    coset_repair_locate_plan(lp, verdict, row_start, lo, hi);
+    st[0] += lp.rows.size(), st[1] += lp.items();
+    if (lp.rows.empty()) return ret;
+    // the locate pipeline takes flat items: the failing rows' cosets, gathered, each with its row's commitment
+    const size_t l = (size_t)1 << e, ni = lp.items();
+    std::vector<uint64_t> idx(ni);
+    std::vector<Bytes32> ev(ni * l);
+    std::vector<Bytes48> icb(ni), ipb(ni);
+    for (size_t i = 0; i < ni; i++) {
+        const uint64_t src = lp.item_src[i];
+        idx[i] = coset_indices[src];
+        memcpy(&ev[i * l], &evals[src * l], l * sizeof(Bytes32));
+        icb[i] = cb[lp.item_row[i]];
+        ipb[i] = pb[src];
+    }
+    std::unique_ptr<bool[]> ok(new bool[ni]);
+    uint64_t lst[3] = {0, 0, 0};
+    // (C_KZG_BADARGS here: an item with a commitment or proof that is no G1 point -- its ok is false, like any false item)
+    const C_KZG_RET lret = locate_cosets_on(ctx, ok.get(), nullptr, lst, icb.data(), idx.data(), ev.data(), ipb.data(), ni, e, s);
+    if (lret != C_KZG_OK && lret != C_KZG_BADARGS) return lret;
+    st[3] += lst[0];
+    if (coset_ok) coset_repair_spread_ok(coset_ok, lp, ok.get());
+    CosetRepairSecond sp;
+    coset_repair_second_plan(sp, lp, ok.get(), e);
+    coset_repair_lost(verdict, sp);
+    st[2] += sp.rows();
+    if (sp.rows() == 0) return ret;
+    const size_t nk = sp.src.size();
+    idx.resize(nk), ev.resize(nk * l);
+    for (size_t i = 0; i < nk; i++) {
+        idx[i] = coset_indices[sp.src[i]];
+        memcpy(&ev[i * l], &evals[sp.src[i] * l], l * sizeof(Bytes32));
+    }
+    // (its rows were valid and canonical in the first pass and hold a subset of what they held: status stays 0)
+    const C_KZG_RET ret2 = recover_cosets_rows_on(ctx, recovered_evals, recovered_proofs, status, idx.data(), ev.data(),
+                                                  sp.row_start.data(), 0, sp.rows(), e, chunk_rows, &checks, sp.out_row.data());
+    if (ret2 != C_KZG_OK) return ret2 == C_KZG_BADARGS ? C_KZG_ERROR : ret2;
+    coset_repair_finish(verdict, sp, high, mismatch);
+    return ret;
+}
+
+C_KZG_RET repair_rows_entry(Bytes32 *recovered_evals, KZGProof *recovered_proofs, uint8_t *status, uint8_t *verdict,
+                            bool *coset_ok, uint64_t *stats, const uint64_t *coset_indices, const Bytes32 *evals,
+                            const uint64_t *row_start, uint64_t num_rows, const Bytes48 *cb, const Bytes48 *pb, int e,
+                            size_t chunk_rows, const KZGSettings *s) {
+    if (!settings_of(s)) return C_KZG_ERROR;
+    if ((pb && !cb) || (coset_ok && !pb)) return C_KZG_BADARGS;
+    if (num_rows == 0) return C_KZG_OK;   // (writes nothing, like the rows call)
+    if (!verdict) return C_KZG_BADARGS;
+    // both outputs NULL is check-only mode: the verdicts alone
+    if (!slice_starts_ok(row_start, num_rows)) return C_KZG_BADARGS;
+    if (row_start[num_rows] != 0 && (coset_indices == NULL || evals == NULL)) return C_KZG_BADARGS;
+    // status is the rows call's and the verdicts read it: a caller who passes none gets a private one
+    std::vector<uint8_t> own_status(status ? 0 : (size_t)num_rows), flags(2 * (size_t)num_rows, 0);
+    if (!status) status = own_status.data();
+    std::atomic<uint64_t> sum[4] = {{0}, {0}, {0}, {0}};
+    const C_KZG_RET ret = for_each_device_shard(s, num_rows, 16, [&](dev::DeviceCtx *ctx, uint64_t lo, uint64_t hi) {
+        uint64_t st[4] = {0, 0, 0, 0};
+        const C_KZG_RET r = repair_cosets_rows_on(ctx, recovered_evals, recovered_proofs, status, verdict, coset_ok, st,
+                                                  flags.data(), flags.data() + num_rows, coset_indices, evals, row_start, lo, hi,
+                                                  cb, pb, e, chunk_rows, s);
+        for (int j = 0; j < 4; j++) sum[j].fetch_add(st[j], std::memory_order_relaxed);
+        return r;
+    });
+    if (stats)
+        for (int j = 0; j < 4; j++) stats[j] = sum[j].load(std::memory_order_relaxed);
+    return ret;
+}
+
+}  // namespace
+
+extern "C" C_KZG_RET ckzg_hip_repair_cosets_and_kzg_proofs_rows(Bytes32 *recovered_evals, KZGProof *recovered_proofs,
+                                                                uint8_t *status, uint8_t *verdict, bool *coset_ok,
+                                                                uint64_t *stats, const uint64_t *coset_indices,
+                                                                const Bytes32 *evals, const uint64_t *row_start,
+                                                                uint64_t num_rows, const Bytes48 *commitments_bytes,
+                                                                const Bytes48 *held_proofs_bytes, uint32_t log2_coset,
+                                                                const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        if (log2_coset > CKZG_HIP_COSET_MAX_LOG2) return C_KZG_BADARGS;
+        return repair_rows_entry(recovered_evals, recovered_proofs, status, verdict, coset_ok, stats, coset_indices, evals,
+                                 row_start, num_rows, commitments_bytes, held_proofs_bytes, (int)log2_coset,
+                                 CKZG_HIP_COSET_RECOVER_CHUNK_ROWS, s);
+    });
+}
+
+extern "C" C_KZG_RET ckzg_hip_repair_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs,
+                                                               uint8_t *status, uint8_t *verdict, bool *cell_ok,
+                                                               uint64_t *stats, const uint64_t *cell_indices, const Cell *cells,
+                                                               const uint64_t *row_start, uint64_t num_rows,
+                                                               const Bytes48 *commitments_bytes,
+                                                               const Bytes48 *held_proofs_bytes, const KZGSettings *s) {
+    return guarded([&]() -> C_KZG_RET {
+        return repair_rows_entry(reinterpret_cast<Bytes32 *>(recovered_cells), recovered_proofs, status, verdict, cell_ok, stats,
+                                 cell_indices, reinterpret_cast<const Bytes32 *>(cells), row_start, num_rows, commitments_bytes,
+                                 held_proofs_bytes, 6, RECOVER_CHUNK_ROWS, s);
     });
 }
 

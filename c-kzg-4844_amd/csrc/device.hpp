@@ -638,6 +638,15 @@ int scatter_cosets_rows_enqueue(DeviceCtx *ctx, uint8_t *d_image, const uint8_t 
                                 size_t ncosets, int e);
 //   a[row][p] *= f[row_set[row]][p >> e] over nrows rows of 8192
 int fr_mul_coset_factor_enqueue(DeviceCtx *ctx, Fr *d_a, const Fr *d_f, const uint32_t *d_row_set, size_t nrows, int e);
+// coset_repair.hip: the checks of ckzg_hip_repair_cosets_and_kzg_proofs_rows inside the recovery pipeline (ckzg_api2.hip:
+// RecoverChecks).  All enqueue-only, on ctx->stream; d_rows: nrows rows of 8192 Fr (Montgomery).
+//   d_flags[row] <- 1 if a coefficient 4096 .. 8191 of the row is not zero, else 0 (every row's flag is written)
+int rows_high_degree_enqueue(DeviceCtx *ctx, uint32_t *d_flags, const Fr *d_rows, size_t nrows);
+//   d_out48[row] <- the compressed commitment of the row's first 4096 values over ctx->commit; digits and partial sums in
+//   ctx->scratch, which the caller has reserved with commit_scratch_bytes(ctx, nrows)
+int fr_rows_commit_enqueue(DeviceCtx *ctx, uint8_t *d_out48, const Fr *d_rows, size_t nrows);
+//   d_flags[row] <- 1 if d_got48[row] and d_want48[row] differ in any of their 48 bytes, else 0 (16-byte aligned buffers)
+int commit_compare_enqueue(DeviceCtx *ctx, uint32_t *d_flags, const uint8_t *d_got48, const uint8_t *d_want48, size_t nrows);
 // pairing.hip: verify_kzg_proof for n independent items (ckzg_api2.hip: verify_point_proofs_on).  Enqueue-only, on
 // ctx->stream.  d_pts: commitments [0, n), proofs [n, 2n), decompressed; d_st_dec / d_st_sub: their 2n flags from
 // decompress_g1_batch_device / subgroup_g1_batch_device; d_z32 / d_y32: n x 32 big-endian bytes.  Writes the check's

@@ -1385,3 +1385,47 @@ extern "C" void hs_coset_verify_digest(uint8_t *digest32, const uint8_t *commitm
     coset_verify_digest<Sha256>(digest32, commitments48, num_commitments, commitment_indices, coset_indices, evals32, proofs48,
                                 num_cosets, e);
 }
+
+// ---- recovery from untrusted cosets: the planning of the repair pass (coset_repair_plan.hpp) replayed from flags the
+// caller makes up (tests/test_coset_repair_cpu.py, whose model is tests/coset_repair_expect.py).  One call is one shard
+// [0, num_rows): first-pass flags status / high1 / mismatch1 [num_rows]; with_proofs != 0: the locate pass runs, item_ok
+// being its answers at the CALLER'S flat cosets (read only at the located rows' cosets); high2 / mismatch2 [num_rows]:
+// the second pass's flags at the caller rows it lands on.  Out: verdict [num_rows], coset_ok [cosets] (may be null),
+// loc_rows [num_rows], item_src / item_row [cosets], out_row [num_rows], start2 [num_rows + 1], src2 [cosets], lost
+// [num_rows]; counts[5] = located rows, items, second-pass rows, cosets of the second pass, lost rows.  Returns 0, or -1
+// for e > 6 or a malformed row_start. ----
+#include <algorithm>
+#include "coset_repair_plan.hpp"
+extern "C" long hs_coset_repair_plan(uint8_t *verdict, uint8_t *coset_ok, uint64_t *loc_rows, uint64_t *item_src, uint64_t *item_row,
+                                     uint64_t *out_row, uint64_t *start2, uint64_t *src2, uint64_t *lost, uint64_t *counts,
+                                     const uint8_t *status, const uint8_t *high1, const uint8_t *mismatch1, const uint8_t *item_ok,
+                                     const uint8_t *high2, const uint8_t *mismatch2, const uint64_t *row_start, uint64_t num_rows,
+                                     int with_proofs, int e) {
+    if (e < 0 || e > 6 || !slice_starts_ok(row_start, num_rows)) return -1;
+    const uint64_t total = row_start[num_rows];
+    std::unique_ptr<bool[]> ok(new bool[total ? total : 1]), cok(new bool[total ? total : 1]);
+    coset_repair_first_pass(verdict, coset_ok ? cok.get() : nullptr, status, high1, mismatch1, row_start, 0, num_rows);
+    for (int j = 0; j < 5; j++) counts[j] = 0;
+    start2[0] = 0;
+    if (with_proofs) {
+        CosetRepairLocate lp;
+        coset_repair_locate_plan(lp, verdict, row_start, 0, num_rows);
+        for (size_t i = 0; i < lp.items(); i++) ok[i] = item_ok[lp.item_src[i]] != 0;
+        if (coset_ok) coset_repair_spread_ok(cok.get(), lp, ok.get());
+        CosetRepairSecond sp;
+        coset_repair_second_plan(sp, lp, ok.get(), e);
+        coset_repair_lost(verdict, sp);
+        coset_repair_finish(verdict, sp, high2, mismatch2);
+        counts[0] = lp.rows.size(), counts[1] = lp.items(), counts[2] = sp.rows(), counts[3] = sp.src.size(), counts[4] = sp.lost.size();
+        std::copy(lp.rows.begin(), lp.rows.end(), loc_rows);
+        std::copy(lp.item_src.begin(), lp.item_src.end(), item_src);
+        std::copy(lp.item_row.begin(), lp.item_row.end(), item_row);
+        std::copy(sp.out_row.begin(), sp.out_row.end(), out_row);
+        std::copy(sp.row_start.begin(), sp.row_start.end(), start2);
+        std::copy(sp.src.begin(), sp.src.end(), src2);
+        std::copy(sp.lost.begin(), sp.lost.end(), lost);
+    }
+    if (coset_ok)
+        for (uint64_t i = 0; i < total; i++) coset_ok[i] = cok[i] ? 1 : 0;
+    return 0;
+}

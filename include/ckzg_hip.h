@@ -720,6 +720,72 @@ C_KZG_RET ckzg_hip_recover_cosets_and_kzg_proofs_rows(Bytes32 *recovered_evals, 
                                                       const uint64_t *row_start, uint64_t num_rows, uint32_t log2_coset,
                                                       const KZGSettings *s);
 
+/* Recovery from UNTRUSTED cosets: check, locate, repair.  The rows calls above behave as the reference does: a row with
+ * one false value among its held cosets comes back as well-formed garbage with status C_KZG_OK.  These two calls are those
+ * calls -- same inputs, same row layout, same status[], same return value (C_KZG_BADARGS iff a row is structurally invalid
+ * or holds a non-canonical value; verdicts never change it), same sharding by whole rows -- plus one verdict a row:
+ *   CKZG_HIP_ROW_OK            the held cosets lie on one polynomial of degree < 4096 and, if commitments were given, that
+ *                              polynomial is the committed blob: every held and every recovered value is the true one;
+ *   CKZG_HIP_ROW_INCONSISTENT  the held cosets lie on no polynomial of degree < 4096;
+ *   CKZG_HIP_ROW_MISMATCH      consistent, but not the committed blob (also: the 48 bytes given are no G1 encoding);
+ *   CKZG_HIP_ROW_REPAIRED      false cosets found and dropped, recovered from the rest, equals the commitment;
+ *   CKZG_HIP_ROW_UNRECOVERABLE fewer than m / 2 held cosets verify (or the rest still fails); unspecified output;
+ *   CKZG_HIP_ROW_INVALID       status[r] != 0.
+ * Two checks, both needed.  CONSISTENCY costs nothing: after the last inverse transform the pipeline holds the 8192
+ * coefficients of the row; with Q the result and Z the vanishing polynomial of the missing set, deg Q < 4096 iff the held
+ * values are consistent, so the test is "coefficients 4096 .. 8191 are zero" -- one pass over half a row.  With exactly
+ * m / 2 held cosets every input is consistent, so this alone does not suffice.  IDENTITY costs one commitment: the first
+ * 4096 recovered values are the blob, the commitment table is over that basis, compressed encodings are canonical, so
+ * byte equality with commitments_bytes[r] settles the row with no proofs and no pairing; the given bytes are never
+ * decompressed.  A full row whose only false value is in its extension half commits correctly and is caught by the
+ * first check alone.  Precedence: INCONSISTENT, MISMATCH, OK; without commitments only OK and INCONSISTENT occur.
+ * FIRST PASS, every valid row: outputs are byte for byte those of the unchecked rows call on the same input, whatever the
+ * verdict.  verdict is required; recovered_evals and recovered_proofs may BOTH be NULL (check-only: e.g. a full row
+ * against its commitment without a single proof).  A chunk whose rows are all full is transformed to coefficients and
+ * back for the degree flag (the unchecked call transforms nothing there).
+ * REPAIR, only with held_proofs_bytes (flat, one per held coset, the proof of that coset against the row's commitment)
+ * and only for rows INCONSISTENT or MISMATCH: their held cosets go through the pipeline of
+ * ckzg_hip_verify_coset_kzg_proof_batch_locate, each with its row's commitment; coset_ok[i] is that call's ok[i]; a row
+ * that keeps at least m / 2 true cosets is recovered again from those, checked again, its outputs overwritten: REPAIRED
+ * if the second pass is OK, else UNRECOVERABLE.  coset_ok[i] is true for every held coset of an OK row (the checks imply
+ * it; no pairing is spent), false for INVALID rows.  stats (optional): [0] rows sent to repair, [1] cosets through
+ * locate, [2] rows recovered in the second pass, [3] host range checks of the locate pass.
+ * Rejected with nothing written and nothing launched: held_proofs_bytes without commitments_bytes, coset_ok without
+ * held_proofs_bytes, NULL verdict (C_KZG_BADARGS); log2_coset > 6, a malformed row_start, NULL inputs with work to do as
+ * the rows call.  num_rows == 0 returns C_KZG_OK and writes nothing.  status may be NULL.
+ * The cells call is the cosets call at e = 6 with chunks of 512 rows, as with the rows calls.
+ * Measured (profiles/coset_repair_bench.json; medians of 20, of 3 where a call takes more than 0.4 s; a fresh process,
+ * default tables, rows of 8 blobs holding m / 2 + 3 cosets; e = 0 / 3 / 6; the unchecked rows call and the composition on
+ * a build of the parent commit in the same process).  Price of the checks, everything true, evaluations only: 16 rows
+ * +0.36 / +0.52 / +0.51 ms (16.5 / 1.81 / 1.41 ms), 256 rows +3.1 / +3.9 / +4.2 ms (39.8 / 8.57 / 7.94 ms): 12-17 us a row,
+ * which DOUBLES a 256-row evaluations-only call at e = 3 and 6.  With proofs: inside the parent's spread at e = 0 and 3,
+ * +0.45 ms (16 rows, 5.29 ms) and +3.7 ms (256 rows, 36.1 ms) at e = 6.  Against ckzg_hip_verify_coset_kzg_proof_batch_locate
+ * over all held cosets followed by the rows call, everything true: 16.6 / 1.78 / 1.41 against 52.8 / 15.9 / 13.5 ms for 16
+ * rows, 39.7 / 8.4 / 7.8 against 418 / 66.9 / 37.0 ms for 256 (evaluations only); 1,593 / 463 / 35.9 against 1,969 / 527 /
+ * 66.3 ms for 256 rows with proofs: faster in all twelve shapes.  256 rows with one false coset in one row: 70.3 / 33.6 /
+ * 28.2 ms; one in every row 1,256 / 342 / 190 ms; every coset false 2,476 / 417 / 271 ms: NOT faster than that composition
+ * when most rows hold a false coset (3-5x its all-true time: every row through locate's bisection, every row recovered
+ * twice).  The three existing recovery entries launch the same kernels as before (one kernel trace listing per entry and
+ * build, same names and counts) and are not slower in this build.  Multi-device sharding is the rows call's and unmeasured. */
+#define CKZG_HIP_ROW_OK            0
+#define CKZG_HIP_ROW_INCONSISTENT  1
+#define CKZG_HIP_ROW_MISMATCH      2
+#define CKZG_HIP_ROW_REPAIRED      3
+#define CKZG_HIP_ROW_UNRECOVERABLE 4
+#define CKZG_HIP_ROW_INVALID       5
+C_KZG_RET ckzg_hip_repair_cosets_and_kzg_proofs_rows(Bytes32 *recovered_evals, KZGProof *recovered_proofs, uint8_t *status,
+                                                     uint8_t *verdict, bool *coset_ok, uint64_t *stats,
+                                                     const uint64_t *coset_indices, const Bytes32 *evals,
+                                                     const uint64_t *row_start, uint64_t num_rows,
+                                                     const Bytes48 *commitments_bytes, const Bytes48 *held_proofs_bytes,
+                                                     uint32_t log2_coset, const KZGSettings *s);
+C_KZG_RET ckzg_hip_repair_cells_and_kzg_proofs_rows(Cell *recovered_cells, KZGProof *recovered_proofs, uint8_t *status,
+                                                    uint8_t *verdict, bool *cell_ok, uint64_t *stats,
+                                                    const uint64_t *cell_indices, const Cell *cells,
+                                                    const uint64_t *row_start, uint64_t num_rows,
+                                                    const Bytes48 *commitments_bytes, const Bytes48 *held_proofs_bytes,
+                                                    const KZGSettings *s);
+
 /* Timing hook for bench.py: elapsed milliseconds of the named kernel family inside the last
  * batch call, measured with hipEvents on the stream the kernels were launched on (for a call that was
  * processed in several chunks: the last chunk).
