@@ -12,7 +12,6 @@
 #include <string_view>
 #include <unordered_map>
 #include "blob_groups_plan.hpp"
-#include "cell_groups_plan.hpp"
 #include "coset_groups_plan.hpp"
 #include "combiner.hpp"
 #include "coset_verify_plan.hpp"
@@ -2404,141 +2403,158 @@ static C_KZG_RET settle_groups(bool *ok, uint8_t *status, const uint64_t *start,
 }
 
 // ------------------------------------------------------------------------------------------
-// ckzg_hip_verify_cell_kzg_proof_batch_groups: many cell batches in one call, one verdict per group
+// The cell check by groups at every coset size l = 2^e, e <= 6, once: ckzg_hip_verify_coset_kzg_proof_batch_groups at
+// its e, ckzg_hip_verify_cell_kzg_proof_batch_groups and ckzg_hip_verify_blob_cell_kzg_proof_batch_groups at e = 6 (a
+// Cell is 64 values).  Index maps and launch pickers: coset_groups_plan.hpp, device stages: coset_groups.hip.
+// DESIGN.md sections 3b, 3e and 3i.2.
 // ------------------------------------------------------------------------------------------
 
-// G groups over start[G] cells (start[0] = 0) on one device, as one chunk.  Everything that costs latency rather than
-// work is paid once for the chunk: the points are validated in one launch each (the commitments deduplicated across
-// the whole chunk), the cells converted in one, and after the groups' challenges have been hashed on the host pool the
-// segmented kernels of verify.hip make every group's scalars, aggregate and interpolate its columns and run the two
-// sums of every group -- final_g = sum w_j C_j + sum r^i h^64 proof_i - sum interp_g[k] [s^k]_1 and
-// proof_lc_g = sum r^i proof_i -- in ONE pass of the ladder kernels.  The 2 G points come back and every valid group
-// gets its own two-pairing check on the host pool.  Validation flags are folded into per-group status: an invalid
-// point, index or field element marks the groups that use it and says nothing about the others.
+// G groups over start[G] items (start[0] = 0) of l values each on one device, as one chunk.  Everything that costs
+// latency rather than work is paid once for the chunk: the points are validated in one launch each (the commitments
+// deduplicated across the whole chunk), the values converted in one, and after the groups' challenges have been hashed
+// on the host pool (coset_verify_digest on each slice) the four segmented stages make every group's scalars, aggregate
+// its rows, interpolate them and add them up, and the two sums of every group --
+// final_g = sum w_j C_j + sum r^i x_c^l proof_i - sum interp_g[k] [s^k]_1 and proof_lc_g = sum r^i proof_i -- run in ONE
+// pass of the ladder kernels.  The 2 G points come back and every valid group gets its own two-pairing check against
+// [s^l]_2 on the host pool.  Validation flags are folded into per-group status: an invalid point, index or field element
+// marks the groups that use it and says nothing about the others.
 //
-// The chunk in two halves.  The first brings the inputs to the device and is the caller's own: the cells come from the
-// host and are parsed (verify_cell_groups_on), or blobs are extended to their cells where they are
-// (verify_blob_cell_groups_on).  The second runs from cells-in-Fr onwards and is written once (cell_groups_from_fr).
-// Between them: the plan, the buffers both halves use, and where the flags land.
-struct CellGroupsChunk {
-    size_t N = 0, G = 0, ncu = 0, R_ntt = 0, npool = 0, nparts = 0;
-    std::vector<uint32_t> cell_commit;   // [N] chunk-wide id of each cell's commitment (the caller fills these two)
+// The chunk in two halves.  The first brings the inputs to the device and is the caller's own: the items come from the
+// host and are parsed (verify_coset_groups_on, for the coset entry and for the cell entry at CELL_LOG), or blobs are
+// extended to their cells where they are (verify_blob_cell_groups_on).  The second runs from values-in-Fr onwards and is
+// written once (coset_groups_from_fr).  Between them: the plan, the buffers both halves use, and where the flags land.
+struct CosetGroupsChunk {
+    int e = 0;
+    size_t N = 0, G = 0, ncu = 0, npool = 0, nparts = 0;
+    std::vector<uint32_t> item_commit;   // [N] chunk-wide id of each item's commitment
     std::vector<Bytes48> uniq;           // the chunk's distinct commitments: validated once, however many groups repeat them
     std::vector<Bytes48> pair_bytes;     // [P] the commitments of every group in the order of its transcript
-    std::vector<uint8_t> invalid;        // [G]
+    std::vector<uint8_t> invalid;        // [G] (the caller marks the groups with an index out of range)
     std::vector<Fr> r;                   // [G] the groups' challenges
-    CellGroupsPlan plan;
+    CosetGroupsPlan plan;
     IndexMaps maps;
     size_t m_grp = 0, m_col = 0, m_gd = 0, m_pstart = 0, m_pmem = 0, m_pterm = 0, m_rstart = 0, m_rorder = 0, m_rcol = 0, m_grows = 0,
            m_src = 0;
     ABuf<uint8_t> d_ptb, d_st, d_st2;
-    ABuf<G1Affine> d_pool, d_jobpts, d_out;   // pool: proofs, the chunk's distinct commitments, g1_values_monomial[0..63]
-    ABuf<Fr> d_cellfr, d_rp, d_rows, d_r;
+    ABuf<G1Affine> d_pool, d_jobpts, d_out;   // pool: proofs, the chunk's distinct commitments, g1_values_monomial[0 .. l - 1]
+    ABuf<Fr> d_itemfr, d_rp, d_rows, d_r;
     ABuf<uint32_t> d_maps, d_sc, d_off;
     ABuf<G1XYZZ> d_part;
-    // page-locked, the caller's layout: point flags [N + ncu] each, and one flag per 2^bad_shift cells for a
-    // non-canonical field element (a flag per cell, or per blob: 128 cells)
+    // page-locked, the caller's layout: point flags [N + ncu] each, and one flag per 2^bad_shift items for a
+    // non-canonical field element (a flag per item, or per blob: 128 cells)
     uint8_t *h_st = nullptr, *h_st2 = nullptr;
     const uint32_t *h_bad = nullptr;
     unsigned bad_shift = 0;
 };
 
-// cell_commit and uniq are filled: the plan over start[G + 1] (in cells) and the commitments every transcript hashes
-static void cell_groups_plan(CellGroupsChunk &ch, const uint64_t *start, size_t G, const uint64_t *cell_indices) {
+// The chunk's distinct commitments and every item's id among them: commitment j of the n stands for the `per` items
+// from item j * per on (one, or the 128 cells of a blob)
+static void coset_groups_dedup(CosetGroupsChunk &ch, const Bytes48 *commitments_bytes, size_t n, size_t per) {
+    ch.item_commit.resize(n * per);
+    std::unordered_map<std::string_view, uint32_t> ids;
+    ids.reserve(256);
+    for (size_t j = 0; j < n; j++) {
+        auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(commitments_bytes[j].bytes), 48), (uint32_t)ch.uniq.size());
+        if (it.second) ch.uniq.push_back(commitments_bytes[j]);
+        for (size_t k = 0; k < per; k++) ch.item_commit[j * per + k] = it.first->second;
+    }
+}
+
+// item_commit and uniq are filled: the plan over start[G + 1] (in items), the commitments every transcript hashes, and
+// the index maps as one upload
+static void coset_groups_plan(CosetGroupsChunk &ch, const uint64_t *start, size_t G, const uint64_t *coset_indices, int e) {
     static const size_t quad_max = (size_t)dev::ab_knob("CKZG_HIP_QUAD_MAX", 8192);
+    ch.e = e;
     ch.N = (size_t)start[G];
     ch.G = G;
     ch.ncu = ch.uniq.size();
-    build_cell_groups_plan(ch.plan, start, G, ch.cell_commit.data(), ch.ncu, cell_indices, quad_max);
-    ch.R_ntt = (ch.plan.R + 63) / 64 * 64;   // fr_ntt_batch works on whole tiles of 4096 elements: zero rows behind the last one
-    ch.npool = ch.N + ch.ncu + FIELD_ELEMENTS_PER_CELL;
-    ch.nparts = ch.plan.total / ch.plan.per();
-    ch.pair_bytes.resize(ch.plan.P);
-    for (size_t j = 0; j < ch.plan.P; j++) ch.pair_bytes[j] = ch.uniq[ch.plan.pair_commit[j]];
+    CosetGroupsPlan &plan = ch.plan;
+    build_coset_groups_plan(plan, start, G, ch.item_commit.data(), ch.ncu, coset_indices, e, quad_max);
+    ch.npool = ch.N + ch.ncu + ((size_t)1 << e);
+    ch.nparts = plan.total / plan.per();
+    ch.pair_bytes.resize(plan.P);
+    for (size_t j = 0; j < plan.P; j++) ch.pair_bytes[j] = ch.uniq[plan.pair_commit[j]];
     ch.r.assign(G, Fr::zero());
-}
-
-// One SHA-256 stream per group (eip7594.c:390-482 on the group's slice, its commitments deduplicated within the
-// group), on the host pool: the jobs, for the caller to start once the cells' bytes are where `cells` points
-static void cell_groups_hash_jobs(BackgroundFor &hashes, CellGroupsChunk &ch, const uint64_t *start, const uint64_t *cell_indices,
-                                  const Cell *cells, const Bytes48 *proofs_bytes) {
-    hashes.what = "cell group transcript hash jobs";
-    hashes.n = ch.G;
-    CellGroupsChunk *c = &ch;
-    hashes.fn = [c, start, cell_indices, cells, proofs_bytes](size_t g) {
-        const size_t a = (size_t)start[g], n = (size_t)(start[g + 1] - start[g]);
-        if (n == 0) return;
-        compute_verify_cell_kzg_proof_batch_challenge((fr_t *)&c->r[g], c->pair_bytes.data() + c->plan.pair_off[g],
-                                                      c->plan.pair_off[g + 1] - c->plan.pair_off[g], c->plan.cell_pair.data() + a,
-                                                      cell_indices + a, cells + a, proofs_bytes + a, n);
-    };
-}
-
-// the index maps, one upload
-static void cell_groups_maps(CellGroupsChunk &ch) {
-    const CellGroupsPlan &plan = ch.plan;
     IndexMaps &maps = ch.maps;
-    maps.words.reserve(4 * ch.N + 4 * ch.G + 2 * plan.P + 2 * plan.R + plan.total + 8);
-    ch.m_grp = maps.put(plan.cell_grp), ch.m_col = maps.put(plan.cell_col), ch.m_gd = maps.put(plan.gd);
+    maps.words.reserve(4 * ch.N + 4 * G + 2 * plan.P + 2 * plan.R + plan.total + 8);
+    ch.m_grp = maps.put(plan.item_grp), ch.m_col = maps.put(plan.item_col), ch.m_gd = maps.put(plan.gd);
     ch.m_pstart = maps.put(plan.pair_start), ch.m_pmem = maps.put(plan.pair_members), ch.m_pterm = maps.put(plan.pair_term);
     ch.m_rstart = maps.put(plan.row_start), ch.m_rorder = maps.put(plan.row_order), ch.m_rcol = maps.put(plan.row_col);
     ch.m_grows = maps.put(plan.grp_rows), ch.m_src = maps.put(plan.term_src);
 }
 
+// One SHA-256 stream per group (coset_verify_digest on the group's slice, its commitments deduplicated within the
+// group; at e = 6 eip7594.c:390-482), on the host pool: the jobs, for the caller to start once the values' bytes are
+// where `evals` points
+static void coset_groups_hash_jobs(BackgroundFor &hashes, CosetGroupsChunk &ch, const uint64_t *start, const uint64_t *coset_indices,
+                                   const Bytes32 *evals, const Bytes48 *proofs_bytes) {
+    hashes.what = "coset group transcript hash jobs";
+    hashes.n = ch.G;
+    CosetGroupsChunk *c = &ch;
+    hashes.fn = [c, start, coset_indices, evals, proofs_bytes](size_t g) {
+        const size_t a = (size_t)start[g], n = (size_t)(start[g + 1] - start[g]);
+        if (n == 0) return;
+        const CosetGroupsPlan &plan = c->plan;
+        uint8_t digest[32];
+        coset_verify_digest<Sha256>(digest, c->pair_bytes[plan.pair_off[g]].bytes, plan.pair_off[g + 1] - plan.pair_off[g],
+                                    plan.item_pair.data() + a, coset_indices + a, evals[a << c->e].bytes, proofs_bytes[a].bytes, n, c->e);
+        c->r[g] = fr_from_bytes_reduce(digest);
+    };
+}
+
 // The arena of the call: what both halves use, and `own` bytes for the caller's inputs (taken by the caller, after this)
-static C_KZG_RET cell_groups_alloc(dev::DeviceCtx *ctx, CellGroupsChunk &ch, size_t own) {
-    const size_t N = ch.N, G = ch.G, ncu = ch.ncu, l = FIELD_ELEMENTS_PER_CELL, total = ch.plan.total;
+static C_KZG_RET coset_groups_alloc(dev::DeviceCtx *ctx, CosetGroupsChunk &ch, size_t own) {
+    const size_t N = ch.N, G = ch.G, ncu = ch.ncu, l = (size_t)1 << ch.e, R = ch.plan.R, total = ch.plan.total;
     Arena &ar = ctx->api_arena;
-    OKM(ar.begin((N + ncu) * (48 + 2) + ch.npool * sizeof(G1Affine) + (N * l + N + ch.R_ntt * l + G) * sizeof(Fr) +
-                 ch.maps.words.size() * 4 + total * (32 + sizeof(G1Affine)) + ch.nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) +
-                 (2 * G + 1) * 4 + 20 * 256 + own));
+    OKM(ar.begin((N + ncu) * (48 + 2) + ch.npool * sizeof(G1Affine) + (N * l + N + R * l + G) * sizeof(Fr) + ch.maps.words.size() * 4 +
+                 total * (32 + sizeof(G1Affine)) + ch.nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) + (2 * G + 1) * 4 + 20 * 256 +
+                 own));
     ch.d_ptb = ABuf<uint8_t>(ar, (N + ncu) * 48), ch.d_st = ABuf<uint8_t>(ar, N + ncu), ch.d_st2 = ABuf<uint8_t>(ar, N + ncu);
     ch.d_pool = ABuf<G1Affine>(ar, ch.npool), ch.d_jobpts = ABuf<G1Affine>(ar, total), ch.d_out = ABuf<G1Affine>(ar, 2 * G);
-    ch.d_cellfr = ABuf<Fr>(ar, N * l), ch.d_rp = ABuf<Fr>(ar, N), ch.d_rows = ABuf<Fr>(ar, ch.R_ntt * l), ch.d_r = ABuf<Fr>(ar, G);
+    ch.d_itemfr = ABuf<Fr>(ar, N * l), ch.d_rp = ABuf<Fr>(ar, N), ch.d_rows = ABuf<Fr>(ar, R * l), ch.d_r = ABuf<Fr>(ar, G);
     ch.d_maps = ABuf<uint32_t>(ar, ch.maps.words.size()), ch.d_sc = ABuf<uint32_t>(ar, total * 8), ch.d_off = ABuf<uint32_t>(ar, 2 * G + 1);
     ch.d_part = ABuf<G1XYZZ>(ar, ch.nparts);
-    OKM(ch.d_ptb.p && ch.d_st.p && ch.d_st2.p && ch.d_pool.p && ch.d_jobpts.p && ch.d_out.p && ch.d_cellfr.p && ch.d_rp.p &&
+    OKM(ch.d_ptb.p && ch.d_st.p && ch.d_st2.p && ch.d_pool.p && ch.d_jobpts.p && ch.d_out.p && ch.d_itemfr.p && ch.d_rp.p &&
         ch.d_rows.p && ch.d_r.p && ch.d_maps.p && ch.d_sc.p && ch.d_off.p && ch.d_part.p);
     return C_KZG_OK;
 }
 
 // the compressed points: proofs [0, N), the chunk's distinct commitments [N, N + ncu)
-static C_KZG_RET cell_groups_upload_points(dev::DeviceCtx *ctx, CellGroupsChunk &ch, const Bytes48 *proofs_bytes) {
+static C_KZG_RET coset_groups_upload_points(dev::DeviceCtx *ctx, CosetGroupsChunk &ch, const Bytes48 *proofs_bytes) {
     OKB(hipMemcpyAsync(ch.d_ptb.p, proofs_bytes, ch.N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     OKB(hipMemcpyAsync(ch.d_ptb.p + ch.N * 48, ch.uniq.data(), ch.ncu * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     return C_KZG_OK;
 }
 
 // what the sums need besides the scalars, enqueued underneath the transcript hashes: the jobs' points, gathered by
-// index (the commitments and the 64 setup points are shared between groups), and zeroes where scalars and rows are not
-// written
-static C_KZG_RET cell_groups_jobs_enqueue(dev::DeviceCtx *ctx, CellGroupsChunk &ch) {
-    const size_t l = FIELD_ELEMENTS_PER_CELL, R = ch.plan.R;
-    OKB(hipMemcpyAsync(ch.d_pool.p + ch.N + ch.ncu, ctx->d_mono, l * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
+// index (the commitments and the l setup points are shared between groups), and zeroes where no scalar is written
+static C_KZG_RET coset_groups_jobs_enqueue(dev::DeviceCtx *ctx, CosetGroupsChunk &ch) {
+    OKB(hipMemcpyAsync(ch.d_pool.p + ch.N + ch.ncu, ctx->d_mono, ((size_t)1 << ch.e) * sizeof(G1Affine), hipMemcpyDeviceToDevice,
+                       ctx->stream) == hipSuccess);
     RC(dev::group_gather_points_enqueue(ctx, ch.d_jobpts.p, ch.d_pool.p, ch.d_maps.p + ch.m_src, ch.plan.total));
     OKB(hipMemsetAsync(ch.d_sc.p, 0, ch.plan.total * 32, ctx->stream) == hipSuccess);
-    if (ch.R_ntt > R) OKB(hipMemsetAsync(ch.d_rows.p + R * l, 0, (ch.R_ntt - R) * l * sizeof(Fr), ctx->stream) == hipSuccess);
     return C_KZG_OK;
 }
 
-// The second half: d_cellfr holds the cells as field elements, the points are being validated, the jobs' points are
+// The second half: d_itemfr holds the values as field elements, the points are being validated, the jobs' points are
 // gathered, flags_ev is recorded behind the copy of the field-element flags, and the hash jobs are running (or will
-// run here).  start[G + 1] in cells.
-static C_KZG_RET cell_groups_from_fr(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const uint64_t *start, CellGroupsChunk &ch,
-                                     BackgroundFor &hashes, const PreparedG2 *pg, StagedTrace &tr) {
+// run here).  start[G + 1] in items.
+static C_KZG_RET coset_groups_from_fr(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const uint64_t *start, CosetGroupsChunk &ch,
+                                      BackgroundFor &hashes, const PreparedG2 *pg, const KZGSettings *s, StagedTrace &tr) {
     const size_t N = ch.N, G = ch.G, R = ch.plan.R;
+    const int e = ch.e;
     uint32_t *const m = ch.d_maps.p;
     hashes.finish();
     tr.mark("hashes");
     OKB(hipMemcpyAsync(ch.d_r.p, ch.r.data(), G * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    RC(dev::group_rlc_scalars_enqueue(ctx, ch.d_rp.p, ch.d_sc.p, m + ch.m_grp, m + ch.m_col, m + ch.m_gd, ch.d_r.p, m + ch.m_pstart,
-                                      m + ch.m_pmem, m + ch.m_pterm, N, G, ch.plan.P));
+    RC(dev::coset_group_rlc_scalars_enqueue(ctx, ch.d_rp.p, ch.d_sc.p, m + ch.m_grp, m + ch.m_col, m + ch.m_gd, ch.d_r.p, m + ch.m_pstart,
+                                            m + ch.m_pmem, m + ch.m_pterm, N, G, ch.plan.P, e));
     OKB(tr.stage("scalars"));
-    // per row: cell data is in bit-reversed order -> DIT inverse NTT(64) gives the interpolation polynomial over the
-    // row's coset; the group's rows are summed with their own coset scaling (eip7594.c:661-752)
-    RC(dev::group_cell_aggregate_device(ctx, ch.d_rows.p, ch.d_cellfr.p, ch.d_rp.p, m + ch.m_rstart, m + ch.m_rorder, N, R));
-    RC(dev::fr_ntt_batch(ctx, ch.d_rows.p, ch.R_ntt, 6, false, true, true));
-    RC(dev::group_interp_sum_device(ctx, ch.d_sc.p, ch.d_rows.p, m + ch.m_grows, m + ch.m_rcol, m + ch.m_gd, G));
+    // per row: the values are in bit-reversed order -> the interpolation polynomial over the row's coset, scaled by the
+    // coset's own factors; then the group's rows are added up (at e = 6 eip7594.c:661-752)
+    RC(dev::coset_group_aggregate_device(ctx, ch.d_rows.p, ch.d_itemfr.p, ch.d_rp.p, m + ch.m_rstart, m + ch.m_rorder, N, R, e));
+    RC(dev::coset_group_interp_device(ctx, ch.d_rows.p, m + ch.m_rcol, R, e));
+    RC(dev::coset_group_interp_sum_device(ctx, ch.d_sc.p, ch.d_rows.p, m + ch.m_grows, m + ch.m_gd, R, G, e));
     OKB(tr.stage("aggregation"));
     std::vector<G1Affine> sums;
     RC(group_sums(ctx, sums, ch.plan, G, ch.d_out, ch.d_part.p, ch.d_off.p, ch.d_jobpts.p, ch.d_sc.p));
@@ -2547,17 +2563,19 @@ static C_KZG_RET cell_groups_from_fr(dev::DeviceCtx *ctx, bool *ok, uint8_t *sta
     OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
     const uint8_t *h_st = ch.h_st, *h_st2 = ch.h_st2;
     for (size_t i = 0; i < N; i++) {
-        const size_t c = N + ch.cell_commit[i];
-        if (h_st[i] || h_st2[i] || h_st[c] || h_st2[c] || ch.h_bad[i >> ch.bad_shift]) ch.invalid[ch.plan.cell_grp[i]] = 1;
+        const size_t c = N + ch.item_commit[i];
+        if (h_st[i] || h_st2[i] || h_st[c] || h_st2[c] || ch.h_bad[i >> ch.bad_shift]) ch.invalid[ch.plan.item_grp[i]] = 1;
     }
-    // e(final_g, [1]_2) * e(-proof_lc_g, [s^64]_2) == 1, one check per valid group, on the host pool
-    return settle_groups(ok, status, start, G, ch.invalid, sums, pg, pg->s64, tr);
+    // e(final_g, [1]_2) * e(-proof_lc_g, [s^l]_2) == 1, one check per valid group, on the host pool
+    return settle_groups(ok, status, start, G, ch.invalid, sums, pg, prepared_s_pow2(pg, e, s), tr);
 }
 
-static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
-                                       const uint64_t *cell_indices, const Cell *cells, const Bytes48 *proofs_bytes,
-                                       const uint64_t *start, size_t G, const KZGSettings *s) {
-    const size_t N = (size_t)start[G], l = FIELD_ELEMENTS_PER_CELL;
+// The first half with the items in host memory, at any e: the values are uploaded and parsed (a flag per item), the
+// transcripts hashed from the caller's bytes underneath.  `what`: the entry's name in a trace.
+static C_KZG_RET verify_coset_groups_on(dev::DeviceCtx *ctx, const char *what, bool *ok, uint8_t *status,
+                                        const Bytes48 *commitments_bytes, const uint64_t *coset_indices, const Bytes32 *evals,
+                                        const Bytes48 *proofs_bytes, const uint64_t *start, size_t G, int e, const KZGSettings *s) {
+    const size_t N = (size_t)start[G], l = (size_t)1 << e, m = coset_verify_cosets(e);
     for (size_t g = 0; g < G; g++) {
         ok[g] = false;
         status[g] = (uint8_t)C_KZG_OK;
@@ -2568,38 +2586,27 @@ static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     }
     const PreparedG2 *pg = prepared_of(ctx);
     if (!pg) return C_KZG_ERROR;
-    StagedTrace tr("verify_cell_groups", ctx->stream);
-    CellGroupsChunk ch;
+    StagedTrace tr(what, ctx->stream);
+    CosetGroupsChunk ch;
     ch.invalid.assign(G, 0);
-    // the chunk's distinct commitments: validated once, however many groups repeat them
-    ch.cell_commit.resize(N);
-    {
-        std::unordered_map<std::string_view, uint32_t> ids;
-        ids.reserve(256);
-        for (size_t i = 0; i < N; i++) {
-            auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(commitments_bytes[i].bytes), 48), (uint32_t)ch.uniq.size());
-            if (it.second) ch.uniq.push_back(commitments_bytes[i]);
-            ch.cell_commit[i] = it.first->second;
-        }
-    }
+    coset_groups_dedup(ch, commitments_bytes, N, 1);
     for (size_t i = 0, g = 0; i < N; i++) {
         while (i >= start[g + 1]) g++;
-        if (cell_indices[i] >= CELLS_PER_EXT_BLOB) ch.invalid[g] = 1;
+        if (coset_indices[i] >= m) ch.invalid[g] = 1;
     }
-    cell_groups_plan(ch, start, G, cell_indices);
+    coset_groups_plan(ch, start, G, coset_indices, e);
     const size_t ncu = ch.ncu;
-    // The transcripts are hashed from the caller's cells, on the host pool, underneath the copies and the validation
+    // The transcripts are hashed from the caller's bytes, on the host pool, underneath the copies and the validation
     // below.  (declared after everything its jobs touch: an early return waits for them first)
     BackgroundFor hashes;
-    cell_groups_hash_jobs(hashes, ch, start, cell_indices, cells, proofs_bytes);
+    coset_groups_hash_jobs(hashes, ch, start, coset_indices, evals, proofs_bytes);
     hashes.start();
-    cell_groups_maps(ch);
     Arena &ar = ctx->api_arena;
     ArenaTrim trim(ar);
-    RC(cell_groups_alloc(ctx, ch, N * BYTES_PER_CELL + N * 4));
-    ABuf<uint8_t> d_cells(ar, N * BYTES_PER_CELL);
+    RC(coset_groups_alloc(ctx, ch, N * l * 32 + N * 4));
+    ABuf<uint8_t> d_ev(ar, N * l * 32);
     ABuf<uint32_t> d_bad(ar, N);
-    OKM(d_cells.p && d_bad.p);
+    OKM(d_ev.p && d_bad.p);
     OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, 2 * (N + ncu) + N * 4));
     uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[0]), *h_st2 = h_st + (N + ncu);
     uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
@@ -2610,18 +2617,22 @@ static C_KZG_RET verify_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *s
     StreamDrain drain_main{ctx->stream}, drain{ctx->copy_stream};
     // (all copies from pageable memory first: such a copy returns only when it is done, so it must not queue behind
     // the validation kernels)
-    RC(cell_groups_upload_points(ctx, ch, proofs_bytes));
-    OKB(hipMemcpyAsync(d_cells.p, cells, N * BYTES_PER_CELL, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
+    RC(coset_groups_upload_points(ctx, ch, proofs_bytes));
+    OKB(hipMemcpyAsync(d_ev.p, evals, N * l * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
     OKB(ch.maps.upload(ch.d_maps.p, ctx->stream));
     RC(validate_points_two_streams(ctx, ch.d_pool.p, ch.d_st.p, ch.d_st2.p, ch.d_ptb.p, N + ncu, h_st, h_st2));
     OKB(hipMemsetAsync(d_bad.p, 0, N * 4, ctx->stream) == hipSuccess);
-    RC(dev::bytes_to_fr_batch(ctx, ch.d_cellfr.p, d_bad.p, d_cells.p, N * l, (uint32_t)l));
+    RC(dev::bytes_to_fr_batch(ctx, ch.d_itemfr.p, d_bad.p, d_ev.p, N * l, (uint32_t)l));   // a flag per item
     OKB(hipMemcpyAsync(h_bad, d_bad.p, N * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
     OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
-    RC(cell_groups_jobs_enqueue(ctx, ch));
+    RC(coset_groups_jobs_enqueue(ctx, ch));
     OKB(tr.stage("copies and validation (underneath the transcript hashes)"));
-    return cell_groups_from_fr(ctx, ok, status, start, ch, hashes, pg, tr);
+    return coset_groups_from_fr(ctx, ok, status, start, ch, hashes, pg, s, tr);
 }
+
+// ------------------------------------------------------------------------------------------
+// ckzg_hip_verify_cell_kzg_proof_batch_groups: many cell batches in one call, one verdict per group
+// ------------------------------------------------------------------------------------------
 
 extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
                                                                 const uint64_t *cell_indices, const Cell *cells,
@@ -2642,142 +2653,14 @@ extern "C" C_KZG_RET ckzg_hip_verify_cell_kzg_proof_batch_groups(bool *ok, uint8
             });
         },
         [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, const uint64_t *start, size_t G) {
-            return verify_cell_groups_on(ctx, ok, status, commitments_bytes + a, cell_indices + a, cells + a, proofs_bytes + a,
-                                         start, G, s);
+            return verify_coset_groups_on(ctx, "verify_cell_groups", ok, status, commitments_bytes + a, cell_indices + a,
+                                          cell_values(cells + a), proofs_bytes + a, start, G, CELL_LOG, s);
         });
 }
 
 // ------------------------------------------------------------------------------------------
 // ckzg_hip_verify_coset_kzg_proof_batch_groups: many coset batches in one call, one verdict per group, at every coset size
 // ------------------------------------------------------------------------------------------
-
-// G groups over start[G] items (start[0] = 0) of l = 2^e values each on one device, as one chunk: verify_cell_groups_on
-// with the coset size a parameter (index maps and launch pickers: coset_groups_plan.hpp, device stages:
-// coset_groups.hip).  As there, everything that costs latency rather than work is paid once for
-// the chunk -- the points validated in one launch each with the commitments deduplicated across the chunk, the values
-// converted in one, the groups' transcripts (coset_verify_digest on each slice) hashed on the host pool underneath -- and
-// then the four segmented stages make every group's scalars, aggregate its rows, interpolate them and add them up, and
-// final_g = sum w_j C_j + sum r^i x_c^l proof_i - sum interp_g[k] [s^k]_1 and proof_lc_g = sum r^i proof_i of every
-// group run in ONE pass of the ladder kernels.  Every valid group gets its own two-pairing check against [s^l]_2.
-static C_KZG_RET verify_coset_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
-                                        const uint64_t *coset_indices, const Bytes32 *evals, const Bytes48 *proofs_bytes,
-                                        const uint64_t *start, size_t G, int e, const KZGSettings *s) {
-    static const size_t quad_max = (size_t)dev::ab_knob("CKZG_HIP_QUAD_MAX", 8192);
-    const size_t N = (size_t)start[G], l = (size_t)1 << e, m = coset_verify_cosets(e);
-    for (size_t g = 0; g < G; g++) {
-        ok[g] = false;
-        status[g] = (uint8_t)C_KZG_OK;
-    }
-    if (N == 0) {
-        for (size_t g = 0; g < G; g++) ok[g] = true;
-        return C_KZG_OK;
-    }
-    const PreparedG2 *pg = prepared_of(ctx);
-    if (!pg) return C_KZG_ERROR;
-    const host::G2Prepared &q2 = prepared_s_pow2(pg, e, s);
-    StagedTrace tr("verify_coset_groups", ctx->stream);
-    std::vector<uint8_t> invalid(G, 0);
-    // the chunk's distinct commitments: validated once, however many groups repeat them
-    std::vector<uint32_t> item_commit(N);
-    std::vector<Bytes48> uniq;
-    {
-        std::unordered_map<std::string_view, uint32_t> ids;
-        ids.reserve(256);
-        for (size_t i = 0; i < N; i++) {
-            auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(commitments_bytes[i].bytes), 48), (uint32_t)uniq.size());
-            if (it.second) uniq.push_back(commitments_bytes[i]);
-            item_commit[i] = it.first->second;
-        }
-    }
-    for (size_t i = 0, g = 0; i < N; i++) {
-        while (i >= start[g + 1]) g++;
-        if (coset_indices[i] >= m) invalid[g] = 1;
-    }
-    const size_t ncu = uniq.size();
-    CosetGroupsPlan plan;
-    build_coset_groups_plan(plan, start, G, item_commit.data(), ncu, coset_indices, e, quad_max);
-    const size_t P = plan.P, R = plan.R, total = plan.total, npool = N + ncu + l, nparts = total / plan.per();
-    std::vector<Bytes48> pair_bytes(P);   // the commitments of every group in the order of its transcript
-    for (size_t j = 0; j < P; j++) pair_bytes[j] = uniq[plan.pair_commit[j]];
-    std::vector<Fr> r(G, Fr::zero());
-    // One SHA-256 stream per group, from the caller's bytes, on the host pool, underneath the copies and the validation
-    // below.  (declared after everything its jobs touch: an early return waits for them first)
-    BackgroundFor hashes;
-    hashes.what = "coset group transcript hash jobs";
-    hashes.n = G;
-    hashes.fn = [&plan, &pair_bytes, &r, start, coset_indices, evals, proofs_bytes, e](size_t g) {
-        const size_t a = (size_t)start[g], n = (size_t)(start[g + 1] - start[g]);
-        if (n == 0) return;
-        uint8_t digest[32];
-        coset_verify_digest<Sha256>(digest, pair_bytes[plan.pair_off[g]].bytes, plan.pair_off[g + 1] - plan.pair_off[g],
-                                    plan.item_pair.data() + a, coset_indices + a, evals[a << e].bytes, proofs_bytes[a].bytes, n, e);
-        r[g] = fr_from_bytes_reduce(digest);
-    };
-    hashes.start();
-    IndexMaps maps;
-    maps.words.reserve(4 * N + 4 * G + 2 * P + 2 * R + total + 8);
-    const size_t m_grp = maps.put(plan.item_grp), m_col = maps.put(plan.item_col), m_gd = maps.put(plan.gd),
-                 m_pstart = maps.put(plan.pair_start), m_pmem = maps.put(plan.pair_members), m_pterm = maps.put(plan.pair_term),
-                 m_rstart = maps.put(plan.row_start), m_rorder = maps.put(plan.row_order), m_rcol = maps.put(plan.row_col),
-                 m_grows = maps.put(plan.grp_rows), m_src = maps.put(plan.term_src);
-    Arena &ar = ctx->api_arena;
-    ArenaTrim trim(ar);
-    OKM(ar.begin((N + ncu) * (48 + 2) + npool * sizeof(G1Affine) + (N * l + N + R * l + G) * sizeof(Fr) + maps.words.size() * 4 +
-                 total * (32 + sizeof(G1Affine)) + nparts * sizeof(G1XYZZ) + 2 * G * sizeof(G1Affine) + (2 * G + 1) * 4 +
-                 N * l * 32 + N * 4 + 20 * 256));
-    ABuf<uint8_t> d_ptb(ar, (N + ncu) * 48), d_st(ar, N + ncu), d_st2(ar, N + ncu), d_ev(ar, N * l * 32);
-    ABuf<G1Affine> d_pool(ar, npool), d_jobpts(ar, total), d_out(ar, 2 * G);   // pool: proofs, distinct commitments, g1_values_monomial[0 .. l - 1]
-    ABuf<Fr> d_evfr(ar, N * l), d_rp(ar, N), d_rows(ar, R * l), d_r(ar, G);
-    ABuf<uint32_t> d_maps(ar, maps.words.size()), d_sc(ar, total * 8), d_off(ar, 2 * G + 1), d_bad(ar, N);
-    ABuf<G1XYZZ> d_part(ar, nparts);
-    OKM(d_ptb.p && d_st.p && d_st2.p && d_ev.p && d_pool.p && d_jobpts.p && d_out.p && d_evfr.p && d_rp.p && d_rows.p && d_r.p &&
-        d_maps.p && d_sc.p && d_off.p && d_bad.p && d_part.p);
-    OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, 2 * (N + ncu) + N * 4));
-    uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[0]), *h_st2 = h_st + (N + ncu);
-    uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
-    OKB(dev::ensure_event(ctx->pts_ev) == hipSuccess && dev::ensure_event(ctx->subgroup_ev) == hipSuccess &&
-        dev::ensure_event(ctx->flags_ev) == hipSuccess);
-    // whatever path leaves this function, both streams must be idle before the arena is reused
-    StreamDrain drain_main{ctx->stream}, drain{ctx->copy_stream};
-    // (all copies from pageable memory first: such a copy returns only when it is done, so it must not queue behind
-    // the validation kernels)
-    OKB(hipMemcpyAsync(d_ptb.p, proofs_bytes, N * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemcpyAsync(d_ptb.p + N * 48, uniq.data(), ncu * 48, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(hipMemcpyAsync(d_ev.p, evals, N * l * 32, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    OKB(maps.upload(d_maps.p, ctx->stream));
-    RC(validate_points_two_streams(ctx, d_pool.p, d_st.p, d_st2.p, d_ptb.p, N + ncu, h_st, h_st2));
-    OKB(hipMemsetAsync(d_bad.p, 0, N * 4, ctx->stream) == hipSuccess);
-    RC(dev::bytes_to_fr_batch(ctx, d_evfr.p, d_bad.p, d_ev.p, N * l, (uint32_t)l));   // a flag per item
-    OKB(hipMemcpyAsync(h_bad, d_bad.p, N * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
-    OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
-    // what the sums need besides the scalars: the jobs' points, gathered by index, and zeroes where no scalar is written
-    uint32_t *const dm = d_maps.p;
-    OKB(hipMemcpyAsync(d_pool.p + N + ncu, ctx->d_mono, l * sizeof(G1Affine), hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess);
-    RC(dev::group_gather_points_enqueue(ctx, d_jobpts.p, d_pool.p, dm + m_src, total));
-    OKB(hipMemsetAsync(d_sc.p, 0, total * 32, ctx->stream) == hipSuccess);
-    OKB(tr.stage("copies and validation (underneath the transcript hashes)"));
-    hashes.finish();
-    tr.mark("hashes");
-    OKB(hipMemcpyAsync(d_r.p, r.data(), G * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    RC(dev::coset_group_rlc_scalars_enqueue(ctx, d_rp.p, d_sc.p, dm + m_grp, dm + m_col, dm + m_gd, d_r.p, dm + m_pstart, dm + m_pmem,
-                                            dm + m_pterm, N, G, P, e));
-    OKB(tr.stage("scalars"));
-    RC(dev::coset_group_aggregate_device(ctx, d_rows.p, d_evfr.p, d_rp.p, dm + m_rstart, dm + m_rorder, N, R, e));
-    RC(dev::coset_group_interp_device(ctx, d_rows.p, dm + m_rcol, R, e));
-    RC(dev::coset_group_interp_sum_device(ctx, d_sc.p, d_rows.p, dm + m_grows, dm + m_gd, R, G, e));
-    OKB(tr.stage("aggregation"));
-    std::vector<G1Affine> sums;
-    RC(group_sums(ctx, sums, plan, G, d_out, d_part.p, d_off.p, d_jobpts.p, d_sc.p));
-    tr.mark("sums");
-    // the validation flags, folded into per-group status
-    OKB(dev::sync_event(ctx->flags_ev) == hipSuccess && dev::sync_event(ctx->subgroup_ev) == hipSuccess);
-    for (size_t i = 0; i < N; i++) {
-        const size_t c = N + item_commit[i];
-        if (h_st[i] || h_st2[i] || h_st[c] || h_st2[c] || h_bad[i]) invalid[plan.item_grp[i]] = 1;
-    }
-    // e(final_g, [1]_2) * e(-proof_lc_g, [s^l]_2) == 1, one check per valid group, on the host pool
-    return settle_groups(ok, status, start, G, invalid, sums, pg, q2, tr);
-}
 
 extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_groups(bool *ok, uint8_t *status, const Bytes48 *commitments_bytes,
                                                                  const uint64_t *coset_indices, const Bytes32 *evals,
@@ -2800,8 +2683,8 @@ extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_groups(bool *ok, uint
             });
         },
         [&](dev::DeviceCtx *ctx, bool *ok, uint8_t *status, uint64_t a, const uint64_t *start, size_t G) {
-            return verify_coset_groups_on(ctx, ok, status, commitments_bytes + a, coset_indices + a, evals + (a << e), proofs_bytes + a,
-                                          start, G, e, s);
+            return verify_coset_groups_on(ctx, "verify_coset_groups", ok, status, commitments_bytes + a, coset_indices + a,
+                                          evals + (a << e), proofs_bytes + a, start, G, e, s);
         });
 }
 
@@ -2811,12 +2694,12 @@ extern "C" C_KZG_RET ckzg_hip_verify_coset_kzg_proof_batch_groups(bool *ok, uint
 
 // G groups over start[G] blobs (start[0] = 0) on one device, as one chunk: compute_cells of every blob, then
 // verify_cell_kzg_proof_batch per group over all its cells, without the cells leaving HBM except as bytes for the
-// transcript.  The first half of a cell-groups chunk (CellGroupsChunk) with the blobs as input: bytes -> Fr (a flag per
-// blob), DIT inverse NTT(4096), zero extension, DIF NTT(8192) straight into the buffer the aggregation reads -- the
-// 8192 evaluations of a blob ARE its 128 cells in flat order, canonical by construction, so nothing is parsed twice --
-// and Fr -> bytes into page-locked staging, where the host pool hashes one SHA-256 stream per group with the
+// transcript.  The first half of a chunk of groups (CosetGroupsChunk at e = 6) with the blobs as input: bytes -> Fr (a
+// flag per blob), DIT inverse NTT(4096), zero extension, DIF NTT(8192) straight into the buffer the aggregation reads --
+// the 8192 evaluations of a blob ARE its 128 cells in flat order, canonical by construction, so nothing is parsed twice
+// -- and Fr -> bytes into page-locked staging, where the host pool hashes one SHA-256 stream per group with the
 // reference's transcript code.  Commitment ids and the indices k = 0..127 per blob are implied.  Then
-// cell_groups_from_fr.  Plain streams only.
+// coset_groups_from_fr.  Plain streams only.
 static C_KZG_RET verify_blob_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8_t *status, const Blob *blobs, const Bytes48 *cb,
                                             const Bytes48 *pb, const uint64_t *start, size_t G, const KZGSettings *s) {
     const size_t NB = (size_t)start[G], N = NB * CELLS_PER_EXT_BLOB;
@@ -2831,40 +2714,28 @@ static C_KZG_RET verify_blob_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8
     const PreparedG2 *pg = prepared_of(ctx);
     if (!pg) return C_KZG_ERROR;
     StagedTrace tr("verify_blob_cell_groups", ctx->stream);
-    CellGroupsChunk ch;
+    CosetGroupsChunk ch;
     ch.invalid.assign(G, 0);
     // what the caller of the cell call would have had to write out: the groups in cells, every blob's commitment for
     // each of its 128 cells (as an id: the chunk's distinct commitments are validated once), the indices 0..127
     std::vector<uint64_t> cell_start(G + 1), cell_indices(N);
     for (size_t g = 0; g <= G; g++) cell_start[g] = start[g] * CELLS_PER_EXT_BLOB;
-    ch.cell_commit.resize(N);
-    {
-        std::unordered_map<std::string_view, uint32_t> ids;
-        ids.reserve(256);
-        for (size_t b = 0; b < NB; b++) {
-            auto it = ids.emplace(std::string_view(reinterpret_cast<const char *>(cb[b].bytes), 48), (uint32_t)ch.uniq.size());
-            if (it.second) ch.uniq.push_back(cb[b]);
-            for (size_t k = 0; k < CELLS_PER_EXT_BLOB; k++) {
-                ch.cell_commit[b * CELLS_PER_EXT_BLOB + k] = it.first->second;
-                cell_indices[b * CELLS_PER_EXT_BLOB + k] = k;
-            }
-        }
-    }
-    cell_groups_plan(ch, cell_start.data(), G, cell_indices.data());
-    cell_groups_maps(ch);
+    for (size_t i = 0; i < N; i++) cell_indices[i] = i % CELLS_PER_EXT_BLOB;
+    coset_groups_dedup(ch, cb, NB, CELLS_PER_EXT_BLOB);
+    coset_groups_plan(ch, cell_start.data(), G, cell_indices.data(), CELL_LOG);
     const size_t ncu = ch.ncu;
     // page-locked: the cells' bytes for the transcripts | blob flags, point flags
     OKM(ensure_pinned(ctx->h_out, ctx->h_out_bytes, N * (size_t)BYTES_PER_CELL));   // (> NB * 4 + 2 * (N + ncu))
-    const Cell *h_cells = static_cast<const Cell *>(ctx->h_out[0]);
+    const Bytes32 *h_cells = static_cast<const Bytes32 *>(ctx->h_out[0]);
     uint32_t *h_bad = static_cast<uint32_t *>(ctx->h_out[1]);
     uint8_t *h_st = static_cast<uint8_t *>(ctx->h_out[1]) + NB * 4, *h_st2 = h_st + (N + ncu);
     ch.h_st = h_st, ch.h_st2 = h_st2, ch.h_bad = h_bad, ch.bad_shift = 7;   // a flag per blob: 128 cells
     // (declared after everything its jobs touch: an early return waits for them first)
     BackgroundFor hashes;
-    cell_groups_hash_jobs(hashes, ch, cell_start.data(), cell_indices.data(), h_cells, pb);
+    coset_groups_hash_jobs(hashes, ch, cell_start.data(), cell_indices.data(), h_cells, pb);
     Arena &ar = ctx->api_arena;
     ArenaTrim trim(ar);
-    RC(cell_groups_alloc(ctx, ch, NB * ((size_t)BYTES_PER_BLOB + FIELD_ELEMENTS_PER_BLOB * sizeof(Fr) + 4) + N * (size_t)BYTES_PER_CELL + 4 * 256));
+    RC(coset_groups_alloc(ctx, ch,NB * ((size_t)BYTES_PER_BLOB + FIELD_ELEMENTS_PER_BLOB * sizeof(Fr) + 4) + N * (size_t)BYTES_PER_CELL + 4 * 256));
     ABuf<uint8_t> d_blobs(ar, NB * (size_t)BYTES_PER_BLOB), d_cells(ar, N * (size_t)BYTES_PER_CELL);
     ABuf<Fr> d_poly(ar, NB * (size_t)FIELD_ELEMENTS_PER_BLOB);
     ABuf<uint32_t> d_bad(ar, NB);
@@ -2875,18 +2746,18 @@ static C_KZG_RET verify_blob_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8
     StreamDrain drain_main{ctx->stream}, drain{ctx->copy_stream};
     // (all copies from pageable memory first: such a copy returns only when it is done, so it must not queue behind a
     // kernel.  The blobs last: what follows them needs them.)
-    RC(cell_groups_upload_points(ctx, ch, pb));
+    RC(coset_groups_upload_points(ctx, ch, pb));
     OKB(ch.maps.upload(ch.d_maps.p, ctx->stream));
     OKB(hipMemcpyAsync(d_blobs.p, blobs, NB * (size_t)BYTES_PER_BLOB, hipMemcpyHostToDevice, ctx->stream) == hipSuccess);
-    // blobs -> cells: the evaluations land in d_cellfr, their bytes and the blobs' flags in page-locked memory
+    // blobs -> cells: the evaluations land in d_itemfr, their bytes and the blobs' flags in page-locked memory
     OKB(hipMemsetAsync(d_bad.p, 0, NB * 4, ctx->stream) == hipSuccess);
-    RC(dev::cells_stage_enqueue(ctx, d_cells.p, d_poly.p, ch.d_cellfr.p, d_bad.p, d_blobs.p, NB));
+    RC(dev::cells_stage_enqueue(ctx, d_cells.p, d_poly.p, ch.d_itemfr.p, d_bad.p, d_blobs.p, NB));
     OKB(hipMemcpyAsync(h_bad, d_bad.p, NB * 4, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
     OKB(hipMemcpyAsync(ctx->h_out[0], d_cells.p, N * (size_t)BYTES_PER_CELL, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess);
     OKB(hipEventRecord(ctx->flags_ev, ctx->stream) == hipSuccess);
     // behind the cells on the stream, underneath the hashes in time: point validation, the jobs' points, the zeroing
     RC(validate_points_two_streams(ctx, ch.d_pool.p, ch.d_st.p, ch.d_st2.p, ch.d_ptb.p, N + ncu, h_st, h_st2));
-    RC(cell_groups_jobs_enqueue(ctx, ch));
+    RC(coset_groups_jobs_enqueue(ctx, ch));
     // The hash jobs read the staging buffer, so they start only when the event behind its copy has happened.  No
     // verdict can show a mistake here: any non-degenerate r gives the same verdict, a challenge hashed from stale or
     // half-written bytes included -- only the soundness of the check would be gone.  The order is therefore right by
@@ -2895,7 +2766,7 @@ static C_KZG_RET verify_blob_cell_groups_on(dev::DeviceCtx *ctx, bool *ok, uint8
     OKB(dev::sync_event(ctx->flags_ev) == hipSuccess);
     hashes.start();
     OKB(tr.stage("copies, blobs to cells, validation (the last underneath the transcript hashes)"));
-    return cell_groups_from_fr(ctx, ok, status, cell_start.data(), ch, hashes, pg, tr);
+    return coset_groups_from_fr(ctx, ok, status, cell_start.data(), ch, hashes, pg, s, tr);
 }
 
 // One group of n blobs through the single-batch path (a chunk of one group: a call of one group, or a group larger
@@ -2945,6 +2816,8 @@ extern "C" C_KZG_RET ckzg_hip_verify_blob_cell_kzg_proof_batch_groups(bool *ok, 
                                                                      const Bytes48 *cell_proofs_bytes, const uint64_t *group_start,
                                                                      uint64_t num_groups, const KZGSettings *s) {
     static_assert(CKZG_HIP_BLOB_CELL_GROUPS_CHUNK_BLOBS * CELLS_PER_EXT_BLOB == CKZG_HIP_CELL_GROUPS_CHUNK_CELLS, "a chunk of blobs is a chunk of cells");
+    static_assert(CKZG_HIP_CELL_GROUPS_CHUNK_CELLS == CKZG_HIP_COSET_GROUPS_CHUNK_ITEMS && CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS == CKZG_HIP_COSET_GROUPS_CHUNK_GROUPS,
+                  "a chunk of cells is a chunk of cosets of 64");
     // chunks of at most CKZG_HIP_BLOB_CELL_GROUPS_CHUNK_BLOBS blobs / CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS groups
     return verify_groups_entry(
         ok, status, group_start, num_groups, blobs && commitments_bytes && cell_proofs_bytes, s, CKZG_HIP_CELL_GROUPS_CHUNK_GROUPS,

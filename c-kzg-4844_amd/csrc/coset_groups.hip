@@ -14,8 +14,8 @@
 namespace ckzg {
 namespace dev {
 
-// Item i of group g gets r_g^(i - start_g) by square-and-multiply from its offset (k_group_rlc_scalars, verify.hip):
-// in Montgomery form for the aggregation, in canonical limbs on the item's proof in B_g, and times x_c^l of its coset
+// Item i of group g gets r_g^(i - start_g) by square-and-multiply from its offset (<= 2 log2 of the group's size
+// products, no lane waits for another): in Montgomery form for the aggregation, in canonical limbs on the item's proof in B_g, and times x_c^l of its coset
 // on the same proof in A_g.
 __global__ void k_coset_group_rlc_scalars(Fr *rp, uint32_t *sc, const uint32_t *item_grp, const uint32_t *item_col,
                                           const uint32_t *gd, const Fr *r, const Fr *roots, uint32_t n, uint32_t ngroups, int e) {

@@ -1,13 +1,14 @@
-// Index maps and launch decisions of ckzg_hip_verify_coset_kzg_proof_batch_groups: cell_groups_plan.hpp with the coset
-// size l = 2^e, e <= COSET_MAX_LOG, a parameter -- everything the segmented kernels of coset_groups.hip need to know about
+// Index maps and launch decisions of the cell check by groups at coset size l = 2^e, e <= COSET_MAX_LOG
+// (ckzg_hip_verify_coset_kzg_proof_batch_groups at its e; the cell and the blob-cell calls by groups at e = 6, where a
+// coset is a cell and a coset index a column) -- everything the segmented kernels of coset_groups.hip need to know about
 // which item belongs to which group, coset and commitment, built on the host while the transcripts are being hashed.
-// Plain C++ (no HIP): host_shim.cpp replays the same maps on the CPU (tests/test_coset_groups_cpu.py).  DESIGN.md
-// section 3i.2.
+// Plain C++ (no HIP): host_shim.cpp replays the same maps on the CPU (tests/test_coset_groups_cpu.py,
+// tests/test_cell_groups_cpu.py).  DESIGN.md sections 3b and 3i.2.
 //
 // A chunk is G groups over N items; group g is the slice [start[g], start[g + 1]).  Three kinds of segment:
 //   pairs   the distinct (group, commitment) pairs, per group in order of first appearance -- the order in which
-//           coset_verify_digest wants the slice's commitments, so a pair's index inside its group is the commitment
-//           index the group's transcript hashes;
+//           coset_verify_digest wants the slice's commitments (the reference's deduplication, eip7594.c:345-376), so a
+//           pair's index inside its group is the commitment index the group's transcript hashes;
 //   rows    the distinct (group, coset) pairs: one aggregated column of l values each, at most N of them, the rows of a
 //           group back to back -- R l slots, over which the kernels map their lanes;
 //   jobs    two linear combinations per group, in the layout of group_jobs.hpp:
@@ -15,7 +16,6 @@
 //                     B_g = [its proofs]
 //           A_g's scalars are the weights, r^i x_c^l and the negated interpolation coefficients, B_g's are r^i.
 // Points are named by their index in the chunk's pool [N proofs | the chunk's distinct commitments | l setup points].
-// At e = 6 every map is cell_groups_plan.hpp's, entry for entry.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -135,8 +135,7 @@ inline void build_coset_groups_plan(CosetGroupsPlan &p, const uint64_t *start, s
 // k_coset_group_aggregate: one lane per (row slot, part) over the R l slots, COSET_AGG_SLOTS_PER_BLOCK slots a workgroup.
 // The parts rule is coset_verify_agg_parts' with the chunk's rows in the place of the m columns: a power of two that
 // grows while an average row would give a lane more than COSET_AGG_ITEMS_PER_LANE items, at most COSET_AGG_MAX_PARTS
-// (1024 threads, 32 KB of LDS).  At e = 6 these are the numbers of group_cell_aggregate_device (verify.hip); the switch
-// points are taken over from there, unmeasured for this call.
+// (1024 threads, 32 KB of LDS).  The switch points are those of the single check, unmeasured for this call.
 HD uint32_t coset_groups_agg_parts(uint64_t items, uint64_t rows) {
     uint32_t parts = 1;
     while (parts < COSET_AGG_MAX_PARTS && (uint64_t)parts * rows * COSET_AGG_ITEMS_PER_LANE < items) parts <<= 1;
@@ -154,9 +153,9 @@ HD uint64_t coset_groups_interp_blocks(uint64_t rows, int e) {
 // k_coset_group_interp_sum: one lane per (output, part) over the G l outputs, COSET_GROUPS_SUM_OUT_PER_BLOCK outputs a
 // workgroup; part p of an output adds every parts-th row of its group from the p-th on, and the parts are folded in
 // LDS.  parts is a power of two that grows while an average group would give a lane more than
-// COSET_GROUPS_SUM_ROWS_PER_LANE rows, at most COSET_GROUPS_SUM_MAX_PARTS: a lane of k_group_interp_sum (four parts
-// over at most 128 rows) adds at most 32 rows, and this rule keeps that for the average group at every e.  Switch
-// points set by this reasoning alone: unmeasured.
+// COSET_GROUPS_SUM_ROWS_PER_LANE rows, at most COSET_GROUPS_SUM_MAX_PARTS: a cell group has at most 128 rows, which
+// four parts bring to 32 a lane, and this rule keeps that for the average group at every e.  Switch points set by this
+// reasoning alone: unmeasured.
 constexpr uint32_t COSET_GROUPS_SUM_OUT_PER_BLOCK = 64;
 constexpr uint32_t COSET_GROUPS_SUM_ROWS_PER_LANE = 32;
 constexpr uint32_t COSET_GROUPS_SUM_MAX_PARTS = 16;

@@ -44,8 +44,7 @@ HD uint32_t coset_verify_twiddle_root(uint32_t pos, int s) {
 // Aggregation: one lane per slot and part.  A column with many items is split over `parts` lanes per slot, each taking
 // every parts-th item of the column's list, and the parts are folded in LDS.  parts is a power of two, grows while an
 // average column would give a lane more than COSET_AGG_ITEMS_PER_LANE items, and stops at COSET_AGG_MAX_PARTS (1024
-// threads, 32 KB of LDS).  At e = 6 these are the numbers of k_cell_aggregate
-// (verify.hip: the aggregation by groups).
+// threads, 32 KB of LDS).  The aggregation by groups (coset_groups_plan.hpp) takes the same numbers.
 constexpr uint32_t COSET_AGG_ITEMS_PER_LANE = 4;
 constexpr uint32_t COSET_AGG_MAX_PARTS = 16;
 constexpr uint32_t COSET_AGG_SLOTS_PER_BLOCK = 64;

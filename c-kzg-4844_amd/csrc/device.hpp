@@ -581,29 +581,17 @@ int coset_aggregate_device(DeviceCtx *ctx, Fr *d_agg, const Fr *d_item_fr, const
 //   d_agg[8192] <- each column's interpolation coefficients over the l-th roots of unity (in place); d_interp[l][8] <-
 //   their sum over the columns, each times x_c^-k, as canonical MSM scalars; d_partial: COSET_INTERP_BLOCKS * l scratch
 int coset_interp_device(DeviceCtx *ctx, uint32_t *d_interp, Fr *d_partial, Fr *d_agg, int e);
-// The same steps segmented by group (ckzg_hip_verify_cell_kzg_proof_batch_groups; index maps: cell_groups_plan.hpp over
-// the job layout of group_jobs.hpp, whose field names the parameters carry).  All enqueue-only, on ctx->stream.
-// d_sc: the scalars of every job ([total][8], zeroed by the caller), d_r: the groups' challenges (Montgomery).
-//   d_rp[n] <- r_g^(i - start_g); d_sc <- the same on each cell's proof in B_g, times h_k^64 in A_g, and the
-//   per-(group, commitment) weights on the pairs' terms
-int group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_cell_grp, const uint32_t *d_cell_col,
-                              const uint32_t *d_gd, const Fr *d_r, const uint32_t *d_pair_start, const uint32_t *d_pair_members,
-                              const uint32_t *d_pair_term, size_t n, size_t ngroups, size_t npairs);
-//   d_sc <- the per-(group, commitment) weights alone: the sum of d_rp over each pair's members, onto the pair's term
+// The same steps segmented by group at every coset size l = 2^e, e <= 6 (ckzg_hip_verify_coset_kzg_proof_batch_groups,
+// and the cell and blob-cell calls by groups at e = 6; index maps and launch pickers: coset_groups_plan.hpp over the job
+// layout of group_jobs.hpp, whose field names the parameters carry).  All enqueue-only, on ctx->stream.
+// d_sc: the scalars of every job ([total][8], zeroed by the caller), d_r: the groups' challenges (Montgomery).  A row is
+// a distinct (group, coset) pair of l values.  The two stages that do not depend on l are in verify.hip:
+//   d_sc <- the per-(group, commitment) weights: the sum of d_rp over each pair's members, onto the pair's term
 int group_commit_weights_enqueue(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rp, const uint32_t *d_pair_start,
                                  const uint32_t *d_pair_members, const uint32_t *d_pair_term, size_t npairs);
-//   rows[t][j] = sum over the cells i of row t (CSR: row_start[nrows + 1], row_order[n]) of rp[i] * cell_fr[i][j]
-int group_cell_aggregate_device(DeviceCtx *ctx, Fr *d_rows, const Fr *d_cell_fr, const Fr *d_rp, const uint32_t *d_row_start,
-                                const uint32_t *d_row_order, size_t n_cells, size_t nrows);
-//   d_sc <- minus the interpolation coefficients of each group, summed over its rows (after the rows' inverse NTTs)
-int group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, const uint32_t *d_grp_rows, const uint32_t *d_row_col,
-                            const uint32_t *d_gd, size_t ngroups);
 //   d_out[t] <- d_pool[term_src[t]], infinity for a padding term
 int group_gather_points_enqueue(DeviceCtx *ctx, G1Affine *d_out, const G1Affine *d_pool, const uint32_t *d_term_src, size_t total);
-// coset_groups.hip: the same steps segmented by group at every coset size l = 2^e, e <= 6
-// (ckzg_hip_verify_coset_kzg_proof_batch_groups; index maps and launch pickers: coset_groups_plan.hpp, whose field names
-// the parameters carry).  All enqueue-only, on ctx->stream; d_sc and d_r as above.  A row is a distinct (group, coset)
-// pair of l values; the jobs' points are gathered by group_gather_points_enqueue.
+// ... and the others in coset_groups.hip:
 //   d_rp[n] <- r_g^(i - start_g); d_sc <- the same on each item's proof in B_g, times x_c^l of its coset in A_g, and the
 //   per-(group, commitment) weights on the pairs' terms
 int coset_group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_item_grp, const uint32_t *d_item_col,

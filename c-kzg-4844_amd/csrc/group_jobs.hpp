@@ -1,4 +1,4 @@
-// The job layout the grouped verifications share (cell_groups_plan.hpp, blob_groups_plan.hpp): two linear
+// The job layout the grouped verifications share (coset_groups_plan.hpp, blob_groups_plan.hpp): two linear
 // combinations per group, A_g then B_g, laid out job after job for ONE pass of the ladder kernels
 // (lincomb_multi_device).  Every job is padded to a whole partial of those kernels -- 8 terms while all jobs together
 // stay within quad_max_terms (the four-lane ladders), 32 otherwise -- and the whole layout to a multiple of 64 terms.

@@ -579,94 +579,8 @@ void hs_host_miller(Fp12 *r, const G1Jac *a1, const G2Jac *q1, const G1Jac *a2, 
 }
 }
 
-// ---- ckzg_hip_verify_cell_kzg_proof_batch_groups: the segmented scalar, aggregation and interpolation arithmetic of
-// verify.hip (k_group_rlc_scalars, k_group_commit_weights, k_cell_aggregate over rows, the rows' inverse NTTs,
-// k_group_interp_sum) replayed element by element over the index maps the product builds (cell_groups_plan.hpp), so
-// that the maps can be checked without a GPU (tests/test_cell_groups_cpu.py).  Field elements cross as canonical
-// little-endian limbs: cells [N][64], r [G], roots w^i [8193].  Out: the plan's sizes in info (total, quad, pairs,
-// rows), term_src [total], part_off [2 G + 1] and the jobs' scalars sc [total][8].  Returns the number of terms, or
-// -1 if it exceeds cap_terms. ----
-#include "cell_groups_plan.hpp"
-extern "C" long hs_cell_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_t *part_off, uint32_t *info, size_t cap_terms,
-                                      const uint64_t *start, size_t G, const uint32_t *cell_commit, size_t num_commits,
-                                      const uint64_t *cell_indices, const uint32_t *cells_raw, const uint32_t *r_raw,
-                                      const uint32_t *roots_raw, size_t quad_max_terms) {
-    CellGroupsPlan p;
-    build_cell_groups_plan(p, start, G, cell_commit, num_commits, cell_indices, quad_max_terms);
-    if (p.total > cap_terms) return -1;
-    const size_t N = p.N;
-    info[0] = (uint32_t)p.total;
-    info[1] = p.quad ? 1 : 0;
-    info[2] = (uint32_t)p.P;
-    info[3] = (uint32_t)p.R;
-    for (size_t t = 0; t < p.total; t++) term_src[t] = p.term_src[t];
-    for (size_t j = 0; j <= 2 * G; j++) part_off[j] = p.part_off[j];
-    for (size_t t = 0; t < p.total * 8; t++) sc[t] = 0;
-    auto fr_at = [](const uint32_t *raw, size_t i) { return from_raw<FrParams>(raw + i * 8); };
-    auto brp7 = [](uint32_t c) {
-        uint32_t o = 0;
-        for (int b = 0; b < 7; b++) o |= ((c >> b) & 1u) << (6 - b);
-        return o;
-    };
-    const uint32_t *gd = p.gd.data();
-    // k_group_rlc_scalars
-    std::vector<Fr> rp(N);
-    for (size_t i = 0; i < N; i++) {
-        const uint32_t g = p.cell_grp[i], off = (uint32_t)i - gd[g];
-        Fr base = fr_at(r_raw, g), pw = Fr::one();
-        for (uint32_t e = off; e; e >>= 1) {
-            if (e & 1u) pw = mul(pw, base);
-            base = mul(base, base);
-        }
-        rp[i] = pw;
-        const size_t ta = (size_t)gd[G + 1 + g] + gd[2 * G + 1 + g] + off, tb = (size_t)gd[3 * G + 1 + g] + off;
-        to_raw<FrParams>(sc + ta * 8, mul(pw, fr_at(roots_raw, (size_t)brp7(p.cell_col[i]) * 64)));
-        to_raw<FrParams>(sc + tb * 8, pw);
-    }
-    // k_group_commit_weights
-    for (size_t j = 0; j < p.P; j++) {
-        Fr acc = Fr::zero();
-        for (uint32_t m = p.pair_start[j]; m < p.pair_start[j + 1]; m++) acc = add(acc, rp[p.pair_members[m]]);
-        to_raw<FrParams>(sc + (size_t)p.pair_term[j] * 8, acc);
-    }
-    // k_cell_aggregate over the rows, then each row's inverse NTT: the data is in bit-reversed order
-    std::vector<Fr> rows(p.R * 64);
-    const Fr inv64 = fr_inv(from_raw<FrParams>((const uint32_t[8]){64, 0, 0, 0, 0, 0, 0, 0}));
-    for (size_t t = 0; t < p.R; t++) {
-        Fr agg[64], nat[64];
-        for (uint32_t j = 0; j < 64; j++) {
-            Fr acc = Fr::zero();
-            for (uint32_t m = p.row_start[t]; m < p.row_start[t + 1]; m++) {
-                const uint32_t i = p.row_order[m];
-                acc = add(acc, mul(fr_at(cells_raw, (size_t)i * 64 + j), rp[i]));
-            }
-            agg[j] = acc;
-        }
-        for (uint32_t m = 0; m < 64; m++) nat[m] = agg[brp7(m) >> 1];   // 6-bit reversal
-        for (uint32_t k = 0; k < 64; k++) {
-            Fr acc = Fr::zero();
-            for (uint32_t m = 0; m < 64; m++) acc = add(acc, mul(nat[m], fr_at(roots_raw, (8192u - 128u * ((m * k) & 63u)) & 8191u)));
-            rows[t * 64 + k] = mul(acc, inv64);
-        }
-    }
-    // k_group_interp_sum
-    for (size_t g = 0; g < G; g++) {
-        const uint32_t n = gd[g + 1] - gd[g];
-        if (!n) continue;
-        for (uint32_t k = 0; k < 64; k++) {
-            Fr acc = Fr::zero();
-            for (uint32_t t = p.grp_rows[g]; t < p.grp_rows[g + 1]; t++) {
-                const uint32_t idx = ((8192u - brp7(p.row_col[t])) * k) & 8191u;
-                acc = add(acc, mul(rows[(size_t)t * 64 + k], fr_at(roots_raw, idx)));
-            }
-            to_raw<FrParams>(sc + ((size_t)gd[G + 1 + g] + gd[2 * G + 1 + g] + n + k) * 8, neg(acc));
-        }
-    }
-    return (long)p.total;
-}
-
-// ---- ckzg_hip_verify_coset_kzg_proof_batch_groups: hs_cell_groups_replay with the coset size 2^e a parameter -- the
-// kernels of coset_groups.hip (k_coset_group_rlc_scalars, k_group_commit_weights, k_coset_group_aggregate,
+// ---- The cell check by groups at coset size 2^e (ckzg_hip_verify_coset_kzg_proof_batch_groups; the cell call by groups
+// at e = 6: hs_cell_groups_replay below) -- the kernels of coset_groups.hip (k_coset_group_rlc_scalars, k_group_commit_weights, k_coset_group_aggregate,
 // k_coset_group_interp with its butterfly stages, k_coset_group_interp_sum) replayed slot by slot over the index maps
 // the product builds (coset_groups_plan.hpp), so that the maps can be checked without a GPU
 // (tests/test_coset_groups_cpu.py).  Field elements cross as canonical little-endian limbs: evals [N][l], r [G], roots
@@ -751,6 +665,19 @@ extern "C" long hs_coset_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_
         }
     }
     return (long)p.total;
+}
+
+// ckzg_hip_verify_cell_kzg_proof_batch_groups: the same at e = 6 -- cells [N][64], info = (total, quad, pairs, rows)
+// (tests/test_cell_groups_cpu.py)
+extern "C" long hs_cell_groups_replay(uint32_t *sc, uint32_t *term_src, uint32_t *part_off, uint32_t *info, size_t cap_terms,
+                                      const uint64_t *start, size_t G, const uint32_t *cell_commit, size_t num_commits,
+                                      const uint64_t *cell_indices, const uint32_t *cells_raw, const uint32_t *r_raw,
+                                      const uint32_t *roots_raw, size_t quad_max_terms) {
+    uint32_t info6[6];
+    const long total = hs_coset_groups_replay(sc, term_src, part_off, info6, cap_terms, start, G, cell_commit, num_commits,
+                                              cell_indices, cells_raw, r_raw, roots_raw, 6, quad_max_terms);
+    if (total >= 0) memcpy(info, info6, 4 * sizeof(uint32_t));
+    return total;
 }
 
 // ---- ckzg_hip_verify_blob_kzg_proof_batch_groups: the segmented scalar arithmetic of verify.hip

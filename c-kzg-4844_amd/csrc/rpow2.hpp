@@ -1,5 +1,6 @@
 // rpow2.hpp -- the powers of a batch challenge, made where they are used: only r crosses PCIe (verify.hip:
-// k_rlc_scalars, k_group_rlc_scalars; coset_verify.hip: k_coset_rlc_scalars; locate.hip: k_locate_scale).
+// k_rlc_scalars; coset_verify.hip: k_coset_rlc_scalars; coset_groups.hip: k_coset_group_rlc_scalars; locate.hip:
+// k_locate_scale).
 #pragma once
 #include "field.hpp"
 

@@ -787,32 +787,6 @@ __global__ void k_scatter_cells(uint4 *image, const uint4 *cells, const uint32_t
     image[(b * 128 + idx[j]) * U4 + w] = cells[g];
 }
 
-// agg[c][j] = sum over the cells i of row c of r^i * cell_i[j]  (eip7594.c:661-683), a row being a (group, column)
-// pair of a chunk of groups (group_cell_aggregate_device; the single check aggregates in k_coset_aggregate).
-// order[col_start[c] .. col_start[c+1]) lists the cells of column c.  One workgroup per column, thread (j, p): position
-// j over every parts-th cell of the list, then a fold over the parts in LDS (a large batch has 64+ cells per column:
-// that many dependent multiply-adds per thread in the one-part form).
-__global__ void k_cell_aggregate(Fr *agg, const Fr *cell_fr, const Fr *rp, const uint32_t *col_start,
-                                 const uint32_t *order, uint32_t parts) {
-    extern __shared__ Fr sh_agg[];   // [parts][64]
-    const uint32_t c = blockIdx.x, j = threadIdx.x & 63u, p = threadIdx.x >> 6;
-    Fr acc = Fr::zero();
-    for (uint32_t t = col_start[c] + p; t < col_start[c + 1]; t += parts) {
-        const uint32_t i = order[t];
-        acc = add(acc, mul(vld_fr(cell_fr + (size_t)i * 64 + j), vld_fr(rp + i)));
-    }
-    if (parts > 1) {
-        sh_agg[p * 64 + j] = acc;
-        __syncthreads();
-        for (uint32_t s2 = parts >> 1; s2 >= 1; s2 >>= 1) {
-            if (p < s2) sh_agg[p * 64 + j] = add(sh_agg[p * 64 + j], sh_agg[(p + s2) * 64 + j]);
-            __syncthreads();
-        }
-        acc = sh_agg[j];
-    }
-    if (p == 0) vst_fr(agg + c * 64 + j, acc);
-}
-
 int scatter_cells_device(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *d_cells, const uint32_t *d_idx,
                          uint32_t num_cells, size_t num_rows) {
     const size_t u4 = num_rows * num_cells * (2048 / 16);
@@ -824,38 +798,10 @@ int scatter_cells_device(DeviceCtx *ctx, uint8_t *d_image, const uint8_t *d_cell
 }
 
 // ------------------------------------------------------------------------------------------
-// cell verification by groups (ckzg_hip_verify_cell_kzg_proof_batch_groups): the stages of the single
-// check (coset_verify.hip, at cosets of 64) once per chunk, segmented by group.  The index maps are the host's (cell_groups_plan.hpp); gd is its group table
-// start[G + 1] | first term of A_g [G] | distinct commitments of g [G] | first term of B_g [G], and sc the scalar
-// vector of all jobs (canonical limbs, 8 words per term, zero where a term is padding).
+// cell / coset verification by groups: the two stages that do not depend on the coset size (the others:
+// coset_groups.hip).  The index maps are the host's (coset_groups_plan.hpp), and sc the scalar vector of all jobs
+// (canonical limbs, 8 words per term, zero where a term is padding).
 // ------------------------------------------------------------------------------------------
-
-// Cell i of group g gets r_g^(i - start_g) by square-and-multiply from its offset (<= 2 log2 of the group's size
-// products, no lane waits for another): in Montgomery form for the aggregation, in canonical limbs on the cell's proof
-// in B_g, and times the coset factor h_k^64 of its column on the same proof in A_g (eip7594.c:784-812).
-__global__ void k_group_rlc_scalars(Fr *rp, uint32_t *sc, const uint32_t *cell_grp, const uint32_t *cell_col, const uint32_t *gd,
-                                    const Fr *r, const Fr *roots, uint32_t n, uint32_t ngroups) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t g = cell_grp[i], off = i - gd[g];
-    Fr base = vld_fr(r + g), pw = Fr::one();
-#pragma unroll 1
-    for (uint32_t e = off; e; e >>= 1) {
-        if (e & 1u) pw = mul(pw, base);
-        base = mul(base, base);
-    }
-    vst_fr(rp + i, pw);
-    const uint32_t rb = __brev(cell_col[i]) >> 25;   // 7-bit reversal of the column index (128 columns)
-    uint32_t a[8], c[8];
-    to_raw<FrParams>(a, pw);
-    to_raw<FrParams>(c, mul(pw, vld_fr(roots + (size_t)rb * N_CELL)));
-    const size_t ta = (size_t)gd[ngroups + 1 + g] + gd[2 * ngroups + 1 + g] + off, tb = (size_t)gd[3 * ngroups + 1 + g] + off;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        sc[ta * 8 + k] = c[k];
-        sc[tb * 8 + k] = a[k];
-    }
-}
 
 // Weight of each (group, commitment) pair (eip7594.c:494-539 on the group's slice): the sum of r_g^i over the
 // group's cells that name the commitment, onto the pair's term in A_g.  One 64-lane workgroup per pair.
@@ -880,35 +826,6 @@ __global__ __launch_bounds__(64) void k_group_commit_weights(uint32_t *sc, const
     }
 }
 
-// -interp_g[k] = -sum over the rows of group g of row[k] * (h_c^-1)^k, c the row's column (the fold of
-// k_coset_interp_fold with a row -> column map and the group's rows instead of the 128 columns), in canonical limbs onto the k-th setup
-// point of A_g: the interpolation commitment is subtracted by its scalars, not by a negated point table.  One
-// workgroup per group, thread (k, p): coefficient k over every fourth row, then a fold over the four parts.
-__global__ __launch_bounds__(256) void k_group_interp_sum(uint32_t *sc, const Fr *rows, const uint32_t *grp_rows,
-                                                         const uint32_t *row_col, const uint32_t *gd, const Fr *roots,
-                                                         uint32_t ngroups) {
-    __shared__ Fr sh[256];
-    const uint32_t g = blockIdx.x, k = threadIdx.x & 63u, p = threadIdx.x >> 6;
-    Fr acc = Fr::zero();
-    for (uint32_t t = grp_rows[g] + p; t < grp_rows[g + 1]; t += 4) {
-        const uint32_t rb = __brev(row_col[t]) >> 25;
-        const uint32_t idx = ((8192u - rb) * k) & 8191u;
-        acc = add(acc, mul(vld_fr(rows + (size_t)t * 64 + k), vld_fr(roots + idx)));
-    }
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    if (p < 2) sh[threadIdx.x] = add(sh[threadIdx.x], sh[threadIdx.x + 128]);
-    __syncthreads();
-    const uint32_t n = gd[g + 1] - gd[g];
-    if (p == 0 && n != 0) {
-        uint32_t raw[8];
-        to_raw<FrParams>(raw, neg(add(sh[k], sh[k + 64])));
-        const size_t t = (size_t)gd[ngroups + 1 + g] + gd[2 * ngroups + 1 + g] + n + k;
-#pragma unroll
-        for (int w = 0; w < 8; w++) sc[t * 8 + w] = raw[w];
-    }
-}
-
 // The points of every job, job after job as k_lincomb_partial* want them, gathered by index from the chunk's pool
 // (proofs, distinct commitments, setup points); a padding term is the point at infinity (0, 0).  One lane per 16 bytes.
 __global__ void k_group_gather_points(uint4 *out, const uint4 *pool, const uint32_t *term_src, size_t total_u4) {
@@ -925,39 +842,6 @@ int group_commit_weights_enqueue(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rp,
     if (!npairs) return 0;
     hipLaunchKernelGGL(k_group_commit_weights, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, d_sc, d_rp, d_pair_start,
                        d_pair_members, d_pair_term);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int group_rlc_scalars_enqueue(DeviceCtx *ctx, Fr *d_rp, uint32_t *d_sc, const uint32_t *d_cell_grp, const uint32_t *d_cell_col,
-                              const uint32_t *d_gd, const Fr *d_r, const uint32_t *d_pair_start, const uint32_t *d_pair_members,
-                              const uint32_t *d_pair_term, size_t n, size_t ngroups, size_t npairs) {
-    if (!n) return 0;
-    if (n >= ((size_t)1 << 31)) return 2;
-    hipLaunchKernelGGL(k_group_rlc_scalars, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_rp, d_sc, d_cell_grp,
-                       d_cell_col, d_gd, d_r, ctx->d_roots, (uint32_t)n, (uint32_t)ngroups);
-    HIP_TRY(hipGetLastError());
-    return group_commit_weights_enqueue(ctx, d_sc, d_rp, d_pair_start, d_pair_members, d_pair_term, npairs);
-}
-
-// k_cell_aggregate over the rows of a chunk (one workgroup per distinct (group, column) pair instead of per column)
-int group_cell_aggregate_device(DeviceCtx *ctx, Fr *d_rows, const Fr *d_cell_fr, const Fr *d_rp, const uint32_t *d_row_start,
-                                const uint32_t *d_row_order, size_t n_cells, size_t nrows) {
-    if (!nrows) return 0;
-    // parts: a power of two, ~4 cells per thread at the average row, at most 16 (1024 threads, 32 KB of LDS)
-    uint32_t parts = 1;
-    while (parts < 16 && (size_t)parts * nrows * 4 < n_cells) parts <<= 1;
-    hipLaunchKernelGGL(k_cell_aggregate, dim3((unsigned)nrows), dim3(64 * parts), parts > 1 ? parts * 64 * sizeof(Fr) : 0,
-                       ctx->stream, d_rows, d_cell_fr, d_rp, d_row_start, d_row_order, parts);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int group_interp_sum_device(DeviceCtx *ctx, uint32_t *d_sc, const Fr *d_rows, const uint32_t *d_grp_rows, const uint32_t *d_row_col,
-                            const uint32_t *d_gd, size_t ngroups) {
-    if (!ngroups) return 0;
-    hipLaunchKernelGGL(k_group_interp_sum, dim3((unsigned)ngroups), dim3(256), 0, ctx->stream, d_sc, d_rows, d_grp_rows, d_row_col,
-                       d_gd, ctx->d_roots, (uint32_t)ngroups);
     HIP_TRY(hipGetLastError());
     return 0;
 }

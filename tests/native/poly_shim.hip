@@ -1,9 +1,9 @@
 // poly_shim.hip -- the stages that move and combine vectors of Fr, behind a C ABI (tests/test_gpu_poly_stages.py):
 //   ntt.hip     fr_ntt_batch, bytes_to_fr_batch, fr_to_bytes_batch, zero_extend_batch
 //   verify.hip  eval_blob_bytes_batch_device (k_eval_tree), eval_quotient_batch_device (k_eval_barycentric<true>,
-//               k_quotient_in_domain), group_cell_aggregate_device (k_cell_aggregate),
-//               group_interp_sum_device, fr_mul_inplace_device, fr_div_inplace_device,
-//               scatter_cells_device
+//               k_quotient_in_domain), fr_mul_inplace_device, fr_div_inplace_device, scatter_cells_device
+//   coset_groups.hip  coset_group_aggregate_device, coset_group_interp_device, coset_group_interp_sum_device at cosets
+//               of 64: the aggregation and interpolation of a chunk of cell groups
 //   coset_recover.hip  coset_recover_factors_enqueue, fr_mul_coset_factor_enqueue, scatter_cosets_rows_enqueue at cosets
 //               of 64: the factors, the multiplication and the scatter of recovery by rows, in the cell call's terms
 //   coset_verify.hip  coset_aggregate_device, coset_interp_device at cosets of 64: the aggregation and interpolation of a
@@ -84,6 +84,21 @@ int stage_ctx(DeviceCtx &ctx, hipStream_t st, const std::vector<Arg> &args, size
     ctx.d_shift = (Fr *)args[at + 2].dev;
     ctx.d_brp_roots29 = (uint32_t *)args[at + 3].dev;
     return roots29_build(&ctx, ctx.d_brp_roots29);
+}
+
+// rows of 64 coefficients -> each row's values over the 64th roots of unity, in bit-reversed order, on the host:
+// value j = sum_k coeffs[k] w_64^(brp_6(j) k), w_64 = w^128
+std::vector<Fr> values_of_coeffs64(const Tables &tb, const std::vector<Fr> &coeffs) {
+    std::vector<Fr> values(coeffs.size());
+    for (size_t c = 0; c < coeffs.size() / 64; c++) {
+        for (uint32_t j = 0; j < 64; j++) {
+            const uint32_t t = brp13(j) >> 7;   // brp_6(j)
+            Fr acc = Fr::zero();
+            for (uint32_t k = 0; k < 64; k++) acc = add(acc, mul(coeffs[c * 64 + k], tb.roots[(128 * t * k) & (N_EXT - 1)]));
+            values[c * 64 + j] = acc;
+        }
+    }
+    return values;
 }
 
 bool csr_ok(const uint32_t *start, size_t nrows, const uint32_t *order, size_t n) {
@@ -335,7 +350,7 @@ int ps_scatter_cells_rows(uint8_t *image, size_t image_rows, const uint8_t *cell
 
 // rows [nrows + 1][64][8] go up as the caller filled them; cell_fr [n][64][8]; rp [n][8]; row_start [nrows + 1]; order [n].
 // grouped = 0: the aggregation of a single cell batch, coset_aggregate_device at cosets of 64 (nrows must be 128: its
-// columns), else group_cell_aggregate_device
+// columns), else that of a chunk of groups, coset_group_aggregate_device at cosets of 64
 int ps_cell_aggregate(uint32_t *rows, const uint32_t *cell_fr, const uint32_t *rp, const uint32_t *row_start, const uint32_t *order,
                       size_t n, size_t nrows, int grouped, int *rc) {
     if (!n || n * 64 > PS_MAX_ELEMS || !nrows || nrows > 4096 || (!grouped && nrows != 128)) return DS_BAD_ARG;
@@ -351,8 +366,8 @@ int ps_cell_aggregate(uint32_t *rows, const uint32_t *cell_fr, const uint32_t *r
         DeviceCtx ctx;
         ctx.stream = st;
         if (grouped)
-            *rc = group_cell_aggregate_device(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const Fr *)args[2].dev,
-                                              (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, n, nrows);
+            *rc = coset_group_aggregate_device(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const Fr *)args[2].dev,
+                                               (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, n, nrows, CELL_LOG);
         else
             *rc = coset_aggregate_device(&ctx, (Fr *)args[0].dev, (const Fr *)args[1].dev, (const Fr *)args[2].dev,
                                          (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, n, CELL_LOG);
@@ -365,20 +380,11 @@ int ps_cell_aggregate(uint32_t *rows, const uint32_t *cell_fr, const uint32_t *r
 // interp [128][8] (canonical, as the stage writes them: 64 values and a guard of 64) goes up as the caller filled it;
 // cols [128][64][8]: the coefficients of each column's interpolation polynomial.  The stage of a single cell batch,
 // coset_interp_device at cosets of 64, takes a column's VALUES (bit-reversed order) and makes the coefficients itself,
-// so the shim evaluates each column first, on the host: value j = sum_k cols[c][k] w_64^(brp_6(j) k), w_64 = w^128.
+// so the shim evaluates each column first, on the host (values_of_coeffs64).
 // (The stage on values, with its coefficients and partial rows read back: coset_verify_shim.hip.)
 int ps_interp_sum(uint32_t *interp, const uint32_t *cols, const uint32_t *roots, int *rc) {
     const Tables tb(roots);
-    const std::vector<Fr> cv = fr_in(cols, 128 * 64);
-    std::vector<Fr> values(128 * 64);
-    for (uint32_t c = 0; c < 128; c++) {
-        for (uint32_t j = 0; j < 64; j++) {
-            const uint32_t t = brp13(j) >> 7;   // brp_6(j)
-            Fr acc = Fr::zero();
-            for (uint32_t k = 0; k < 64; k++) acc = add(acc, mul(cv[c * 64 + k], tb.roots[(128 * t * k) & (N_EXT - 1)]));
-            values[c * 64 + j] = acc;
-        }
-    }
+    const std::vector<Fr> values = values_of_coeffs64(tb, fr_in(cols, 128 * 64));
     std::vector<Arg> args = {{interp, interp, 128 * 32, nullptr},
                              {values.data(), nullptr, values.size() * 32, nullptr},
                              {nullptr, nullptr, (size_t)COSET_INTERP_BLOCKS * 64 * sizeof(Fr), nullptr}};
@@ -390,8 +396,12 @@ int ps_interp_sum(uint32_t *interp, const uint32_t *cols, const uint32_t *roots,
     });
 }
 
-// sc [total][8] (canonical) goes up as the caller filled it; rows [nrows][64][8]; grp_rows [G + 1]; row_col [nrows];
-// gd [4 G + 1]: start [G + 1] | first term of A_g [G] | distinct commitments of g [G] | first term of B_g [G]
+// sc [total][8] (canonical) goes up as the caller filled it; rows [nrows][64][8]: the coefficients of each row's
+// interpolation polynomial; grp_rows [G + 1]; row_col [nrows];
+// gd [4 G + 1]: start [G + 1] | first term of A_g [G] | distinct commitments of g [G] | first term of B_g [G].
+// The stages of a chunk of groups, coset_group_interp_device and coset_group_interp_sum_device at cosets of 64: the first
+// takes a row's VALUES and makes the coefficients itself, so the shim evaluates each row first, as ps_interp_sum does.
+// (The stages on values, each with its whole buffer read back: coset_groups_shim.hip.)
 int ps_group_interp_sum(uint32_t *sc, size_t total, const uint32_t *rows, size_t nrows, const uint32_t *grp_rows,
                         const uint32_t *row_col, const uint32_t *gd, size_t G, const uint32_t *roots, int *rc) {
     if (!G || G > 64 || !nrows || nrows > 4096 || !total || total > PS_MAX_ELEMS) return DS_BAD_ARG;
@@ -404,9 +414,9 @@ int ps_group_interp_sum(uint32_t *sc, size_t total, const uint32_t *rows, size_t
     for (size_t t = 0; t < nrows; t++)
         if (row_col[t] >= 128) return DS_BAD_ARG;
     const Tables tb(roots);
-    const std::vector<Fr> rv = fr_in(rows, nrows * 64);
+    const std::vector<Fr> rv = fr_in(rows, nrows * 64), values = values_of_coeffs64(tb, rv);
     std::vector<Arg> args = {{sc, sc, total * 32, nullptr},
-                             {rv.data(), nullptr, rv.size() * 32, nullptr},
+                             {values.data(), nullptr, values.size() * 32, nullptr},
                              {grp_rows, nullptr, (G + 1) * 4, nullptr},
                              {row_col, nullptr, nrows * 4, nullptr},
                              {gd, nullptr, (4 * G + 1) * 4, nullptr}};
@@ -414,9 +424,10 @@ int ps_group_interp_sum(uint32_t *sc, size_t total, const uint32_t *rows, size_t
     return run_bounded(args, [&](hipStream_t st) {
         DeviceCtx ctx;
         *rc = stage_ctx(ctx, st, args, at);
+        if (*rc == 0) *rc = coset_group_interp_device(&ctx, (Fr *)args[1].dev, (const uint32_t *)args[3].dev, nrows, CELL_LOG);
         if (*rc == 0)
-            *rc = group_interp_sum_device(&ctx, (uint32_t *)args[0].dev, (const Fr *)args[1].dev, (const uint32_t *)args[2].dev,
-                                          (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, G);
+            *rc = coset_group_interp_sum_device(&ctx, (uint32_t *)args[0].dev, (const Fr *)args[1].dev, (const uint32_t *)args[2].dev,
+                                                (const uint32_t *)args[4].dev, nrows, G, CELL_LOG);
     });
 }
 

@@ -1,6 +1,6 @@
 // stage_shim.hip -- the stages that turn a batch challenge into scalars, and the items into the bytes that are hashed,
 // behind a C ABI (tests/test_gpu_rlc_stages.py): rlc_scalars_enqueue, coset_rlc_scalars_enqueue at
-// cosets of 64 (the scalars of a cell batch), group_rlc_scalars_enqueue, blob_group_scalars_enqueue, locate_scale_enqueue, batch_transcript_rows_device and
+// cosets of 64 (the scalars of a cell batch), coset_group_rlc_scalars_enqueue at cosets of 64, blob_group_scalars_enqueue, locate_scale_enqueue, batch_transcript_rows_device and
 // rpow2.hpp's rpow_at.  A weight of a batch check is the one value no verdict can check -- any consistent weights pass an
 // honest batch and fail a spoilt one -- so these values are read here and compared with integers.
 //
@@ -19,7 +19,7 @@
 #include "device.hpp"
 #include "rpow2.hpp"
 #include "blob_groups_plan.hpp"
-#include "cell_groups_plan.hpp"
+#include "coset_groups_plan.hpp"
 
 using namespace ckzg;
 using namespace ckzg::dev;
@@ -129,7 +129,9 @@ int ss_cell_rlc_scalars(uint32_t *rp, uint32_t *vec_rp, uint32_t *vec_wrp, uint3
     return 0;
 }
 
-// The index maps are the product's (build_cell_groups_plan).  Out, as hs_cell_groups_replay gives them: info = total,
+// The scalars of a chunk of cell groups: coset_group_rlc_scalars_enqueue at cosets of 64 (the stage at every coset size,
+// with guards around its buffers: coset_groups_shim.hip).  The index maps are the product's (build_coset_groups_plan at
+// e = 6).  Out, as hs_cell_groups_replay gives them: info = total,
 // quad, pairs, rows; term_src [total]; part_off [2 G + 1]; sc [total][8] -- here with the terms of the interpolation
 // commitment left as the caller of the stage zeroed them -- and rp [N][8] (canonical).  r: the groups' challenges.
 // DS_BAD_ARG if the layout exceeds cap_terms.
@@ -143,8 +145,8 @@ int ss_cell_groups_scalars(uint32_t *sc, uint32_t *rp, uint32_t *term_src, uint3
     if (!N || N > SS_MAX_ITEMS) return DS_BAD_ARG;
     for (size_t i = 0; i < N; i++)
         if (cell_commit[i] >= num_commits) return DS_BAD_ARG;
-    CellGroupsPlan p;
-    build_cell_groups_plan(p, start, G, cell_commit, num_commits, cell_indices, quad_max_terms);
+    CosetGroupsPlan p;
+    build_coset_groups_plan(p, start, G, cell_commit, num_commits, cell_indices, CELL_LOG, quad_max_terms);
     if (p.total > cap_terms) return DS_BAD_ARG;
     info[0] = (uint32_t)p.total;
     info[1] = p.quad ? 1 : 0;
@@ -156,8 +158,8 @@ int ss_cell_groups_scalars(uint32_t *sc, uint32_t *rp, uint32_t *term_src, uint3
     std::vector<Fr> rpf(N);
     std::vector<Arg> args = {{nullptr, rpf.data(), N * 32},
                              {nullptr, sc, p.total * 32},
-                             {p.cell_grp.data(), nullptr, N * 4},
-                             {p.cell_col.data(), nullptr, N * 4},
+                             {p.item_grp.data(), nullptr, N * 4},
+                             {p.item_col.data(), nullptr, N * 4},
                              {p.gd.data(), nullptr, p.gd.size() * 4},
                              {rf.data(), nullptr, G * 32},
                              {p.pair_start.data(), nullptr, p.pair_start.size() * 4},
@@ -168,10 +170,10 @@ int ss_cell_groups_scalars(uint32_t *sc, uint32_t *rp, uint32_t *term_src, uint3
     const int run = run_bounded(args, [&](hipStream_t st) {
         DeviceCtx ctx;
         stage_ctx(ctx, st, (Fr *)args[9].dev);
-        rc = group_rlc_scalars_enqueue(&ctx, (Fr *)args[0].dev, (uint32_t *)args[1].dev, (const uint32_t *)args[2].dev,
-                                       (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, (const Fr *)args[5].dev,
-                                       (const uint32_t *)args[6].dev, (const uint32_t *)args[7].dev,
-                                       (const uint32_t *)args[8].dev, N, G, p.P);
+        rc = coset_group_rlc_scalars_enqueue(&ctx, (Fr *)args[0].dev, (uint32_t *)args[1].dev, (const uint32_t *)args[2].dev,
+                                             (const uint32_t *)args[3].dev, (const uint32_t *)args[4].dev, (const Fr *)args[5].dev,
+                                             (const uint32_t *)args[6].dev, (const uint32_t *)args[7].dev,
+                                             (const uint32_t *)args[8].dev, N, G, p.P, CELL_LOG);
     });
     if (run || rc) return run ? run : rc;
     fr_out(rp, rpf);

@@ -1,6 +1,6 @@
 """What the scalar vectors of the batch checks must hold, as Python integers: the weights r^i of a random linear
 combination and the products and sums made from them, laid out term by term the way csrc/group_jobs.hpp,
-csrc/blob_groups_plan.hpp and csrc/cell_groups_plan.hpp document it.  Nothing here reads the library under test.
+csrc/blob_groups_plan.hpp and csrc/coset_groups_plan.hpp (at cosets of 64) document it.  Nothing here reads the library under test.
 Shared by tests/test_gpu_rlc_stages.py (the device stages) and the CPU replay tests (tests/test_blob_groups_cpu.py,
 tests/test_cell_groups_cpu.py)."""
 import random

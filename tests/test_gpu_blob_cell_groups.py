@@ -219,6 +219,21 @@ def test_duplicate_commitment_in_a_group(hip, material):
     _check(hip.verify_blob_cell_kzg_proof_batch_groups([g]), [False])
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("bad", [0, 1, 2, 3])
+def test_a_non_canonical_blob_marks_its_own_group_only(hip, oracle, material, bad):
+    """groups of 1, 2 and 1 blobs in one chunk; blob `bad` of the chunk -- the first one, either one of the middle group,
+    the last one -- holds the modulus as a field element.  The flag is one word per blob, the half that folds the flags
+    takes one per 2^bad_shift cells: only the group of that blob is C_KZG_BADARGS, the two others verify."""
+    groups = [_group(material, w) for w in ([0], [1, 2], [3])]
+    g, i = [(0, 0), (1, 0), (1, 1), (2, 0)][bad]
+    groups[g][0][i] = _set_element(groups[g][0][i], 17, R)
+    exp = [True] * 3
+    exp[g] = None
+    assert _oracle_composition(oracle, groups[g], {m[0]: m[2] for m in material}) is None   # (compute_cells rejects the blob)
+    _check(hip.verify_blob_cell_kzg_proof_batch_groups(groups), exp)
+
+
 def _raw_call(api, groups, with_status=True, start=None, null_data=False):
     g = len(groups)
     flat = [b"".join(x for grp in groups for x in grp[k]) for k in range(3)]

@@ -182,6 +182,37 @@ def test_every_group_equals_the_single_call_on_its_slice_and_the_oracle(hip, ora
     assert kinds == {(True, 0), (False, 0), (False, BADARGS)}
 
 
+def _groups_with_rows(material, rows):
+    """groups of 1, 2, 3, 1, ... cells, every cell of a group in a column of its own, so that the chunk has exactly `rows`
+    distinct (group, column) pairs; an empty group last, so that one row is still a chunk of two groups"""
+    cm, cells, proofs = material
+    groups, at = [], 0
+    while at < rows:
+        n = min(len(groups) % 3 + 1, rows - at)
+        ids = [((5 * i) % 8, (37 * i) % 128) for i in range(at, at + n)]
+        groups.append([[cm[b] for b, _ in ids], [c for _, c in ids], [cells[b][c] for b, c in ids], [proofs[b][c] for b, c in ids]])
+        at += n
+    return groups + [[[], [], [], []]]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows", [1, 3, 4, 5, 63, 64, 65])
+def test_row_counts_around_a_workgroup_and_a_tile_of_rows(hip, oracle, material, rows):
+    """The rows of a chunk lie back to back, unpadded: k_coset_group_interp takes 4 rows of 64 values a workgroup, and 64
+    rows were the tile the rows were once padded to.  One forged cell in the last group that has cells."""
+    groups = _groups_with_rows(material, rows)
+    assert sum(len(set(g[1])) for g in groups) == rows and len(groups) >= 2 and all(len(g[2]) <= 3 for g in groups)
+    forged = len(groups) - 2
+    cell = bytearray(groups[forged][2][0])
+    cell[32 * 17 + 31] ^= 1          # the lowest bit of a field element: still canonical
+    assert int.from_bytes(cell[32 * 17:32 * 18], "big") < R
+    groups[forged][2][0] = bytes(cell)
+    ok, st = hip.verify_cell_kzg_proof_batch_groups(groups)
+    for g, grp in enumerate(groups):
+        want = [(api.verify_cell_kzg_proof_batch(*grp), 0) for api in (oracle, hip)]
+        assert want[0] == want[1] == (ok[g], st[g]) == (g != forged, 0), (rows, g, want, ok[g], st[g])
+
+
 def _raw_call(api, groups, with_status=True, start=None):
     g = len(groups)
     flat = [[x for grp in groups for x in grp[k]] for k in range(4)]
@@ -321,7 +352,8 @@ def test_concurrent_callers(hip, material):
         _check(results[t], sets[t][1])
 
 
-NEW_KERNELS = ("k_group_rlc_scalars", "k_group_commit_weights", "k_group_interp_sum", "k_group_gather_points")
+NEW_KERNELS = ("k_coset_group_rlc_scalars", "k_group_commit_weights", "k_coset_group_aggregate", "k_coset_group_interp",
+               "k_coset_group_interp_sum", "k_group_gather_points")
 
 
 def test_group_kernels_use_no_scratch():

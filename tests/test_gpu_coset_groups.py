@@ -132,6 +132,25 @@ def test_size_64_is_the_oracle_and_the_cell_groups_call(hip, oracle, mat):
 
 
 @pytest.mark.gpu
+def test_index_128_marks_its_own_group_at_the_cell_entry_and_at_the_coset_entry(hip, oracle, mat):
+    """one pipeline behind both entries at e = 6, each with a range check of its own: three groups in one chunk, the
+    middle one with index 128"""
+    e, m = 6, _m(6)
+    assert m == 128
+    groups = [[mat.item(b, e, c) for c in (0, 5) for b in (0, 1)], [mat.item(0, e, 9), mat.item(1, e, 9), mat.item(0, e, 127)],
+              [mat.item(1, e, 127)]]
+    assert [oracle.verify_cell_kzg_proof_batch(*_lists(g)) for g in groups] == [True, True, True]
+    _check(_groups_call(hip, groups, e), [True, True, True])
+    groups[1][1] = _with(groups[1][1], c=m)
+    exp = [True, None, True]
+    with pytest.raises(KzgError):
+        oracle.verify_cell_kzg_proof_batch(*_lists(groups[1]))
+    assert call(hip, groups[1], e) == (BADARGS, False)
+    _check(hip.verify_cell_kzg_proof_batch_groups([_lists(g) for g in groups]), exp)
+    _check(_groups_call(hip, groups, e), exp)
+
+
+@pytest.mark.gpu
 def test_size_one_is_verify_kzg_proof(hip, mat):
     groups, exp = _mixed_groups(mat, 0, 100)
     valid = [(g, x) for g, x in zip(groups, exp) if x is not None]

@@ -11,8 +11,9 @@ kernels are the product's binary code) runs each stage on chosen inputs and retu
     eval_quotient_batch_device                        k_eval_barycentric<true>, k_quotient_in_domain
     fr_div_inplace_device, fr_mul_inplace_device      k_fr_div_inplace (zero divisors), k_fr_mul_inplace
     coset_recover_factors_enqueue, fr_mul_coset_factor_enqueue, scatter_cosets_rows_enqueue at cosets of 64; scatter_cells_device
-    coset_aggregate_device at cosets of 64, group_cell_aggregate_device     parts = 1 .. 16
-    coset_interp_device at cosets of 64 (on the values of given coefficients), group_interp_sum_device
+    coset_aggregate_device, coset_group_aggregate_device at cosets of 64    parts = 1 .. 16
+    coset_interp_device, coset_group_interp_device + coset_group_interp_sum_device at cosets of 64 (on the values of
+    given coefficients)
 
 Every comparison is exact and over the whole buffer, a guard region behind the data included: Python integers
 (tests/poly_expect.py, each reference checked by a second route in tests/test_poly_expect_cpu.py) and bytes.
@@ -509,7 +510,7 @@ GROUP_ROWS = [0, 1, 5, 130]
 
 
 def test_group_cell_aggregate(shim):
-    """k_cell_aggregate with one workgroup per (group, column) row: 136 rows of 0 .. 9 cells, parts = 2"""
+    """k_coset_group_aggregate at cosets of 64 over (group, column) rows: 136 rows of 0 .. 9 cells, parts = 2"""
     rnd = random.Random(7300)
     nrows = sum(GROUP_ROWS)
     sizes = [(7 * t + 3) % 10 for t in range(nrows)]
@@ -523,7 +524,7 @@ def test_group_cell_aggregate(shim):
 
 
 def test_group_interp_sum(shim, roots, roots_raw):
-    """the index arrays by hand, to the layout verify.hip documents: gd = start [G + 1] | first term of A_g [G] | distinct
+    """the index arrays by hand, to the layout coset_groups.hip documents: gd = start [G + 1] | first term of A_g [G] | distinct
     commitments of g [G] | first term of B_g [G]; A_g = commitments | proofs | 64 setup points.  The 64 setup terms of
     each non-empty group become -interp_g[k]; nothing else of sc changes, and the empty group writes nothing"""
     rnd = random.Random(7400)

@@ -8,7 +8,7 @@ stage on chosen inputs and returns its whole output buffer:
     rpow_at (rpow2.hpp)                               every table entry: indices 2^k - 1, 2^k, 2^k + 1, k < 24
     rlc_scalars_enqueue                               k_rlc_scalars
     coset_rlc_scalars_enqueue at cosets of 64         k_coset_rlc_scalars, k_coset_commit_weights (a cell batch's)
-    group_rlc_scalars_enqueue                         k_group_rlc_scalars, k_group_commit_weights
+    coset_group_rlc_scalars_enqueue at cosets of 64   k_coset_group_rlc_scalars, k_group_commit_weights (cell groups')
     blob_group_scalars_enqueue                        k_blob_group_scalars, k_blob_group_ysum
     locate_scale_enqueue                              k_locate_scale
     batch_transcript_rows_device                      k_batch_transcript_rows

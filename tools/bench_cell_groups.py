@@ -3,6 +3,7 @@ of getting per-group verdicts from verify_cell_kzg_proof_batch, at the C-ABI, on
 with the default tables.  The PeerDAS shape: group c = column c of every blob of a block.
 
     python tools/bench_cell_groups.py [--out FILE] [--reps 20] [--shapes 128x64,8x64,128x8] [--lib OTHER_BUILD.so]
+                                      [--ab-lib PARENT_BUILD.so]
 
 Per shape (groups x cells per group) the variants are alternated in one process, `--reps` timed repetitions of each
 after a warm-up round; median and min in milliseconds:
@@ -13,7 +14,10 @@ after a warm-up round; median and min in milliseconds:
 128 x 64 gets all four, every other shape (a) and (b).  Then one traced call of (a) per shape (CKZG_HIP_TRACE: the
 call waits after every stage, so the marks are the stages' own times, and their sum is more than an untraced call).
 --lib times (b) and (d) only, on another build of the library (the parent commit's: both variants go through code this
-call does not touch, so the two builds should agree).  Prints one JSON object and writes it to FILE."""
+call does not touch, so the two builds should agree).  --ab-lib adds the variant groups_ab: (a) in another build of the
+library (the parent commit's), loaded into the same process and alternated with the others (block medians of both builds
+with the parent's own spread as the margin: tools/bench_groups_merge_ab.py).  Prints one JSON object and writes it to
+FILE."""
 import argparse
 import ctypes as C
 import hashlib
@@ -47,9 +51,15 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--shapes", default="128x64,8x64,128x8")
     ap.add_argument("--lib", default="")
+    ap.add_argument("--ab-lib", default="")
     a = ap.parse_args()
     mod = ge.load_package()
     hip = mod.Kzg(os.path.abspath(a.lib) if a.lib else mod.HIP_SO)
+    ab = mod.Kzg(os.path.abspath(a.ab_lib)) if a.ab_lib else None
+    groups_ab = None
+    if ab:
+        groups_ab = ab.lib.ckzg_hip_verify_cell_kzg_proof_batch_groups
+        groups_ab.restype = C.c_int
     mat = []
     for i in range(8):
         blob = b"".join(b"\x00" + hashlib.sha256(b"bench%d/%d" % (i, j)).digest()[:31] for j in range(4096))
@@ -81,8 +91,8 @@ def main():
         start = (C.c_uint64 * (G + 1))(*[rows * g for g in range(G + 1)])
         ok_g, st_g = (C.c_bool * G)(), (C.c_uint8 * G)()
 
-        def v_groups():
-            rc = groups_fn(ok_g, st_g, flat[0], flat[1], flat[2], flat[3], start, C.c_uint64(G), hip.sp)
+        def v_groups(f=groups_fn, api=hip):
+            rc = f(ok_g, st_g, flat[0], flat[1], flat[2], flat[3], start, C.c_uint64(G), api.sp)
             assert rc == 0 and all(ok_g), (rc, list(ok_g))
 
         def one(g, okb):
@@ -126,6 +136,8 @@ def main():
         variants = []
         if groups_fn:
             variants.append(("groups", v_groups))
+        if groups_ab:
+            variants.append(("groups_ab", lambda: v_groups(groups_ab, ab)))
         variants.append(("loop", v_loop))
         if full and groups_fn:
             variants.append(("threads16", v_threads))
@@ -166,6 +178,8 @@ def main():
     if a.out:
         with open(a.out, "w") as fh:
             json.dump(result, fh, indent=1)
+    if ab:
+        ab.close()
     hip.close()
 
 
