@@ -39,7 +39,9 @@ constexpr int N_CELLS_EXT = 128;   // CELLS_PER_EXT_BLOB
 // from the environment instead, once per process, so that tools/ab_*.sh can sweep one constant on one box; the
 // measured sweeps that chose the defaults are under profiles/.  No losing variant lives in the product.
 #ifdef CKZG_AB
-inline long ab_knob(const char *env, long dflt) {
+// (internal linkage: libckzg_hip_ab.so links an msm.o compiled with -DCKZG_AB to the product's other objects, which
+// hold the constexpr form under the same name)
+static inline long ab_knob(const char *env, long dflt) {
     const char *e = getenv(env);
     return e && *e ? atol(e) : dflt;
 }

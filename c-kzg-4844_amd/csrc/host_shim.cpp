@@ -1356,3 +1356,95 @@ extern "C" long hs_coset_repair_plan(uint8_t *verdict, uint8_t *coset_ok, uint64
         for (uint64_t i = 0; i < total; i++) coset_ok[i] = cok[i] ? 1 : 0;
     return 0;
 }
+
+// ---- Fp on 13 signed 30-bit limbs (fp30.hpp) and the accumulate loop's mixed addition on it (g1_30.hpp) ----
+#include "g1_30.hpp"
+namespace {
+template <int V>
+F30<1, V> f30_load(const int32_t *a) {
+    F30<1, V> r;
+    for (int j = 0; j < 13; j++) r.l[j] = a[j];
+    return r;
+}
+template <int L, int V>
+void f30_store(int32_t *r, const F30<L, V> &a) {
+    for (int j = 0; j < 13; j++) r[j] = a.l[j];
+}
+Fp table_words(const Fp &v) {   // a table coordinate as msm.hip gathers it: 2^392 domain, fully reduced, packed
+    Fp k;
+    for (int i = 0; i < 12; i++) k.l[i] = FP_MONT_2POW8[i];
+    return mul(v, k);
+}
+}  // namespace
+extern "C" {
+// limbs in, limbs out, at the widest value bounds the static_asserts admit (17 * 18, 17^2, 17 * 17 + 5 * 5)
+void hs_fp30_mul(int32_t *r, const int32_t *a, const int32_t *b) { f30_store(r, mul(f30_load<17>(a), f30_load<18>(b))); }
+void hs_fp30_sqr(int32_t *r, const int32_t *a) { f30_store(r, sqr(f30_load<17>(a))); }
+void hs_fp30_mul_add2(int32_t *r, const int32_t *a, const int32_t *b, const int32_t *c, const int32_t *d) {
+    f30_store(r, mul_add2(f30_load<17>(a), f30_load<17>(b), f30_load<5>(c), f30_load<5>(d)));
+}
+// limbs of up to 3 * 2^29 in magnitude
+void hs_fp30_norm(int32_t *r, const int32_t *a) {
+    F30<3, 200> x;
+    for (int j = 0; j < 13; j++) x.l[j] = a[j];
+    f30_store(r, norm(x));
+}
+void hs_fp30_add(int32_t *r, const int32_t *a, const int32_t *b) { f30_store(r, add(f30_load<1>(a), f30_load<1>(b))); }
+void hs_fp30_sub(int32_t *r, const int32_t *a, const int32_t *b) { f30_store(r, sub(f30_load<1>(a), f30_load<1>(b))); }
+void hs_fp30_unpack(int32_t *r, const uint32_t *w) { f30_store(r, f30_unpack(w)); }
+void hs_fp30_to_f28(uint32_t *r, const int32_t *a) {
+    auto o = f30_to_f28(f30_load<1>(a));
+    for (int j = 0; j < 14; j++) r[j] = o.l[j];
+}
+void hs_fp30_consts(int32_t *p, uint32_t *ninv, int32_t *r392, int32_t *r394, int32_t *beta390) {
+    for (int j = 0; j < 13; j++) p[j] = F30_P[j], r392[j] = F30_R392[j], r394[j] = F30_R394[j], beta390[j] = F30_BETA390[j];
+    *ninv = F30_NINV;
+}
+// One lane's chain of the accumulate loop: entries pts[i] (skipped where at_inf[i]), negated where signs[i], phi applied
+// before entry phi_at (phi_at >= n: at the end).  form 0: the 28-bit law (xyzz28_madd_alt), the reference of the two
+// others.  form 1: the 30-bit law through entry and exit, as it stands.  form 2: what msm_sum_pairs30's caller does --
+// the 30-bit law, and the 28-bit one again if the exit finds ZZ = 0.  Returns the exit's equal-x verdict (form 0: 0).
+int hs_g1_madd_alt_chain_form(G1Jac *r, const G1Affine *pts, const uint8_t *signs, const uint8_t *at_inf, int n, int phi_at,
+                              int form) {
+    auto run28 = [&](XYZZ28 &acc, bool &inf, bool &yneg) {
+        inf = true, yneg = false;
+        bool phi_pending = true;
+        for (int i = 0; i < n; i++) {
+            if (phi_pending && i >= phi_at) {
+                if (!inf) acc.x = widen<1, 10>(mul(acc.x, f28_const<1, 1>(FP28_BETA_LAMBDA)));
+                phi_pending = false;
+            }
+            if (at_inf[i]) continue;
+            xyzz28_madd_alt(acc, inf, yneg, table_coord(pts[i].x), table_coord(pts[i].y), signs[i] != 0);
+        }
+        if (phi_pending && !inf) acc.x = widen<1, 10>(mul(acc.x, f28_const<1, 1>(FP28_BETA_LAMBDA)));
+    };
+    XYZZ28 acc28;
+    bool inf = true, yneg = false;
+    int met = 0;
+    if (form == 0) {
+        run28(acc28, inf, yneg);
+    } else {
+        XYZZ30 acc;
+        bool phi_pending = true;
+        for (int i = 0; i < n; i++) {
+            if (phi_pending && i >= phi_at) {
+                if (!inf) xyzz30_apply_phi(acc);
+                phi_pending = false;
+            }
+            if (at_inf[i]) continue;
+            Fp x = table_words(pts[i].x), y = table_words(pts[i].y);
+            xyzz30_madd_alt(acc, inf, yneg, f30_unpack(x.l), f30_unpack(y.l), signs[i] != 0);
+        }
+        if (phi_pending && !inf) xyzz30_apply_phi(acc);
+        if (!inf) {
+            acc28 = xyzz30_to_xyzz28(acc);
+            met = xyzz30_met_equal_x(acc28) ? 1 : 0;
+        }
+        if (met && form == 2) run28(acc28, inf, yneg);
+    }
+    xyzz28_fix_sign(acc28, inf, yneg);
+    *r = jac_from_xyzz(xyzz28_to_xyzz(acc28, inf));
+    return met;
+}
+}

@@ -21,6 +21,7 @@
 #include "device.hpp"
 #include "dev_inline.hpp"
 #include "g1_28.hpp"
+#include "g1_30.hpp"
 #include "g1_quad.hpp"
 
 namespace ckzg {
@@ -464,6 +465,16 @@ __global__ void k_raw_digits(int16_t *digits, const uint32_t *scalars, size_t to
 __device__ __forceinline__ void msm_apply_phi(XYZZ28 &acc28) {
     acc28.x = widen<1, 10>(mul(acc28.x, f28_const<1, 1>(FP28_BETA_LAMBDA)));
 }
+__device__ __forceinline__ void msm_apply_phi(XYZZ30 &acc30) { xyzz30_apply_phi(acc30); }
+
+// acc += +-(the table entry in wd[0..24): x then y, 12 packed words each, 2^392 domain, fully reduced): the 28-bit law,
+// and the throughput loop's 30-bit one (g1_30.hpp), which unpacks the same words straight into balanced 30-bit limbs
+__device__ __forceinline__ void msm_madd_entry(XYZZ28 &acc, bool &inf, bool &yneg, const uint32_t *wd, bool dneg) {
+    xyzz28_madd_alt(acc, inf, yneg, f28_unpack<1>(wd), f28_unpack<1>(wd + 12), dneg);
+}
+__device__ __forceinline__ void msm_madd_entry(XYZZ30 &acc, bool &inf, bool &yneg, const uint32_t *wd, bool dneg) {
+    xyzz30_madd_alt(acc, inf, yneg, f30_unpack(wd), f30_unpack(wd + 12), dneg);
+}
 
 // Alternating priority slices between the two waves of a SIMD.
 // What the per-wave trace of round 3 showed (tools/msm_trace.py, profiles/r03_msm_trace_*.json): of two resident
@@ -501,8 +512,9 @@ __device__ __forceinline__ void msm_fair_prio(uint32_t prio_bit, uint32_t parity
 // compiler's s_waitcnt vmcnt(0) lands (tools/isa_waits.py) -- a first version that loaded e[] in a prologue got the
 // wait in FRONT of the addition, because vmcnt counts in order, and measured slower than no prefetch at all.
 // Same-box A/B on the headline kernel: 9.76 -> 9.50 ms per 1024 blobs (profiles/r02_fp28_ab.txt).
-template <int STRIDE>
-__device__ __forceinline__ void msm_sum_pairs(XYZZ28 &acc28, bool &inf, bool &yneg, const G1Affine *table,
+// ACC is XYZZ28, or XYZZ30 through msm_sum_pairs30 below: one walk, one pipeline, two addition laws.
+template <int STRIDE, class ACC>
+__device__ __forceinline__ void msm_sum_pairs(ACC &acc28, bool &inf, bool &yneg, const G1Affine *table,
                                               const int16_t *dg, uint32_t first, uint32_t q1, uint32_t phi_pairs,
                                               uint32_t twin, uint32_t ppv, uint32_t npoints, uint32_t voff,
                                               int half_shift, uint32_t prio_bit = 0) {
@@ -541,7 +553,7 @@ __device__ __forceinline__ void msm_sum_pairs(XYZZ28 &acc28, bool &inf, bool &yn
                 any |= e[k].x | e[k].y | e[k].z | e[k].w;
             }
             // (0,0) encodes a table entry at infinity
-            if (any != 0) xyzz28_madd_alt(acc28, inf, yneg, f28_unpack<1>(wd), f28_unpack<1>(wd + 12), d < 0);
+            if (any != 0) msm_madd_entry(acc28, inf, yneg, wd, d < 0);
         }
 #pragma unroll
         for (int k = 0; k < 6; k++) e[k] = nx[k];
@@ -549,6 +561,17 @@ __device__ __forceinline__ void msm_sum_pairs(XYZZ28 &acc28, bool &inf, bool &yn
         d1 = d2;
     }
     if (phi_pending && !inf) msm_apply_phi(acc28);
+}
+
+// The throughput accumulate loop: the same walk on 13 signed 30-bit limbs (fp30.hpp: 3055 multiply-adds per addition
+// instead of 3542).  The 30-bit law has no branch for an entry with the accumulator's x; the caller tests ZZ at exit
+// (g1_30.hpp) and reruns the workgroup's pairs through msm_sum_pairs on XYZZ28 when a lane met one.
+template <int STRIDE>
+__device__ __forceinline__ void msm_sum_pairs30(XYZZ30 &acc30, bool &inf, bool &yneg, const G1Affine *table,
+                                                const int16_t *dg, uint32_t first, uint32_t q1, uint32_t phi_pairs,
+                                                uint32_t twin, uint32_t ppv, uint32_t npoints, uint32_t voff,
+                                                int half_shift, uint32_t prio_bit) {
+    msm_sum_pairs<STRIDE>(acc30, inf, yneg, table, dg, first, q1, phi_pairs, twin, ppv, npoints, voff, half_shift, prio_bit);
 }
 
 #ifdef CKZG_MSM_TRACE
@@ -598,10 +621,40 @@ __global__ __launch_bounds__(THREADS) void k_msm_accumulate(
     // accumulator in the 28-bit-limb / 2^392 domain (fp28.hpp), infinity tracked by a flag
     XYZZ28 acc28;
     bool inf = true, yneg = false;  // yneg: acc28.y currently holds -Y (xyzz28_madd_alt)
+#ifdef CKZG_AB
+    // A/B build: bit 31 of prio_bit (CKZG_HIP_MSM_LOOP28=1, msm_prio_bit) sends the throughput form down the 28-bit loop
+    const bool loop28 = (prio_bit >> 31) != 0;
+    prio_bit &= 0x7fffffffu;
+#endif
     // (Measured alternatives: unrolling by two -- 14.4 ms, two copies of the ~40 KB addition body thrash the
     // instruction cache; capping VGPRs for 3 or 4 waves per SIMD -- 11.4 / 13.2 ms.)
-    msm_sum_pairs<THREADS>(acc28, inf, yneg, table, dg, q0 + threadIdx.x, q1, phi_pairs, twin, ppv, npoints, voff,
-                           half_shift, prio_bit);
+    if constexpr (RAW) {
+        msm_sum_pairs<THREADS>(acc28, inf, yneg, table, dg, q0 + threadIdx.x, q1, phi_pairs, twin, ppv, npoints, voff,
+                               half_shift, prio_bit);
+    } else {
+        // throughput form: the additions on 30-bit limbs, back to XYZZ28 for the sign fix and the fold.  A lane whose
+        // chain met an entry with its accumulator's x (the same point or its negative) leaves ZZ = 0; then the whole
+        // workgroup -- the branch is uniform -- sums its pairs again with the 28-bit law, which doubles and cancels.
+        bool redo = false;
+#ifdef CKZG_AB
+        redo = loop28;
+        if (!loop28)
+#endif
+        {
+            XYZZ30 acc30;
+            msm_sum_pairs30<THREADS>(acc30, inf, yneg, table, dg, q0 + threadIdx.x, q1, phi_pairs, twin, ppv, npoints,
+                                     voff, half_shift, prio_bit);
+            if (!inf) {
+                acc28 = xyzz30_to_xyzz28(acc30);
+                redo = xyzz30_met_equal_x(acc28);
+            }
+        }
+        if (__syncthreads_or(redo ? 1 : 0)) {
+            inf = true, yneg = false;
+            msm_sum_pairs<THREADS>(acc28, inf, yneg, table, dg, q0 + threadIdx.x, q1, phi_pairs, twin, ppv, npoints,
+                                   voff, half_shift, prio_bit);
+        }
+    }
     if (prio_bit) __builtin_amdgcn_s_setprio(0);
     xyzz28_fix_sign(acc28, inf, yneg);
     quad::block_reduce_xyzz28_quad<THREADS>(acc28, inf, sh);   // four lanes per pair: the fold is ~3x shorter
@@ -895,7 +948,10 @@ static size_t partials_bytes(size_t nvec, uint32_t bpv) {
 // 2^9..2^13 ticks no change, 2^15 9.72-9.75 ms, 2^17 9.68 ms, 2^19 10.07 ms -> 2^16 ticks = 0.66 ms per slice.
 // (k_msm_small showed no gain at any slice width and keeps the scheme off.)
 static uint32_t msm_prio_bit() {
-    static const uint32_t v = (uint32_t)ab_knob("CKZG_HIP_MSM_PRIO_BIT", 16);
+    // (A/B build only: CKZG_HIP_MSM_LOOP28=1 sets bit 31, which k_msm_accumulate<256, false> reads as "take the 28-bit
+    // loop" -- the loop of before fp30.hpp, for same-box comparisons and tests/test_gpu_msm30.py)
+    static const uint32_t v = (uint32_t)ab_knob("CKZG_HIP_MSM_PRIO_BIT", 16) |
+                              (ab_knob("CKZG_HIP_MSM_LOOP28", 0) ? 0x80000000u : 0u);
     return v;
 }
 static uint32_t small_prio_bit() {

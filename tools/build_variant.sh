@@ -3,6 +3,8 @@
 #   bash tools/build_variant.sh ab -DCKZG_AB      ->  c-kzg-4844_amd/libckzg_hip_ab.so: the tuning constants of the
 #                                                     product (device.hpp: ab_knob) are read from CKZG_HIP_* variables
 #   bash tools/build_variant.sh trace -DCKZG_MSM_TRACE   per-wave trace of k_msm_accumulate (tools/msm_trace.py)
+#   (libckzg_hip_ab.so with ONLY msm.hip compiled that way is part of `make all`; CKZG_HIP_MSM_LOOP28=1 makes it take
+#   the 28-bit accumulate loop)
 # then   CKZG_HIP_SO=c-kzg-4844_amd/libckzg_hip_ab.so CKZG_HIP_SMALL_LPV=8 python tools/row_driver.py cells wide ...
 # The product itself reads no tuning variable (tools/ab_*.sh, tools/bench_lincomb.sh, tools/bench_fk20_sizes.py need
 # the ab build).
