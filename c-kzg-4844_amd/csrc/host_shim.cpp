@@ -1358,7 +1358,7 @@ extern "C" long hs_coset_repair_plan(uint8_t *verdict, uint8_t *coset_ok, uint64
 }
 
 // ---- Fp on 13 signed 30-bit limbs (fp30.hpp) and the accumulate loop's mixed addition on it (g1_30.hpp) ----
-#include "g1_30.hpp"
+#include "f30_test_ops.hpp"
 namespace {
 template <int V>
 F30<1, V> f30_load(const int32_t *a) {
@@ -1399,6 +1399,26 @@ void hs_fp30_to_f28(uint32_t *r, const int32_t *a) {
 void hs_fp30_consts(int32_t *p, uint32_t *ninv, int32_t *r392, int32_t *r394, int32_t *beta390) {
     for (int j = 0; j < 13; j++) p[j] = F30_P[j], r392[j] = F30_R392[j], r394[j] = F30_R394[j], beta390[j] = F30_BETA390[j];
     *ninv = F30_NINV;
+}
+// f30_test_ops.hpp as g++ builds it: operation `op` of the list on n items (13 int32 per operand, 14 words per result)
+const char *hs_f30_ops() { return f30test::desc(); }
+int hs_f30_run(int op, int32_t *out, const int32_t *a, const int32_t *b, const int32_t *c, const int32_t *d, int n) {
+    for (int i = 0; i < n; i++)
+        if (!f30test::run(op, out + 14 * i, a + 13 * i, b + 13 * i, c + 13 * i, d + 13 * i)) return 1;
+    return 0;
+}
+// the addition on raw state (f30_test_ops.hpp): per item 52 int32 of state, flags (inf, yneg, dneg) in and (inf, yneg) out,
+// a 24-word table entry
+void hs_madd30_step(int32_t *out, uint8_t *oflags, const int32_t *state, const uint8_t *flags, const uint32_t *entry, int n) {
+    for (int i = 0; i < n; i++)
+        f30test::madd_step(out + f30test::STATE_WORDS * i, oflags + 2 * i, state + f30test::STATE_WORDS * i, flags + 3 * i,
+                           entry + f30test::ENTRY_WORDS * i);
+}
+void hs_phi30(int32_t *out, const int32_t *state, int n) {
+    for (int i = 0; i < n; i++) f30test::phi_step(out + f30test::STATE_WORDS * i, state + f30test::STATE_WORDS * i);
+}
+void hs_exit30(uint32_t *out, uint8_t *met, const int32_t *state, int n) {
+    for (int i = 0; i < n; i++) f30test::exit_step(out + f30test::EXIT_WORDS * i, met + i, state + f30test::STATE_WORDS * i);
 }
 // One lane's chain of the accumulate loop: entries pts[i] (skipped where at_inf[i]), negated where signs[i], phi applied
 // before entry phi_at (phi_at >= n: at the end).  form 0: the 28-bit law (xyzz28_madd_alt), the reference of the two

@@ -1,7 +1,9 @@
 // dev_shim.hip -- the device-only arithmetic behind a C ABI, the counterpart of csrc/host_shim.cpp for what g++
 // never sees: the F28 product as the DEVICE compiler builds it, its inline-asm form (CKZG_F28_ASM_BLOCKS), all of
 // g1_quad.hpp (the DPP-quad group law), the straight-line routines of g1_pipe.hpp (xyzz28_addsub_quad,
-// jac28_add_quad_pipe, naf2_128, naf_masks), f28_inv_safegcd, and g1.hpp's complete xyzz_add / xyzz_dbl on 32-bit limbs.
+// jac28_add_quad_pipe, naf2_128, naf_masks), f28_inv_safegcd, g1.hpp's complete xyzz_add / xyzz_dbl on 32-bit limbs, and
+// the accumulate loop's own arithmetic: Fp on 13 signed 30-bit limbs (fp30.hpp, in the asm build its generated products)
+// and the mixed addition on it (g1_30.hpp), through f30_test_ops.hpp (tests/test_gpu_fp30.py).
 // The fields under the Fr kernels and the pairing are in dev_shim_fields.hip (one plain build, ds_dev_*).  Test aid only
 // (tests/test_gpu_dev_arith.py); never part of libckzg_hip.so.
 //
@@ -13,7 +15,8 @@
 // back, frees and returns the HIP error code (0 = ok).  Kernels hold bounded loops only; the LDS-spinning
 // pipeline waves of g1_pipe.hpp (pipe_doubler / pipe_adder / pipe_wait) are deliberately not here.
 //
-// Conventions.  Field: 14 uint32 limbs per operand in and out, taken as they come (f28_test_ops.hpp).  Points:
+// Conventions.  Field: 14 uint32 limbs per operand in and out, taken as they come (f28_test_ops.hpp); the 30-bit field:
+// 13 int32 limbs per operand, 14 words per result, an accumulator as 52 int32 and two flag bytes (f30_test_ops.hpp).  Points:
 // G1Jac (144 bytes, 2^384 domain, Z = 0 for infinity) in and out; an affine point travels as a G1Jac with Z = 1.
 // Conversion to XYZZ28 / JAC28 / JACT28 happens in the kernel with the helpers the product kernels use.
 // Geometry.  `block` threads per workgroup (a multiple of 64, at most 256).  The point kernels give every item a DPP quad (four
@@ -23,6 +26,7 @@
 // verify.hip k_subgroup_g1_quad).  One-lane routines run in all four lanes of the quad on the same input.
 #include "dev_shim_common.hpp"
 #include "f28_test_ops.hpp"
+#include "f30_test_ops.hpp"
 #include "g1_pipe.hpp"
 #include "dev_inline.hpp"
 
@@ -40,6 +44,11 @@ __device__ __forceinline__ F28<1, 1> table_coord(const Fp &v) {   // the stored 
     for (int i = 0; i < 12; i++) k8.l[i] = FP_MONT_2POW8[i];
     const Fp t = mul(v, k8);
     return f28_unpack<1>(t.l);
+}
+__device__ __forceinline__ Fp table_words(const Fp &v) {   // the same coordinate as the kernel gathers it: 12 packed words
+    Fp k8;
+    for (int i = 0; i < 12; i++) k8.l[i] = FP_MONT_2POW8[i];
+    return mul(v, k8);
 }
 __device__ __forceinline__ XYZZ28 load_xyzz(const G1Jac &p, bool &inf) { return xyzz28_from_xyzz(xyzz_from_jac(p), inf); }
 __device__ __forceinline__ G1Jac store_xyzz(const XYZZ28 &v, bool inf) { return jac_from_xyzz(xyzz28_to_xyzz(v, inf)); }
@@ -239,6 +248,101 @@ __global__ __launch_bounds__(MAX_BLOCK) void DS(k_chain)(int kind, G1Jac *out, c
     out[c] = store_xyzz(acc, inf);
 }
 
+// ---- Fp on 13 signed 30-bit limbs (fp30.hpp; f30_test_ops.hpp): one thread per item, 13 int32 per operand, 14 words out ----
+__global__ __launch_bounds__(MAX_BLOCK) void DS(k_f30field)(int op, int32_t *out, const int32_t *a, const int32_t *b, const int32_t *c, const int32_t *d, int n) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    int32_t o[14];
+    if (!f30test::run(op, o, a + 13 * i, b + 13 * i, c + 13 * i, d + 13 * i)) return;
+    for (int j = 0; j < 14; j++) out[14 * i + j] = o[j];
+}
+
+// ---- the accumulate loop's mixed addition on raw state (g1_30.hpp; f30_test_ops.hpp), one thread per item.
+// kind: 0 xyzz30_madd_alt (flags in: inf, yneg, dneg; out: inf, yneg)  1 xyzz30_apply_phi
+// 2 xyzz30_to_xyzz28 + xyzz30_met_equal_x (56 words and the verdict in oflags) ----
+__global__ __launch_bounds__(MAX_BLOCK) void DS(k_step30)(int kind, int32_t *out, uint8_t *oflags, const int32_t *state, const uint8_t *flags, const uint32_t *entry, int n) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= (size_t)n) return;
+    const int32_t *s = state + f30test::STATE_WORDS * i;
+    if (kind == 0) {
+        int32_t o[f30test::STATE_WORDS];
+        uint8_t of[2];
+        uint8_t f[3] = {flags[3 * i], flags[3 * i + 1], flags[3 * i + 2]};
+        uint32_t e[f30test::ENTRY_WORDS];
+        for (int j = 0; j < f30test::ENTRY_WORDS; j++) e[j] = entry[f30test::ENTRY_WORDS * i + j];
+        f30test::madd_step(o, of, s, f, e);
+        for (int j = 0; j < f30test::STATE_WORDS; j++) out[f30test::STATE_WORDS * i + j] = o[j];
+        oflags[2 * i] = of[0];
+        oflags[2 * i + 1] = of[1];
+    } else if (kind == 1) {
+        int32_t o[f30test::STATE_WORDS];
+        f30test::phi_step(o, s);
+        for (int j = 0; j < f30test::STATE_WORDS; j++) out[f30test::STATE_WORDS * i + j] = o[j];
+    } else {
+        uint32_t o[f30test::EXIT_WORDS];
+        uint8_t met;
+        f30test::exit_step(o, &met, s);
+        for (int j = 0; j < f30test::EXIT_WORDS; j++) out[f30test::EXIT_WORDS * i + j] = (int32_t)o[j];
+        oflags[i] = met;
+    }
+}
+
+// ---- one lane's chain of the accumulate loop, one thread per chain (host_shim.cpp: hs_g1_madd_alt_chain_form has the
+// same semantics).  Chain c takes pts[start[c] .. start[c + 1]) (affine, Z = 1), skipped where at_inf, negated where
+// signs, phi applied before its entry phi_at[c] (at the end if the chain is shorter).  form 0: the 28-bit law;
+// 1: the 30-bit law through entry and exit; 2: the 30-bit law, and the 28-bit one again if the exit finds ZZ = 0.
+// met: the exit's equal-x verdict (form 0: 0). ----
+__device__ __forceinline__ void chain28(XYZZ28 &acc, bool &inf, bool &yneg, const G1Jac *pts, const uint8_t *signs, const uint8_t *at_inf, int len, uint32_t phi_at) {
+    inf = true, yneg = false;
+    bool phi_pending = true;
+    for (int i = 0; i < len; i++) {
+        if (phi_pending && (uint32_t)i >= phi_at) {
+            if (!inf) acc.x = widen<1, 10>(mul(acc.x, f28_const<1, 1>(FP28_BETA_LAMBDA)));
+            phi_pending = false;
+        }
+        if (at_inf[i]) continue;
+        const G1Jac pt = pts[i];
+        xyzz28_madd_alt(acc, inf, yneg, table_coord(pt.x), table_coord(pt.y), signs[i] != 0);
+    }
+    if (phi_pending && !inf) acc.x = widen<1, 10>(mul(acc.x, f28_const<1, 1>(FP28_BETA_LAMBDA)));
+}
+
+__global__ __launch_bounds__(MAX_BLOCK) void DS(k_chain30)(int form, G1Jac *out, uint8_t *met_out, const G1Jac *pts, const uint8_t *signs, const uint8_t *at_inf, const uint32_t *start, const uint32_t *phi_at, int n) {
+    const size_t c = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (c >= (size_t)n) return;
+    const uint32_t b = start[c];
+    const int len = (int)(start[c + 1] - b < (uint32_t)MAX_CHAIN ? start[c + 1] - b : (uint32_t)MAX_CHAIN);
+    const uint32_t phi = phi_at[c];
+    XYZZ28 acc28;
+    bool inf = true, yneg = false;
+    uint8_t met = 0;
+    if (form == 0) {
+        chain28(acc28, inf, yneg, pts + b, signs + b, at_inf + b, len, phi);
+    } else {
+        XYZZ30 acc;
+        bool phi_pending = true;
+        for (int i = 0; i < len; i++) {
+            if (phi_pending && (uint32_t)i >= phi) {
+                if (!inf) xyzz30_apply_phi(acc);
+                phi_pending = false;
+            }
+            if (at_inf[b + i]) continue;
+            const G1Jac pt = pts[b + i];
+            const Fp x = table_words(pt.x), y = table_words(pt.y);
+            xyzz30_madd_alt(acc, inf, yneg, f30_unpack(x.l), f30_unpack(y.l), signs[b + i] != 0);
+        }
+        if (phi_pending && !inf) xyzz30_apply_phi(acc);
+        if (!inf) {
+            acc28 = xyzz30_to_xyzz28(acc);
+            met = xyzz30_met_equal_x(acc28) ? 1 : 0;
+        }
+        if (met && form == 2) chain28(acc28, inf, yneg, pts + b, signs + b, at_inf + b, len, phi);
+    }
+    xyzz28_fix_sign(acc28, inf, yneg);
+    out[c] = store_xyzz(acc28, inf);
+    met_out[c] = met;
+}
+
 // ---- the co-Z table {P, 3P, 5P, 7P} and its phi images, mapped home (Z = Zc): out[(4 item + lane) * 16 + e],
 // e = 0..3 entries and 4..7 phi images from eat28_build_quad (coz28_addu_quad inside), 8..15 the same from
 // eat28_build.  Finite points of the prime-order subgroup only. ----
@@ -378,6 +482,66 @@ int DS(g1_chain)(int kind, G1Jac *out, const G1Jac *pts, const uint8_t *signs, c
     return run_bounded(args, [&](hipStream_t st) {
         hipLaunchKernelGGL(DS(k_chain), dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, st, kind, (G1Jac *)args[0].dev,
                            (const G1Jac *)args[1].dev, (const uint8_t *)args[2].dev, (const uint32_t *)args[3].dev, n);
+    });
+}
+
+// ---- Fp on 13 signed 30-bit limbs and the accumulate loop's addition on it (f30_test_ops.hpp) ----
+const char *DS(f30_ops)() { return f30test::desc(); }
+
+int DS(f30field)(int op, int32_t *out, const int32_t *a, const int32_t *b, const int32_t *c, const int32_t *d, int n, int block) {
+    if (!geometry_ok(n, block)) return DS_BAD_ARG;
+    const size_t in = (size_t)n * 13 * 4;
+    std::vector<Arg> args = {{nullptr, out, (size_t)n * 14 * 4}, {a, nullptr, in}, {b, nullptr, in}, {c, nullptr, in}, {d, nullptr, in}};
+    return run_bounded(args, [&](hipStream_t st) {
+        hipLaunchKernelGGL(DS(k_f30field), dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, st, op, (int32_t *)args[0].dev,
+                           (const int32_t *)args[1].dev, (const int32_t *)args[2].dev, (const int32_t *)args[3].dev,
+                           (const int32_t *)args[4].dev, n);
+    });
+}
+
+static int step30(int kind, void *out, size_t out_words, uint8_t *oflags, size_t oflag_bytes, const int32_t *state, const uint8_t *flags,
+                  const uint32_t *entry, int n, int block) {
+    if (!geometry_ok(n, block)) return DS_BAD_ARG;
+    std::vector<Arg> args = {{nullptr, out, (size_t)n * out_words * 4}, {nullptr, oflags, (size_t)n * oflag_bytes},
+                             {state, nullptr, (size_t)n * f30test::STATE_WORDS * 4}};
+    if (kind == 0) {
+        args.push_back({flags, nullptr, (size_t)n * 3});
+        args.push_back({entry, nullptr, (size_t)n * f30test::ENTRY_WORDS * 4});
+    }
+    return run_bounded(args, [&](hipStream_t st) {
+        hipLaunchKernelGGL(DS(k_step30), dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, st, kind, (int32_t *)args[0].dev,
+                           (uint8_t *)args[1].dev, (const int32_t *)args[2].dev, kind == 0 ? (const uint8_t *)args[3].dev : nullptr,
+                           kind == 0 ? (const uint32_t *)args[4].dev : nullptr, n);
+    });
+}
+
+// state: 52 int32 per item; flags: (inf, yneg, dneg) per item; entry: 24 words per item; oflags: (inf, yneg) per item
+int DS(madd30_step)(int32_t *out, uint8_t *oflags, const int32_t *state, const uint8_t *flags, const uint32_t *entry, int n, int block) {
+    return step30(0, out, f30test::STATE_WORDS, oflags, 2, state, flags, entry, n, block);
+}
+int DS(phi30)(int32_t *out, const int32_t *state, int n, int block) {
+    std::vector<uint8_t> unused((size_t)(n > 0 ? n : 1));
+    return step30(1, out, f30test::STATE_WORDS, unused.data(), 1, state, nullptr, nullptr, n, block);
+}
+// out: 56 words per item (x, y, zz, zzz of the XYZZ28); met: one byte per item
+int DS(exit30)(uint32_t *out, uint8_t *met, const int32_t *state, int n, int block) {
+    return step30(2, out, f30test::EXIT_WORDS, met, 1, state, nullptr, nullptr, n, block);
+}
+
+// start: n + 1 offsets into pts / signs / at_inf (total = start[n] entries); phi_at: one per chain
+int DS(g1_chain30)(int form, G1Jac *out, uint8_t *met, const G1Jac *pts, const uint8_t *signs, const uint8_t *at_inf, const uint32_t *start,
+                   const uint32_t *phi_at, int n, int block) {
+    if (!geometry_ok(n, block) || form < 0 || form > 2) return DS_BAD_ARG;
+    for (int c = 0; c < n; c++)
+        if (start[c + 1] < start[c]) return DS_BAD_ARG;
+    const size_t total = start[n];
+    std::vector<Arg> args = {{nullptr, out, (size_t)n * sizeof(G1Jac)}, {nullptr, met, (size_t)n}, {pts, nullptr, total * sizeof(G1Jac)},
+                             {signs, nullptr, total}, {at_inf, nullptr, total}, {start, nullptr, ((size_t)n + 1) * 4},
+                             {phi_at, nullptr, (size_t)n * 4}};
+    return run_bounded(args, [&](hipStream_t st) {
+        hipLaunchKernelGGL(DS(k_chain30), dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, st, form, (G1Jac *)args[0].dev,
+                           (uint8_t *)args[1].dev, (const G1Jac *)args[2].dev, (const uint8_t *)args[3].dev, (const uint8_t *)args[4].dev,
+                           (const uint32_t *)args[5].dev, (const uint32_t *)args[6].dev, n);
     });
 }
 

@@ -1,6 +1,9 @@
 """Fp on 13 signed 30-bit limbs (c-kzg-4844_amd/csrc/fp30.hpp) and the accumulate loop's mixed addition on it
 (g1_30.hpp), compiled for the host into libhost_shim.so: limb-exact against Python integers, and the addition chain --
-through entry, phi and exit -- against the 28-bit law it replaces in the throughput kernel."""
+through entry, phi and exit -- against the 28-bit law it replaces in the throughput kernel.  The models and the corpora
+are those of tests/fp30_expect.py, shared with the device tests (tests/test_gpu_fp30.py): the whole op list of
+f30_test_ops.hpp runs here through hs_f30_run, the addition, phi and the exit on raw state through hs_madd30_step /
+hs_phi30 / hs_exit30, and the step model is anchored to the oracle's group law."""
 import ctypes as C
 import os
 import random
@@ -11,11 +14,10 @@ import pytest
 from arith_cases import P, R
 from conftest import ORACLE_SO, ROOT, SHIM_SO
 
-N, W = 13, 30
-HALF = 1 << 29
-H13 = sum(HALF << (W * j) for j in range(N))        # value of the digit string (2^29, ..., 2^29), 13 digits
-H12 = sum(HALF << (W * j) for j in range(N - 1))
-PINV390 = pow(P, -1, 1 << 390)
+import fp30_expect as fx
+from fp30_expect import (HALF, N, W, column_product, extreme_operands, model_product, out_limbs, rand_operand,  # noqa: F401
+                         value)
+
 I32x13 = C.c_int32 * N
 
 
@@ -29,73 +31,6 @@ def libs():
     o.og1_equal.restype = C.c_bool
     o.og1_is_inf.restype = C.c_bool
     return o, h
-
-
-def value(limbs):
-    return sum(int(v) << (W * j) for j, v in enumerate(limbs))
-
-
-def out_limbs(v):
-    """what a product or norm() leaves: limbs 0..11 balanced in [-2^29, 2^29), limb 12 the rest"""
-    low = ((v + H12) % (1 << 360)) - H12
-    t = low + H12
-    return [((t >> (W * j)) & ((1 << W) - 1)) - HALF for j in range(N - 1)] + [(v - low) >> 360]
-
-
-def model_product(s):
-    """(s + q p) / 2^390 with the balanced quotient q = -s/p mod 2^390, digits in [-2^29, 2^29)"""
-    q = (((-s * PINV390) % (1 << 390)) + H13) % (1 << 390) - H13
-    t = s + q * P
-    assert t % (1 << 390) == 0
-    return out_limbs(t >> 390)
-
-
-def column_product(a, b, c=None, d=None):
-    """the column walk itself, digit by digit (checks model_product, and the 64-bit bound of every column)"""
-    pl = out_limbs(P)
-    ninv = (-pow(P, -1, 1 << W)) % (1 << W)
-    q, r, acc = [], [], 0
-    for k in range(2 * N - 1):
-        lo, hi = max(0, k - (N - 1)), min(k, N - 1)
-        acc += sum(a[i] * b[k - i] for i in range(lo, hi + 1))
-        if c is not None:
-            acc += sum(c[i] * d[k - i] for i in range(lo, hi + 1))
-        up = 0
-        if c is not None and 10 <= k <= 14:
-            assert abs(acc) < 1 << 63
-            up, acc = acc >> W, acc & ((1 << W) - 1)
-        acc += sum(q[i] * pl[k - i] for i in range(lo, min(hi, len(q) - 1) + 1) if k - i >= 1)
-        if k < N:
-            qk = ((acc * ninv) % (1 << W) + HALF) % (1 << W) - HALF
-            q.append(qk)
-            acc += qk * pl[0]
-        else:
-            r.append(((acc % (1 << W)) + HALF) % (1 << W) - HALF)
-            acc -= r[-1]
-        assert abs(acc) < (1 << 63) - (1 << 60), k     # 2^60: room for the carry bias of two columns
-        assert acc % (1 << W) == 0
-        acc = (acc >> W) + up
-    return r + [acc]
-
-
-def rand_operand(rnd, vb):
-    """normalised limbs of a random value of magnitude <= vb p"""
-    return out_limbs(rnd.randrange(-vb * P, vb * P + 1))
-
-
-def extreme_operands(vb):
-    """the declared bounds, both signs: values at +-vb p, and limbs 0..11 all at +-2^29 (alternating too) under
-    a top limb that keeps the value inside +-vb p"""
-    out = [out_limbs(vb * P), out_limbs(-vb * P), [0] * N]
-    for pattern in ([HALF] * 12, [-HALF] * 12, [HALF, -HALF] * 6, [-HALF, HALF] * 6):
-        for target in (vb * P, -vb * P, 0):
-            top = (target - value(pattern)) >> 360
-            for t in (top, top + 1):
-                cand = pattern + [t]
-                if abs(value(cand)) <= vb * P and abs(t) <= HALF:
-                    out.append(cand)
-    assert len(out) >= 10
-    return out
 
 
 def call(h, name, *ops):
@@ -293,6 +228,119 @@ def test_equal_x_leaves_zz_zero_and_the_fallback_is_exact(libs, base_points):
                 o.og1_add(exp, exp, q)
             got0, met = _chain(h, cp, cs, zi, 0, 2)
             assert met == 1 and o.og1_equal(got0, exp), (same, rest)
+
+
+# ---- the op list of f30_test_ops.hpp on the shared corpora (tests/fp30_expect.py), as g++ builds it ----
+
+def _host_ops(h):
+    h.hs_f30_ops.restype = C.c_char_p
+    return fx.parse_ops(h.hs_f30_ops().decode())
+
+
+def test_op_list_is_the_one_the_law_relies_on(libs):
+    _, h = libs
+    assert _host_ops(h) == fx.REQUIRED_OPS
+
+
+@pytest.mark.parametrize("k", range(len(fx.REQUIRED_OPS)), ids=lambda k: "%s%s" % fx.REQUIRED_OPS[k])
+def test_op_on_its_corpus(libs, k):
+    """every operation limb for limb against the model -- norm at LA = 1 and 2 (the other carry formula) included"""
+    _, h = libs
+    op = _host_ops(h)[k]
+    cases = fx.field_cases(op)
+    a, b, c, d = fx.pack_field(cases)
+    out = (C.c_int32 * (14 * len(cases)))()
+    assert h.hs_f30_run(k, out, a, b, c, d, len(cases)) == 0
+    fx.check_field(op, cases, out)
+    assert h.hs_f30_run(len(fx.REQUIRED_OPS), out, a, b, c, d, 1) == 1     # past the list
+
+
+def _jac(pt):
+    """affine integers -> the 144-byte Jacobian form of the oracle (2^384 domain, Z = 1)"""
+    if pt is None:
+        return bytes(144)
+    r384 = pow(2, 384, P)
+    return b"".join((v * r384 % P).to_bytes(48, "little") for v in (pt[0], pt[1], 1))
+
+
+@pytest.fixture(scope="module")
+def grp(libs):
+    from test_gpu_dev_arith import Group
+    return Group(*libs)
+
+
+def test_step_model_is_the_group_law(grp):
+    """the model of xyzz30_madd_alt, anchored without the code under test: the point an accumulator stands for (weights
+    (1, 2, 0, 1), sign flag) moves by +-entry under the ORACLE's group law; equal x leaves ZZ = 0 mod p"""
+    seen = set()
+    for cl, st, inf, yneg, words, dneg, pt, (st2, inf2, yneg2) in fx.step_cases():
+        seen.add(cl)
+        before = None if inf else fx.state_point(st, bool(yneg))
+        assert inf or before is not None
+        entry = _jac(pt)
+        want = grp.add(_jac(before), grp.neg(entry) if dneg else entry)
+        assert not inf2
+        after = fx.state_point(st2, yneg2)
+        if cl == "equal_x":
+            assert after is None and value(st2[2]) % P == 0
+            assert pt[0] == before[0]
+        else:
+            assert after is not None and grp.equal(_jac(after), want), cl
+            fx.check_state(st2)
+    assert {"chain1", "chain2", "chain50", "shifted50", "empty", "equal_x"} <= seen
+
+
+def test_phi_and_exit_models_are_the_group_law(grp):
+    from arith_cases import LAMBDA
+    mets = 0
+    for st, phi, (words, met) in fx.state_cases():
+        pt = fx.state_point(st, False)
+        assert (pt is None) == bool(met)
+        mets += met
+        if pt is None:
+            continue
+        assert grp.equal(_jac(fx.state_point(phi, False)), grp.mul(_jac(pt), LAMBDA))
+        x, y, zz, zzz = (sum(v << (28 * j) for j, v in enumerate(words[14 * i:14 * i + 14])) for i in range(4))
+        assert (x * pow(zz, -1, P) % P, y * pow(zzz, -1, P) % P) == pt          # a point of one domain: 2^392 cancels
+        assert pow(zz, 3, P) == zzz * zzz * pow(2, 392, P) % P                   # ZZ^3 = ZZZ^2, at 2^392
+    assert mets
+
+
+def test_step_phi_exit_match_the_model(libs):
+    _, h = libs
+    steps = fx.step_cases()
+    n = len(steps)
+    state = (C.c_int32 * (fx.STATE_WORDS * n))(*[v for s in steps for v in fx.flat_state(s[1])])
+    flags = bytes(v for s in steps for v in (s[2], s[3], s[5]))
+    entry = (C.c_uint32 * (fx.ENTRY_WORDS * n))(*[w for s in steps for w in s[4]])
+    out, oflags = (C.c_int32 * (fx.STATE_WORDS * n))(), C.create_string_buffer(2 * n)
+    h.hs_madd30_step(out, oflags, state, flags, entry, n)
+    fx.check_steps(steps, list(out), oflags.raw)
+    states = fx.state_cases()
+    n = len(states)
+    state = (C.c_int32 * (fx.STATE_WORDS * n))(*[v for s in states for v in fx.flat_state(s[0])])
+    out = (C.c_int32 * (fx.STATE_WORDS * n))()
+    h.hs_phi30(out, state, n)
+    ex, met = (C.c_uint32 * (fx.EXIT_WORDS * n))(), C.create_string_buffer(n)
+    h.hs_exit30(ex, met, state, n)
+    fx.check_states(states, list(out), list(ex), met.raw)
+
+
+def test_divergent_chains_are_the_group_law(libs, grp, base_points):
+    """the 64 chains of the device's divergent launch, on the host: the 28-bit law and the 30-bit one with its fallback
+    give the oracle's sum, phi included; the verdict is raised on the equal-x chain alone"""
+    o, _ = libs
+    pts = [grp.affine(p.raw) for p in base_points]
+    chains = fx.divergent_chains(grp, pts)
+    assert sorted(len(c[0]) for c in chains)[:3] == [0, 1, 2]
+    mets = []
+    for cp, cs, zi, phi_at in chains:
+        want = fx.chain_expected(grp, cp, cs, zi, phi_at)
+        for form in (0, 2):
+            got, met = _chain(libs[1], [p[:96] for p in cp], cs, zi, phi_at, form)
+            assert grp.equal(got.raw, want), (len(cp), phi_at, form)
+        mets.append(met)
+    assert mets == [1 if i == 9 else 0 for i in range(64)]
 
 
 def test_generated_includes_are_the_generators_output():
